@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- EM-to-convergence throughput of the per-locus EM hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c2u] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c2u] [--scaling weak|strong] [--dump-outputs DIR]
 
 A step = one pass of the hot path over one batch of synthetic loci that is already
 resident in HBM: EM (init + run to convergence) for every locus, the FPKM/Frac
@@ -53,6 +53,33 @@ WORKLOADS = {
     "c5": "C5 synthetic: the C3 law at 4e8 fragments, bias factors 2^U(-1,1) on the weights; fp32 variant of the EM "
           "timed next to the fp64 path (tolerance sweep: tools/c5_sweep.py)",
 }
+
+
+DUMP_MAX_BYTES = 64 << 20    # --dump-outputs: all files together
+DUMP_SEED = 0x5D0            # the sample drawn where the outputs exceed it
+
+
+def resident_outputs(q):
+    """What a resident chain / front step hands its caller (sbgpu_abundances_t): per isoform and per locus, host arrays."""
+    per_iso = {k: getattr(q, k)[:q.n_iso] for k in ("theta", "fpkm", "frac", "keep", "tpm")}
+    return dict(per_iso, status=q.status[:q.n_loci], iters=q.iters[:q.n_loci])
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs DIR: the arrays the timed path handed its caller in its last timed step, one DIR/<name>.npy each, as
+    float64 (status, iterations and keep are integers, exact in it).  Where they come to more than DUMP_MAX_BYTES, every
+    array longer than its share is cut to a sample of its positions drawn with DUMP_SEED, and DIR/<name>_index.npy says which."""
+    arrays = {k: np.array(v, dtype=np.float64, copy=True).reshape(-1) for k, v in outputs.items()}
+    share = DUMP_MAX_BYTES // 8 // max(2 * len(arrays), 1)     # (elements: an array and its index each)
+    sampled = sum(a.size for a in arrays.values()) * 8 > DUMP_MAX_BYTES
+    os.makedirs(path, exist_ok=True)
+    for k, a in sorted(arrays.items()):
+        if sampled and a.size > share:
+            idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(a.size, share, replace=False))
+            np.save(os.path.join(path, k + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(path, k + ".npy"), a)
+    return {"dir": path, "arrays": sorted(arrays), "sampled": sampled}
 
 
 def make_batch(name, rank):
@@ -286,11 +313,11 @@ def resident_comm(ctx, rank, world, comm, sdist):
     return comm if comm is not None else sdist.HostComm(ctx, rank, world)
 
 
-def chain_leg(args, ctx, dev, rank, world, sdist, torch, strong=False, with_cpu=True, comm=None):
+def chain_leg(args, ctx, dev, rank, world, sdist, torch, strong=False, with_cpu=True, comm=None, dump=None):
     """The fragments -> abundances chain (sbgpu_quantify_device) on the chain sample (strawberry_amd/chain.py): 60 000
     distinct gene models, ~2e8 read pairs resident in HBM.  Weak scaling: every rank its own sample; strong: ONE
     sample, locus l on rank l mod world (no locus data crosses ranks; the caller's FPKM total is the one collective).
-    -> dict for the JSON line (rank 0), None on the other ranks."""
+    dump: --dump-outputs DIR (rank 0's share where the loci are sharded).  -> dict for the JSON line (rank 0), None on the other ranks."""
     from strawberry_amd import chain
     n_frags = float(os.environ.get("SB_CHAIN_FRAGS", "2e8"))
     n_loci = int(float(os.environ.get("SB_CHAIN_LOCI", "60000")))
@@ -301,6 +328,8 @@ def chain_leg(args, ctx, dev, rank, world, sdist, torch, strong=False, with_cpu=
     q = chain.ChainQuantifier(ctx, n_loci=n_loci, n_frags=n_frags, seed=31 + (0 if strong else rank), loci_subset=sub, resident=True,
                               empirical=empirical, comm=resident_comm(ctx, rank, world, comm, sdist))
     wall, _ = timed_steps(q, args.steps, args.warmup, dev, sdist, torch)
+    if dump and rank == 0:
+        dump_outputs(dump, resident_outputs(q))
     counts = torch.tensor([q.n_loci, q.n_frags, q.n_hits], dtype=torch.int64, device=dev)
     sdist.allreduce_sum_(counts)
     per_rank = None
@@ -447,7 +476,7 @@ def front_leg(args, ctx, dev, rank, world, sdist, torch, comm=None):
 
 def chain_main(args, ctx, dev, rank, world, sdist, torch, launch, comm=None):
     """--workload c3-chain: the chain is the headline of the line."""
-    c = chain_leg(args, ctx, dev, rank, world, sdist, torch, strong=args.scaling == "strong", comm=comm)
+    c = chain_leg(args, ctx, dev, rank, world, sdist, torch, strong=args.scaling == "strong", comm=comm, dump=args.dump_outputs)
     if rank != 0:
         return
     out = {
@@ -480,6 +509,8 @@ def front_main(args, ctx, dev, rank, world, sdist, torch, launch, comm=None):
                               comm=resident_comm(ctx, rank, world, comm, sdist))
     torch.cuda.empty_cache()      # the packer's temporaries go back to the driver: the library allocates for itself
     wall, _ = timed_steps(q, args.steps, args.warmup, dev, sdist, torch)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, resident_outputs(q))
     ms = wall / args.steps * 1e3
     if world > 1:
         with_chain = q.compare_with_chain()
@@ -662,7 +693,7 @@ def front_host_main(args, ctx, dev, torch, launch):
     upload_ms = min(up)
     del dbuf
     torch.cuda.empty_cache()
-    steps = max(1, min(args.steps, 3))
+    steps = args.steps if args.steps_given else 3
     if n_parts == 1:
         q = parts[0]
         run = lambda: q.stream_step()                                        # noqa: E731
@@ -675,6 +706,9 @@ def front_host_main(args, ctx, dev, torch, launch):
         res = run()
     torch.cuda.synchronize(dev)
     ms = (time.perf_counter() - t0) / steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, resident_outputs(q) if n_parts == 1 else
+                     {k: res[k] for k in ("theta", "fpkm", "frac", "keep", "tpm", "status", "iters")})
     if n_parts == 1:
         info = res
         same = bool(np.array_equal(q.front_hit_off, want[0][1]) and all(np.array_equal(getattr(q, n)[:size_of(q)[n]], v) for n, v in want[0][0].items()))
@@ -777,7 +811,12 @@ def main():
     ap.add_argument("--no-chain", action="store_true", help="default workload: leave the fragments -> abundances leg out of the line")
     ap.add_argument("--from-host", action="store_true", help="c3-front: the records start in host memory and are pushed in chunks (sbgpu_front_stream_*)")
     ap.add_argument("--no-front", action="store_true", help="default workload: leave the records -> theta leg out of the line (also SB_BENCH_NO_FRONT=1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last one -- the arrays its caller receives "
+                         "(theta, FPKM, Frac, keep, TPM per isoform; status, iterations per locus) -- as DIR/<name>.npy in float64, "
+                         "at most 64 MB in all; rank 0's share where the loci are sharded (bench_outputs/ is ignored by git for it)")
     args = ap.parse_args()
+    args.steps_given = args.steps is not None
     em_workload = args.workload in ("c3", "c2", "c5")
     if args.steps is None:
         args.steps = 200 if em_workload else 20
@@ -866,6 +905,7 @@ def main():
         rb, ib, c5_bias = sbias.make_c5_bias(ctx, batch, seed=0xB1A5 + rank)
         solver.set_bias(rb, ib)
     wall, gpu_ms = timed_steps(quant, args.steps, args.warmup, dev, sdist, torch)
+    timed_res = solver.results() if args.dump_outputs else None     # (the headline's: replaced below by the strong / fp32 run's)
     counts = torch.tensor([batch.n_loci, batch.n_frags], dtype=torch.int64, device=dev)
     sdist.allreduce_sum_(counts)
     n_loci_all, n_frags_all = int(counts[0].item()), int(counts[1].item())
@@ -894,6 +934,8 @@ def main():
         # steps without the collective).  Gathered over one all-reduce of a zero-padded table.
         own_ms = timed_steps.own_wall / args.steps * 1e3
         sres = ssolver.results()
+        if args.scaling == "strong":
+            timed_res = sres
         ssolver.set_timing(True)
         em_probe = []
         for _ in range(3):
@@ -944,6 +986,7 @@ def main():
         _, q32 = make_quant(batch, f32=True, solver=solver)
         wall32, _ = timed_steps(q32, args.steps, args.warmup, dev, sdist, torch)
         res32 = solver.results()
+        timed_res = res32
         ok = np.isin(res64["status"], (0, 3)) & np.isin(res32["status"], (0, 3))
         m = ok[np.repeat(np.arange(batch.n_loci), batch.niso)]
         tpm_rel = np.abs(res32["tpm"] - res64["tpm"])[m] / np.maximum(res64["tpm"][m], 1e-3)
@@ -978,6 +1021,8 @@ def main():
         front_obj = front_leg(args, ctx, dev, rank, world, sdist, torch, comm=comm)
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, timed_res)
     res = res_keep if (chain_obj is not None or front_obj is not None) else solver.results()
     head = strong if args.scaling == "strong" else weak
     ms_per_step = head["ms_per_step"]

@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
@@ -65,3 +67,28 @@ def test_default_step_counts_by_workload():
     assert (out["steps"], out["warmup"]) == (20, 5)
     out = line("--gpus", "2", "--workload", "c2")
     assert (out["steps"], out["warmup"], out["n_gpus"]) == (200, 20, 2)
+
+
+def test_dump_outputs_writes_float64_and_keeps_to_its_size(tmp_path, monkeypatch):
+    """--dump-outputs DIR: one DIR/<name>.npy per output, float64 whatever the output's own type, the values as they were; where
+    the outputs come to more than the cap, the same seeded positions are kept from run to run and DIR/<name>_index.npy names them."""
+    sys.path.insert(0, ROOT)
+    import bench
+    theta, status = np.linspace(0.0, 1.0, 1000), np.arange(40, dtype=np.int32) % 4
+    info = bench.dump_outputs(str(tmp_path / "a"), {"theta": theta, "status": status, "sum_fpkm": 2.5})
+    assert info["sampled"] is False and info["arrays"] == ["status", "sum_fpkm", "theta"]
+    assert sorted(os.listdir(tmp_path / "a")) == ["status.npy", "sum_fpkm.npy", "theta.npy"]
+    for name, want in (("theta", theta), ("status", status), ("sum_fpkm", [2.5])):
+        got = np.load(str(tmp_path / "a" / (name + ".npy")))
+        assert got.dtype == np.float64 and np.array_equal(got, np.asarray(want, np.float64))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2000)
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("b%d" % k)
+        assert bench.dump_outputs(str(d), {"theta": theta, "status": status})["sampled"] is True
+        assert sum(os.path.getsize(str(d / f)) - 128 for f in os.listdir(str(d))) <= 2000   # (128: the .npy header)
+        idx = np.load(str(d / "theta_index.npy"))
+        assert idx.size < theta.size and np.array_equal(np.load(str(d / "theta.npy")), theta[idx.astype(np.int64)])
+        assert np.array_equal(np.load(str(d / "status.npy")), status) and not os.path.exists(str(d / "status_index.npy"))
+        runs.append(idx)
+    assert np.array_equal(runs[0], runs[1])

@@ -469,3 +469,28 @@ def test_gpu_fp32_variant_is_close_and_leaves_fp64_untouched(ctx, oracle):
     m = same[np.repeat(np.arange(b.n_loci), b.niso)]
     rel = np.abs(th32 - r64["theta"])[m] / np.maximum(r64["theta"][m], 1.0)
     assert same.mean() > 0.8 and np.percentile(rel, 99) < 1e-3, (same.mean(), np.percentile(rel, 99))
+
+
+def test_bench_dump_outputs_are_the_timed_steps_results(oracle, tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the timed steps computed: on C2 (bench's batch, seed 0x5742) theta, status and
+    iteration counts are the oracle's, and the epilogue's outputs come with them, all float64."""
+    import json
+    import subprocess
+    import sys
+    from strawberry_amd import synth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "c2", "--steps", "3", "--warmup", "1",
+                        "--no-cpu-baseline", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    got = {f[:-4]: np.load(str(out / f)) for f in os.listdir(str(out))}
+    assert set(got) == {"theta", "status", "iters", "fpkm", "frac", "keep", "tpm", "sum_fpkm"}
+    assert all(a.dtype == np.float64 for a in got.values())
+    b = synth.make_c2(seed=0x5742)
+    theta, status, iters = oracle.em_batch(b.row_off, b.iso_off, b.f_off, b.count, b.F)
+    np.testing.assert_array_equal(got["status"], status)
+    np.testing.assert_array_equal(got["iters"], iters)
+    assert theta_err(got["theta"], theta).max() < THETA_RTOL
+    assert got["tpm"].size == theta.size and abs(got["tpm"].sum() - 1e6) < 1e-3
