@@ -140,7 +140,9 @@ int sbgpu_plan_create(sbgpu_ctx_t *ctx, int64_t n_loci, const int64_t *row_off,
 int sbgpu_plan_destroy(sbgpu_plan_t *plan);
 /* out[0]=n_loci, out[1]=total rows, out[2]=total isoforms, out[3]=total F elements,
  * out[4]=#size classes in use, out[5]=#loci on the streaming (large-shape) path,
- * out[6]=algorithmic bytes of the batch (SURVEY 8(d) B_locus summed, fp64).       */
+ * out[6]=algorithmic bytes of the batch (SURVEY 8(d) B_locus summed, fp64),
+ * out[7]=#loci of out[5] served by the wide multi-workgroup kernel; the other
+ * out[5] - out[7] run on the one-workgroup streaming kernel.                     */
 int sbgpu_plan_info(const sbgpu_plan_t *plan, int64_t out[8]);
 /* Per-class description for profiling: fills up to `cap` rows of 6 int64:
  * {kind (0 tile,1 stream), C, R, G, n_loci, n_waves}.  Returns #classes.          */
@@ -197,7 +199,8 @@ int sbgpu_em_run_device_f32(sbgpu_ctx_t *ctx, const sbgpu_plan_t *plan,
  * (src/bias.cpp is comments), so this is NOT a parity path; bench.py --workload c5 derives row_bias from the bins'
  * GC ratio as sbgpu_binseq_device measures it.  Same result as sbgpu_em_run_device on the pre-multiplied weights up
  * to exp2's rounding.  Served by the tile kernels and the multi-workgroup kernel of the wide loci (up to 512 isoforms);
- * a plan with phases, or with a locus on the streaming fallback (more than 512 isoforms or 256 workgroups): SBGPU_EUNSUPPORTED.
+ * a plan with phases, or with a locus on the streaming fallback (a locus that would need more workgroups than the device
+ * has CUs, or one of more than 64 isoforms without rows): SBGPU_EUNSUPPORTED.
  * The fp32 form covers loci of up to 64 isoforms only (it is a tolerance experiment, not a product path).              */
 int sbgpu_em_run_device_bias(sbgpu_ctx_t *ctx, const sbgpu_plan_t *plan, const int32_t *d_count, const double *d_F,
                              const double *d_row_bias, const double *d_iso_bias, double *d_theta, int32_t *d_status,

@@ -96,7 +96,8 @@ inline int wide_layout_for(int64_t niso, int64_t nrow)
    }
    return best;
 }
-// columns per slice of the two-level exchange: the smallest power of two m with m * G >= npad (m * G < 2 npad)
+// columns per slice of the two-level exchange: the smallest power of two m with m * G >= npad (m * G < 2 npad unless
+// m = 1: G may exceed 2 npad, and the exchange then stages the partials in several passes)
 inline int wide_lb_slice(int npad, int G)
 {
    int lb = 0;
@@ -490,27 +491,34 @@ __device__ __forceinline__ void em_wide_body(const WideArgs &g, const int di, co
          const int lbm = d.lb_slice, m = 1 << lbm;
          const int col0 = w << lbm;
          const int mw = max(0, min(m, n_items - col0)); // the columns of my slice that exist
-         // level 1: thread t = g * m + jj fetches workgroup g's partial of column col0 + jj
-         for (int t = tid; t < (G << lbm); t += kWideThreads) {
-            const int gg = t >> lbm, jj = t & (m - 1);
-            if (jj < mw) {
-               u32x4 gr;
-               fetch(buf1 + ((size_t)gg * NPAD + col0 + jj) * 16, gr);
-               stage[t] = gr;
+         // level 1: thread t = g * m + jj fetches workgroup g's partial of column col0 + jj.  The stage holds 2 NPAD
+         // granules: m * G of them fit while G < NPAD, but with m = 1 G may exceed 2 NPAD (up to n_cu workgroups), so the
+         // workgroups are taken in passes of what fits, added in workgroup order as before
+         const int gstep = (2 * NPAD) >> lbm;
+         double sum = 0.0;
+         unsigned fl = 0;
+         for (int g0 = 0; g0 < G; g0 += gstep) {
+            const int gn = min(gstep, G - g0);
+            for (int t = tid; t < (gn << lbm); t += kWideThreads) {
+               const int gg = t >> lbm, jj = t & (m - 1);
+               if (jj < mw && !aborted) {
+                  u32x4 gr;
+                  fetch(buf1 + ((size_t)(g0 + gg) * NPAD + col0 + jj) * 16, gr);
+                  stage[t] = gr;
+               }
             }
-         }
-         if (aborted) s_misc[3] = 1.0;
-         __syncthreads();
-         if (tid < mw) {
-            double sum = 0.0;
-            unsigned fl = 0;
-            for (int gg = 0; gg < G; ++gg) {
-               const u32x4 e = stage[(gg << lbm) + tid];
-               sum += granule_value(e);
-               fl |= granule_flag(e, round);
+            if (aborted) s_misc[3] = 1.0;
+            __syncthreads();
+            if (tid < mw) {
+               for (int gg = 0; gg < gn; ++gg) {
+                  const u32x4 e = stage[(gg << lbm) + tid];
+                  sum += granule_value(e);
+                  fl |= granule_flag(e, round);
+               }
             }
-            granule_store(buf2 + (size_t)(col0 + tid) * 16, sum, round, fl);
+            if (g0 + gstep < G) __syncthreads(); // (the next pass overwrites the stage)
          }
+         if (tid < mw) granule_store(buf2 + (size_t)(col0 + tid) * 16, sum, round, fl);
          // level 2: the total of my item
          if (tid < n_items) {
             u32x4 gr;

@@ -743,7 +743,8 @@ int sbgpu_plan_create(sbgpu_ctx_t *c, int64_t n_loci, const int64_t *row_off, co
          const int64_t rpb = sb::wide_rows_per_block(layout);
          return std::max<int64_t>(1, (nrow + rpb - 1) / rpb);
       };
-      static const bool no_wide = std::getenv("SBGPU_NO_WIDE") != nullptr;
+      // (read per plan, not cached: a test that sets it after an earlier plan must get the streaming kernel)
+      const bool no_wide = std::getenv("SBGPU_NO_WIDE") != nullptr;
       for (int32_t l : sc.loci) {
          int layout;
          const int64_t G = groups_of(l, layout);
@@ -943,7 +944,7 @@ int sbgpu_plan_info(const sbgpu_plan_t *p, int64_t out[8])
    out[4] = (int64_t)p->host.classes.size();
    out[5] = p->host.n_stream_loci;
    out[6] = p->host.algorithmic_bytes;
-   out[7] = 0;
+   out[7] = p->n_wide_loci;
    return SBGPU_OK;
 }
 
@@ -998,7 +999,7 @@ static int em_run_impl(sbgpu_ctx_t *c, const sbgpu_plan_t *p, const int32_t *d_c
       return fail(SBGPU_EUNSUPPORTED, "sbgpu_em_run_device_f32: the fp32 variant covers loci of up to 64 isoforms in the tile kernels only");
    if ((d_row_bias != nullptr) != (d_iso_bias != nullptr)) return fail(SBGPU_EINVAL, "sbgpu_em_run_device_bias: both bias arrays or none");
    // the bias factors are applied where a kernel loads its tile: the tile kernels and, round 5, the multi-workgroup kernel
-   // of the wide loci; the streaming fallback (more than 512 isoforms or 256 workgroups) and the later phases do not
+   // of the wide loci; the streaming fallback (more than n_cu workgroups, or no rows) and the later phases do not
    bool stream_fallback = false;
    if (p->launches[sb::kStream].n_classes > 0)
       stream_fallback = (int32_t)p->host.classes[p->launches[sb::kStream].first_class].loci.size() > p->n_wide_loci;
@@ -1046,9 +1047,12 @@ static int em_run_impl(sbgpu_ctx_t *c, const sbgpu_plan_t *p, const int32_t *d_c
    // behind them (C3: 0.76 -> 0.72 ms per step; a second stream that shares a hardware queue with the first one or with the
    // block kinds': 0.79).  Which stream that is depends on how the runtime folded the process' streams onto its hardware queues:
    // it is looked for once (find_wave_alt), and without one the runs do not alternate.
+   // SBGPU_WAVE_ALT (experiments): 0 = no alternation, 1..7 = that side stream, unset = the probe's choice (tests pin each schedule)
    if (join_stream && fork && c->wave_alt < 0) {
-      c->wave_alt = find_wave_alt(c);
-      if (std::getenv("SBGPU_HOST_TIMING")) std::fprintf(stderr, "[sbgpu] split runs: the wave kinds' second stream = %d (0: none)\n", c->wave_alt);
+      const char *forced = sb::exp_env("SBGPU_WAVE_ALT");
+      c->wave_alt = forced ? std::max(0, std::min(7, std::atoi(forced))) : find_wave_alt(c);
+      if (std::getenv("SBGPU_HOST_TIMING"))
+         std::fprintf(stderr, "[sbgpu] split runs: the wave kinds' second stream = %d (0: none)%s\n", c->wave_alt, forced ? " (SBGPU_WAVE_ALT)" : "");
    }
    const int wave_slot = (join_stream && fork && c->wave_alt > 0 && !p->zero_bytes && !p->n_wide_desc && (c->split_runs++ & 1)) ? c->wave_alt : 0;
    auto stream_of = [&](int k) -> hipStream_t {

@@ -267,12 +267,19 @@ class ShardQuantifier:
     as in a run over many batches.  pipelined=False: one stream, one buffer set (the steps strictly one after the other)."""
 
     def __init__(self, solver, total_mapped_reads, min_isoform_frac=0.01, effective_len_norm=False,
-                 insert_mean=0.0, filter_by_expression=True, comm=None, f32=False, pipelined=True):
+                 insert_mean=0.0, filter_by_expression=True, comm=None, f32=False, pipelined=True, inputs=None):
         """comm: an AbiComm (the C-ABI collective); None: torch.distributed's default group.
-        f32: run the EM's fp32 variant (BASELINE config 5; not a parity path), the epilogue stays fp64."""
+        f32: run the EM's fp32 variant (BASELINE config 5; not a parity path), the epilogue stays fp64.
+        inputs: optional list of device input sets [(d_count, d_F), ...] of the solver's plan: step i solves set i % K (the
+        sets are read only, so consecutive steps differ without a write the pipeline would have to order); None: the
+        solver's own d_count / d_F every step."""
         self.s = solver
         self.comm = comm
         self.f32 = f32
+        if inputs is not None and (f32 or not len(inputs)):
+            raise ValueError("inputs: a non-empty list of (d_count, d_F), fp64 only")
+        self.inputs = None if inputs is None else list(inputs)
+        self._i = 0
         self.kw = dict(total_mapped_reads=int(total_mapped_reads), min_isoform_frac=min_isoform_frac,
                        effective_len_norm=effective_len_norm, insert_mean=insert_mean,
                        filter_by_expression=filter_by_expression)
@@ -295,8 +302,13 @@ class ShardQuantifier:
             allreduce_sum_(s.d_sum_fpkm)
         s.run_tpm(s.d_sum_fpkm)
 
-    def step(self):
+    def step(self, observe=None):
+        """observe: a callable run once this step's outputs are complete, on the stream that made them (the epilogue's when
+        pipelined) and before its buffer set is handed to a later step -- where a caller can copy them out."""
         s = self.s
+        if self.inputs is not None:
+            s.d_count, s.d_F = self.inputs[self._i % len(self.inputs)]
+        self._i += 1
         if not self.pipelined:
             if self.f32:
                 s.run_em_f32()
@@ -304,6 +316,8 @@ class ShardQuantifier:
             else:
                 s.run_em()
             self._epilogue()
+            if observe is not None:
+                observe()
             return
         torch = s.torch
         main = torch.cuda.current_stream(s.dev)
@@ -321,6 +335,8 @@ class ShardQuantifier:
             self._epi.wait_event(solved)
         with torch.cuda.stream(self._epi):
             self._epilogue()
+            if observe is not None:
+                observe()
             done = torch.cuda.Event()
             done.record(self._epi)
         self._read_done[k] = done

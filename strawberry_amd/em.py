@@ -83,7 +83,7 @@ class Plan:
         out = (C.c_int64 * 8)()
         _lib.check(self.ctx.L.sbgpu_plan_info(self.h, out), "sbgpu_plan_info")
         return {"n_loci": out[0], "n_rows": out[1], "n_iso": out[2], "n_elem": out[3], "n_classes": out[4],
-                "n_stream_loci": out[5], "algorithmic_bytes": out[6]}
+                "n_stream_loci": out[5], "algorithmic_bytes": out[6], "n_wide_loci": out[7]}
 
     def classes(self):
         cap = 1024

@@ -60,6 +60,65 @@ def test_product_does_not_import_oracle():
                 assert "liboracle" not in src and "em_oracle" not in src, os.path.join(dirpath, f)
 
 
+def _static_declarations(src):
+    """The text of every `static` declaration of C++ source `src` (comments removed): from the keyword to the `;` that ends it
+    at bracket depth 0 -- initialisers of any form (`= getenv(..)`, `(getenv(..))`, a lambda `= [] { ... }()`) included --
+    or, for a function definition, its header only (up to the `{` of its body)."""
+    src = re.sub(r"'(?:\\.|[^'\\])'|\"(?:\\.|[^\"\\])*\"|//[^\n]*|/\*.*?\*/", lambda m: m.group(0) if m.group(0)[0] in "'\"" else " ", src,
+                 flags=re.S)
+    out = []
+    for m in re.finditer(r"\bstatic\b", src):
+        i, depth, saw_eq, saw_paren = m.end(), 0, False, False
+        while i < len(src):
+            ch = src[i]
+            if ch in "'\"":
+                lit = re.compile(r"'(?:\\.|[^'\\])'|\"(?:\\.|[^\"\\])*\"").match(src, i)
+                i = lit.end() if lit else i + 1
+                continue
+            if ch in "([{":
+                if ch == "{" and depth == 0 and saw_paren and not saw_eq:
+                    break                                   # a function's body: its header is the declaration
+                depth += 1
+                saw_paren |= ch == "(" and depth == 1
+            elif ch in ")]}":
+                depth -= 1
+            elif ch == "=" and depth == 0:
+                saw_eq = True
+            elif ch == ";" and depth == 0:
+                break
+            i += 1
+        out.append(src[m.start():i])
+    return out
+
+
+def test_fallback_hooks_are_read_per_call():
+    """The tests' hooks that force a fallback route (csrc/api_internal.h lists them) are read on every call: a hook cached in a
+    function-static keeps the value of the process' first call, and a test that sets it later checks the default route twice."""
+    # the scanner on the forms a cached read takes, and on what is not one
+    cached = ['static const bool a = std::getenv("SBGPU_X") != nullptr;', 'static std::string b(std::getenv("SBGPU_X"));',
+              'static const bool c = [] { const char *e = std::getenv("SBGPU_X"); return e != nullptr; }();']
+    fine = ['// the static below is gone\nconst bool d = std::getenv("SBGPU_X") != nullptr;',
+            'static int f(int k) { return std::getenv("SBGPU_X") ? k : 0; }', '/* static */ bool g = std::getenv("SBGPU_X");']
+    assert all(any('"SBGPU_X"' in d for d in _static_declarations(t)) for t in cached)
+    assert not any('"SBGPU_X"' in d for t in fine for d in _static_declarations(t))
+    csrc = os.path.join(ROOT, "strawberry_amd", "csrc")
+    hdr = open(os.path.join(csrc, "api_internal.h")).read()
+    m = re.search(r"tests' hooks that force a fallback route[^(]*\(([^)]*)\)", hdr)
+    assert m, "the hook list in api_internal.h moved"
+    hooks = re.findall(r"SBGPU_[A-Z0-9_]+", m.group(1))
+    assert "SBGPU_NO_WIDE" in hooks and len(hooks) >= 6, hooks
+    seen = set()
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".cpp", ".h")):
+            continue
+        src = open(os.path.join(csrc, f)).read()
+        seen |= {h for h in hooks if '"%s"' % h in src}
+        for decl in _static_declarations(src):
+            for hook in hooks:
+                assert '"%s"' % hook not in decl, "%s: %s is read into a function-static: %s" % (f, hook, decl.strip())
+    assert seen == set(hooks), set(hooks) - seen
+
+
 def test_synth_shapes_and_determinism():
     from strawberry_amd import synth
     a = synth.make_c2(n_loci=50)

@@ -409,6 +409,9 @@ def test_wide_loci_multi_workgroup_kernel(oracle, monkeypatch):
         s = em.EmBatchSolver(b, ctx)
         kinds = s.plan.locus_kinds()
         assert (kinds[:10] == 5).all()
+        # kind 5 is "wide or stream": the route itself is the count of wide loci (the fallback leg has none)
+        info = s.plan.info()
+        assert info["n_stream_loci"] == 10 and info["n_wide_loci"] == (0 if no_wide else 10), (no_wide, info)
         s.run_em()
         r = s.results()
         np.testing.assert_array_equal(r["status"], o_status)
