@@ -804,14 +804,16 @@ int sbgpu_quantify_resident(sbgpu_ctx_t *ctx, const sbgpu_annotation_t *annot, c
  *           incomplete cluster onward are decoded again with the next chunk.  The caller must leave the bytes AND the offsets
  *           of a push untouched until the NEXT push (or end) returns.  From page-locked memory (hipHostMalloc, cudaHostRegister'ed
  *           buffers a driver inflates into) the upload runs beside the kernels; from pageable memory it is staged by the
- *           runtime before the call computes (correct, no overlap).  A cluster whose records exceed a chunk: SBGPU_ESHAPE.
+ *           runtime before the call computes (correct, no overlap).  A cluster whose records exceed a chunk: SBGPU_ESHAPE (the
+ *           records carried from one window to the next -- the first incomplete cluster's onward -- may hold chunk_bytes
+ *           bytes, not one more); an empty push is allowed (no chunk).
  *   end     the last chunk, then ONE sbgpu_quantify_resident over the store (arguments as there; mapped_reads is the
  *           stream's own count): the empirical insert-size law is the whole sample's, TPM needs every locus.
  * Results: those of sbgpu_bam_decode_device .. sbgpu_quantify_resident on the whole sample at once, bit for bit.
  * info: 0 records pushed, 1 accepted records consumed, 2 pairs, 3 unique hits, 4 their features, 5 pairs the span filter
- * dropped, 6 mapped reads, 7 chunks, 8 clusters finished, 9 most bytes carried over, 10 records decoded twice, 11 the LEAST free
+ * dropped, 6 mapped reads, 7 chunks (non-empty pushes), 8 clusters finished, 9 most bytes carried over, 10 records decoded twice, 11 the LEAST free
  * device memory seen since begin (bytes, hipMemGetInfo after every chunk and after the last stage: blocks the library's pool
- * holds idle count as used), 12 bytes per chunk buffer half, 13: 1 once ended, 14 free device memory at begin.               */
+ * holds idle count as used), 12 chunk_bytes (the capacity of a chunk and of a carry), 13: 1 once ended, 14 free device memory at begin.               */
 typedef struct sbgpu_front_stream sbgpu_front_stream_t;
 int sbgpu_front_stream_begin(sbgpu_ctx_t *ctx, const sbgpu_clusters_t *clusters, const sbgpu_bam_opts_t *opts, int64_t chunk_bytes,
                              sbgpu_front_stream_t **out);

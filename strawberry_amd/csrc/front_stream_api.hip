@@ -92,8 +92,10 @@ struct sbgpu_front_stream {
    std::vector<uint8_t> c_strand;
    int64_t n_clusters = 0, k0 = 0; // clusters [0, k0) are done
    sbgpu_bam_opts_t opts = {};
-   // two device buffers: [carry room | chunk]; the chunk in flight (uploaded, not yet computed)
-   int64_t chunk_cap = 0;
+   // two device buffers: [carry room | chunk], each half `room` bytes (chunk_cap rounded up to 256: the chunk lands aligned);
+   // the chunk in flight (uploaded, not yet computed).  chunk_cap is the caller's chunk_bytes exactly: the most bytes a push
+   // and a carry may hold
+   int64_t chunk_cap = 0, room = 0;
    char *buf[2] = {nullptr, nullptr};
    size_t buf_cap[2] = {0, 0};
    int cur = 0;                    // the buffer that holds the pending chunk
@@ -161,10 +163,14 @@ int compute_pending(sbgpu_front_stream *F, bool last)
    const int64_t n_carry = F->carry_n;
    const int64_t n_new = F->pending ? F->pend_records : 0;
    const int64_t n_rec = n_carry + n_new, w_bytes = F->carry_bytes + (F->pending ? F->pend_bytes : 0);
-   char *w0 = F->buf[b] + F->chunk_cap - F->carry_bytes; // (the carry was copied to end where the chunk begins)
-   F->n_chunks += F->pending ? 1 : 0;
+   char *w0 = F->buf[b] + F->room - F->carry_bytes; // (the carry was copied to end where the chunk begins)
+   F->n_chunks += F->pending && F->pend_bytes ? 1 : 0; // (an empty push is no chunk)
    F->redecoded += n_carry;
    if (n_rec == 0) {
+      if (last) { // nothing more will come: the clusters not yet finished are, without hits
+         for (int64_t k = F->k0; k < F->n_clusters; ++k) F->locus_hit_off[(size_t)k + 1] = F->n_hits;
+         F->k0 = F->n_clusters;
+      }
       F->pending = false;
       return SBGPU_OK;
    }
@@ -274,7 +280,8 @@ int compute_pending(sbgpu_front_stream *F, bool last)
    } else {
       for (int64_t k = 0; k < n_done; ++k) F->locus_hit_off[(size_t)(F->k0 + k + 1)] = F->n_hits;
    }
-   F->n_records += n_new, F->n_decoded += n_rec, F->n_accepted += nc > 0 ? reads_done : 0;
+   // (every accepted record counts once: in the window that consumes it -- the last consumes all, reads behind the last cluster too)
+   F->n_records += n_new, F->n_decoded += n_rec, F->n_accepted += last ? n_reads : reads_done;
    F->k0 += n_done;
    // ---- carry: the window's records from carry_rec on, in front of where the next chunk lands in the OTHER buffer
    const int64_t cb = w_bytes - c0;
@@ -285,7 +292,7 @@ int compute_pending(sbgpu_front_stream *F, bool last)
    F->carry_bytes = cb;
    F->carry_max = std::max(F->carry_max, cb);
    if (cb) {
-      SB_TRY(hipMemcpyAsync(F->buf[b ^ 1] + F->chunk_cap - cb, w0 + c0, (size_t)cb, hipMemcpyDeviceToDevice, s));
+      SB_TRY(hipMemcpyAsync(F->buf[b ^ 1] + F->room - cb, w0 + c0, (size_t)cb, hipMemcpyDeviceToDevice, s));
       SB_TRY(hipStreamSynchronize(s));
    }
    F->pending = false;
@@ -314,7 +321,8 @@ int sbgpu_front_stream_begin(sbgpu_ctx_t *c, const sbgpu_clusters_t *cl, const s
    F->c_right.assign(cl->right, cl->right + cl->n_clusters);
    F->c_strand.assign(cl->strand, cl->strand + cl->n_clusters);
    F->opts = *opts;
-   F->chunk_cap = (int64_t)up256((size_t)chunk_bytes);
+   F->chunk_cap = chunk_bytes;
+   F->room = (int64_t)up256((size_t)chunk_bytes);
    F->locus_hit_off.assign((size_t)cl->n_clusters + 1, 0);
    hipError_t e = hipSetDevice(F->device);
    size_t tot = 0;
@@ -326,7 +334,7 @@ int sbgpu_front_stream_begin(sbgpu_ctx_t *c, const sbgpu_clusters_t *cl, const s
       if (e == hipSuccess) e = hipStreamCreateWithPriority(&F->up_stream, hipStreamNonBlocking, least);
    }
    for (int b = 0; b < 2 && e == hipSuccess; ++b) {
-      e = sb::dev_take((size_t)F->chunk_cap * 2, &F->buf[b], &F->buf_cap[b]); // [carry room | chunk]
+      e = sb::dev_take((size_t)F->room * 2, &F->buf[b], &F->buf_cap[b]); // [carry room | chunk]
       if (e == hipSuccess) e = hipEventCreateWithFlags(&F->ev_up[b], hipEventDisableTiming);
    }
    if (e != hipSuccess) {
@@ -360,7 +368,7 @@ int sbgpu_front_stream_push(sbgpu_front_stream_t *F, const uint8_t *bytes, int64
    SB_TRY(F->d_pend[nb].reserve((size_t)(n_records + 1) * 8, cs));
    SB_TRY(hipMemcpyAsync(F->d_pend[nb].p, rec_off, (size_t)(n_records + 1) * 8, hipMemcpyHostToDevice, cs));
    if (!found.empty()) SB_TRY(hipStreamSynchronize(cs)); // (the offsets found here live in this frame)
-   if (n_bytes) SB_TRY(hipMemcpyAsync(F->buf[nb] + F->chunk_cap, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, cs));
+   if (n_bytes) SB_TRY(hipMemcpyAsync(F->buf[nb] + F->room, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, cs));
    SB_TRY(hipEventRecord(F->ev_up[nb], cs));
    F->t_enqueue += std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t_push;
    // ... while the pending one is computed (its carry lands in front of this chunk, in buffer nb)

@@ -268,9 +268,10 @@ class FrontQuantifier(ChainQuantifier):
             i = j
         self.h_chunks, self.chunk_bytes = cuts, int(chunk_bytes)
 
-    def stream_step(self):
+    def stream_step(self, long_read=0):
         """One pass records (host) -> TPM through sbgpu_front_stream_begin / push / end; the results land where step() puts
-        them (resident mode).  -> the stream's info (sbgpu_front_stream_info) as a dict."""
+        them (resident mode).  long_read: sbgpu_front_stream_end's flag (1: a long-read sample, bin weights 1 / L).  -> the
+        stream's info (sbgpu_front_stream_info) as a dict."""
         L, ctx = self.ctx.L, self.ctx
         fs = C.c_void_p()
         _lib.check(L.sbgpu_front_stream_begin(ctx.h, C.byref(self._clusters), C.byref(self._opts), self.chunk_bytes, C.byref(fs)), "sbgpu_front_stream_begin")
@@ -279,8 +280,8 @@ class FrontQuantifier(ChainQuantifier):
             for (i, j, b0, b1, off) in self.h_chunks:
                 _lib.check(L.sbgpu_front_stream_push(fs, base + b0, b1 - b0, off.data_ptr(), j - i), "sbgpu_front_stream_push")
             h = C.c_void_p()
-            _lib.check(L.sbgpu_front_stream_end(fs, C.byref(self._an), None if self.empirical else C.byref(self._ins), self.read_len, 0,
-                                                C.byref(self._par), self.comm.h if self.comm is not None else None, C.byref(self._used),
+            _lib.check(L.sbgpu_front_stream_end(fs, C.byref(self._an), None if self.empirical else C.byref(self._ins), self.read_len,
+                                                int(long_read), C.byref(self._par), self.comm.h if self.comm is not None else None, C.byref(self._used),
                                                 C.byref(self._out), C.byref(h)), "sbgpu_front_stream_end")
             u = self._used
             self.law = {"mean": u.mean, "sd": u.sd, "use_emp": int(u.use_emp), "start_offset": int(u.start_offset),
@@ -375,10 +376,11 @@ class FrontQuantifier(ChainQuantifier):
         return out
 
     @staticmethod
-    def stream_parts(parts, empirical=True, comm=None, min_isoform_frac=0.0):
+    def stream_parts(parts, empirical=True, comm=None, min_isoform_frac=0.0, long_read=0):
         """Several samples (FrontQuantifiers brought to_host with ref_id 0, 1, ...) pushed one after the other as ONE stream: a
-        sample too large to be packed on the device in one piece (BASELINE config 5: 4e8 read pairs).  -> dict of results over
-        all parts' loci (theta, fpkm, frac, tpm, keep, status, iters, law, totals, info)."""
+        sample too large to be packed on the device in one piece (BASELINE config 5: 4e8 read pairs).  long_read: as in
+        stream_step.  -> dict of results over all parts' loci (theta, fpkm, frac, tpm, keep, status, iters, law, totals, info,
+        locus_hit_off: where every cluster's unique hits start in the stream's store)."""
         from .exonbin import Annotation
         p0 = parts[0]
         L, ctx = p0.ctx.L, p0.ctx
@@ -405,10 +407,15 @@ class FrontQuantifier(ChainQuantifier):
                 base = p.h_bytes.data_ptr()
                 for (i, j, b0, b1, off) in p.h_chunks:
                     _lib.check(L.sbgpu_front_stream_push(fs, base + b0, b1 - b0, off.data_ptr(), j - i), "sbgpu_front_stream_push")
-            _lib.check(L.sbgpu_front_stream_end(fs, C.byref(an), None if empirical else C.byref(p0._ins), p0.read_len, 0, C.byref(par),
+            _lib.check(L.sbgpu_front_stream_end(fs, C.byref(an), None if empirical else C.byref(p0._ins), p0.read_len, int(long_read), C.byref(par),
                                                 comm.h if comm is not None else None, C.byref(used), C.byref(out), C.byref(h)), "sbgpu_front_stream_end")
             law = {"mean": used.mean, "sd": used.sd, "use_emp": int(used.use_emp), "start_offset": int(used.start_offset),
                    "end_offset": int(used.end_offset), "total_reads": int(used.total_reads)}
+            if used.use_emp:   # (emp_hist points into the bins handle: copied while it lives)
+                law["emp_hist"] = np.ctypeslib.as_array(used.emp_hist, shape=(used.end_offset - used.start_offset + 1,)).copy()
+            hoff = C.c_void_p()
+            _lib.check(L.sbgpu_front_stream_hits(fs, None, None, C.byref(hoff)), "sbgpu_front_stream_hits")
+            hit_off = np.ctypeslib.as_array(C.cast(hoff, C.POINTER(C.c_int64)), shape=(n_loci + 1,)).copy()
             info = (C.c_int64 * 16)()
             _lib.check(L.sbgpu_front_stream_info(fs, info), "sbgpu_front_stream_info")
             L.sbgpu_bins_destroy(h)
@@ -419,7 +426,7 @@ class FrontQuantifier(ChainQuantifier):
                 "free_device_bytes_at_begin")
         r = {k: (v[:n_iso] if k not in ("status", "iters") else v[:n_loci]) for k, v in res.items()}
         r.update({"law": law, "total_fpkm": float(out.total_fpkm), "total_mapped_reads": int(out.total_mapped_reads),
-                  "info": {k: int(info[i]) for i, k in enumerate(keys)}, "annot": annot})
+                  "info": {k: int(info[i]) for i, k in enumerate(keys)}, "annot": annot, "locus_hit_off": hit_off})
         return r
 
     def chain_step(self):

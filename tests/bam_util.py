@@ -207,8 +207,8 @@ def random_records(rng, n, n_ref=len(REFS)):
 
 
 def toy_run_as_bam_records(d, names):
-    """The read pairs of a toy run (reads.npz: what tools/make_e2e_golden.py wrote as SAM for the reference binary) as BAM
-    records in the file's order -> (record bytes, reference names, clusters as sbgpu_assign_reads wants them)."""
+    """The read pairs (or unpaired reads) of a toy run (reads.npz: what tools/make_e2e_golden.py wrote as SAM for the
+    reference binary) as BAM records in the file's order -> (record bytes, reference names, clusters as sbgpu_assign_reads wants them)."""
     import os
     import e2e_util as U
     z = dict(np.load(os.path.join(d, "reads.npz")))
@@ -237,6 +237,10 @@ def toy_run_as_bam_records(d, names):
             serial += 1
             name = "frag%d" % serial
             tags = [("NH", "C", int(nh)), ("XS", "A", xs)]
+            if not right:
+                # an unpaired read (single-end and long-read runs): flag 0, no mate, the read as long as its blocks
+                recs.append((tid, left[0][0], record(tid, left[0][0] - 1, 0, name, cigar(left), tags=tags)))
+                continue
             recs.append((tid, left[0][0], record(tid, left[0][0] - 1, 1 | 2 | 0x20 | 0x40, name, cigar(left), mtid=tid, mpos=right[0][0] - 1, tags=tags)))
             recs.append((tid, right[0][0], record(tid, right[0][0] - 1, 1 | 2 | 0x10 | 0x80, name, cigar(right), mtid=tid, mpos=left[0][0] - 1, tags=tags)))
     recs.sort(key=lambda r: (r[0], r[1]))                      # the BAM's order: (reference, position), stable
