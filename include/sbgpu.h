@@ -761,6 +761,10 @@ int sbgpu_quantify_device(sbgpu_ctx_t *ctx, const sbgpu_annotation_t *annot, con
  *                    an integer histogram --, all-reduced over `comm`, then InsertSize(frag_lens) (read.cpp:238-262) from
  *                    it: every rank holds the law of the WHOLE sample; returned in *insert_used (emp_hist points into the
  *                    handle).  sbgpu_quantify_host / _device with insert == NULL build their law the same way.
+ *                    With long_read = 1 it is the reference's long-read workflow instead (Strawberry.cpp:335-337): no law
+ *                    is built, every weight is 1/L (as with a given law), *insert_used is all zeros (use_emp = 0,
+ *                    emp_hist NULL), n_frag_lens is 0 and pass 1 only all-reduces the mapped-read total.
+ *                    params->effective_len_norm needs the law's mean, so it is refused there (SBGPU_EINVAL).
  *   mapped_reads     this rank's part of Sample::total_mapped_reads(): sum over its clusters of (int) weighted_mass()
  *                    (alignments.cpp:1372; sbgpu_uniq_dev_info's info[4]); all-reduced over `comm`
  *   params           the reference's globals; total_mapped_reads and insert_mean are NOT read (the call fills them in

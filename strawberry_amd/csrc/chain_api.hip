@@ -59,6 +59,8 @@ static int quantify_impl(sbgpu_ctx_t *c, const sbgpu_annotation_t *an, const sbg
    if (!an->iso_off || !an->exon_off || !an->seg_off || (nh && (!hits->hit_locus || !hits->feat_off || !hit_mass)))
       return api_fail(SBGPU_EINVAL, "sbgpu_quantify_host: null array");
    if (!insert && !insert_used) return api_fail(SBGPU_EINVAL, "sbgpu_quantify_host: insert_used is needed when no insert-size law is given");
+   if (!insert && long_read && ro && ro->params && ro->params->effective_len_norm)
+      return api_fail(SBGPU_EINVAL, "sbgpu_quantify_resident: effective_len_norm subtracts the law's mean, and long reads without a law have none");
    if (on_dev && compat_out) return api_fail(SBGPU_EINVAL, "sbgpu_quantify_device: returns no compat words");
    const int64_t n_iso = an->iso_off[nl], n_exon = an->exon_off[n_iso], n_seg = an->seg_off[nl];
    int64_t n_feat = 0;
@@ -282,12 +284,15 @@ static int quantify_impl(sbgpu_ctx_t *c, const sbgpu_annotation_t *an, const sbg
    int64_t n_frag_lens = 0, hist_len = 0;
    const unsigned long long *h_hist = nullptr; // pinned: the histogram as the device (and the other ranks) made it
    int64_t mapped_total = ro ? ro->mapped_reads : 0;
-   if (insert) {
-      ins = *insert;
+   if (insert || long_read) {
+      // long reads without a law: the reference's long-read workflow builds none (Strawberry.cpp:335-337) and weighs every
+      // bin 1/L (estimate.cpp:236-247), which reads no table; the law in use is all zeros (use_emp = 0)
+      if (insert) ins = *insert;
+      else ins = sbgpu_insert_t{};
       ins.read_len = read_len;
       ins.long_read = long_read;
       // the table of the law, on the copy stream beside the kernels (the bin-weight launch waits for its event)
-      SB_RC(sbgpu_insert_pdf_table(&ins, pdf_len, pdf.data()));
+      if (insert) SB_RC(sbgpu_insert_pdf_table(&ins, pdf_len, pdf.data()));
       SB_TRY(hipMemcpyAsync(d_pdf, pdf.data(), (size_t)pdf_len * 8, hipMemcpyHostToDevice, cs));
       SB_TRY(hipEventRecord(ev_pdf, cs));
       if (ro && ro->comm) { // Sample::total_mapped_reads() over all ranks (alignments.cpp:1372)
@@ -324,7 +329,7 @@ static int quantify_impl(sbgpu_ctx_t *c, const sbgpu_annotation_t *an, const sbg
       h_hist = (const unsigned long long *)pin;
    }
    // called before the bin weights are launched: by then the histogram has long arrived (the grouping's kernels ran behind it)
-   bool law_ready = insert != nullptr;
+   bool law_ready = insert != nullptr || long_read;
    auto finish_law = [&]() -> int {
       if (law_ready) return SBGPU_OK;
       SB_TRY(hipEventSynchronize(ev_hist));
@@ -644,7 +649,7 @@ static int quantify_impl(sbgpu_ctx_t *c, const sbgpu_annotation_t *an, const sbg
    }
    if (insert_used) {
       *insert_used = ins;
-      if (!insert) {
+      if (!insert && ins.use_emp) {
          // the histogram lives on with the handle: behind the weights
          const size_t at = F.size();
          F.insert(F.end(), emp_hist.begin(), emp_hist.end());
