@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- EM-to-convergence throughput of the per-locus EM hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c2u] [--scaling weak|strong] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c2u] [--scaling weak|strong] [--dump-outputs DIR] [--full]
+
+A plain run measures the headline alone: it sets up, runs the W untimed and the K timed steps of the headline's
+configuration, writes --dump-outputs, and prints the line (`metric`, `value`, `unit`, `ms_per_step`, ...).
+Everything else the line can carry -- described below -- is `--full`'s.
 
 A step = one pass of the hot path over one batch of synthetic loci that is already
 resident in HBM: EM (init + run to convergence) for every locus, the FPKM/Frac
@@ -12,15 +16,18 @@ torchrun (one rank per GPU, RCCL).  Two measurements, both in the line:
                   that batch's loci per second -- the headline `value` (default);
   weak_scaling    every rank holds its OWN full-size batch (seed + rank); value = the loci
                   all ranks processed per second (`--scaling weak` makes it the headline).
-At N = 1 the two are the same run.
+At N = 1 the two are the same run; a plain run at N > 1 times only the one `--scaling` names.
 
-Prints ONE JSON line on rank 0.  Besides the driver's fields it carries
+Prints ONE JSON line on rank 0.  With --full, besides the driver's fields it carries the other scaling, the steps timed
+one after the other, the per-kernel times, C5's fp64 twin, the default line's `chain` and `front` legs (--no-chain,
+--no-front leave them out),
   roofline     the dominant kernel against the HBM roofline (algorithmic bytes /
                kernel time) and, because the loop runs on-chip, the
                FP64-VALU view of the same kernel,
   cpu_baseline the reference's EmSolver (oracle/_ref, kind "reference") or the C
                restatement (kind "port") on this box's host cores, bounded sample,
-  parity       the timed batch's GPU result against that CPU run (every locus); a mismatch fails the bench.
+  parity       the timed batch's GPU result against that CPU run (every locus); a mismatch fails the bench
+               (--no-cpu-baseline leaves these two out).
 """
 import argparse
 import json
@@ -313,11 +320,12 @@ def resident_comm(ctx, rank, world, comm, sdist):
     return comm if comm is not None else sdist.HostComm(ctx, rank, world)
 
 
-def chain_leg(args, ctx, dev, rank, world, sdist, torch, strong=False, with_cpu=True, comm=None, dump=None):
+def chain_leg(args, ctx, dev, rank, world, sdist, torch, strong=False, with_cpu=True, comm=None, dump=None, full=True):
     """The fragments -> abundances chain (sbgpu_quantify_device) on the chain sample (strawberry_amd/chain.py): 60 000
     distinct gene models, ~2e8 read pairs resident in HBM.  Weak scaling: every rank its own sample; strong: ONE
     sample, locus l on rank l mod world (no locus data crosses ranks; the caller's FPKM total is the one collective).
-    dump: --dump-outputs DIR (rank 0's share where the loci are sharded).  -> dict for the JSON line (rank 0), None on the other ranks."""
+    dump: --dump-outputs DIR (rank 0's share where the loci are sharded).  full=False: the timed steps and their rates only
+    (no per-rank table, stage times, roofline, CPU baseline or host entry).  -> dict for the JSON line (rank 0), None on the other ranks."""
     from strawberry_amd import chain
     n_frags = float(os.environ.get("SB_CHAIN_FRAGS", "2e8"))
     n_loci = int(float(os.environ.get("SB_CHAIN_LOCI", "60000")))
@@ -332,6 +340,13 @@ def chain_leg(args, ctx, dev, rank, world, sdist, torch, strong=False, with_cpu=
         dump_outputs(dump, resident_outputs(q))
     counts = torch.tensor([q.n_loci, q.n_frags, q.n_hits], dtype=torch.int64, device=dev)
     sdist.allreduce_sum_(counts)
+    if not full:
+        q.close()
+        if rank != 0:
+            return None
+        return {"workload": WORKLOADS["c3-chain"], "scaling": "strong" if strong else "weak", "loci": int(counts[0]),
+                "fragments": int(counts[1]), "ms_per_step": wall / args.steps * 1e3, "loci_per_s": int(counts[0]) * args.steps / wall,
+                "gfrags_per_s": int(counts[1]) * args.steps / wall / 1e9}
     per_rank = None
     if world > 1:   # every rank's own K steps (before it waits for the others), its loci and unique hits
         per_rank = sdist.gather_values([timed_steps.own_wall / args.steps * 1e3, q.n_loci, q.n_hits], rank, world, device=dev)
@@ -476,7 +491,8 @@ def front_leg(args, ctx, dev, rank, world, sdist, torch, comm=None):
 
 def chain_main(args, ctx, dev, rank, world, sdist, torch, launch, comm=None):
     """--workload c3-chain: the chain is the headline of the line."""
-    c = chain_leg(args, ctx, dev, rank, world, sdist, torch, strong=args.scaling == "strong", comm=comm, dump=args.dump_outputs)
+    c = chain_leg(args, ctx, dev, rank, world, sdist, torch, strong=args.scaling == "strong", comm=comm, dump=args.dump_outputs,
+                  full=args.full)
     if rank != 0:
         return
     out = {
@@ -486,8 +502,12 @@ def chain_main(args, ctx, dev, rank, world, sdist, torch, launch, comm=None):
         "mfrags_per_s": c["gfrags_per_s"] * 1e3,
         "config": {"workload": WORKLOADS["c3-chain"], "loci": c["loci"], "fragments": c["fragments"],
                    "sharding": "locus l on rank l mod N of ONE sample" if c["scaling"] == "strong" else "every rank its own sample"},
-        "launch": launch, "chain": c, "roofline": c["roofline"],
+        "launch": launch, "full": args.full,
     }
+    if not args.full:
+        print(json.dumps(out))
+        return
+    out.update({"chain": c, "roofline": c["roofline"]})
     if c.get("cpu_baseline"):
         out["cpu_baseline"], out["parity"] = c["cpu_baseline"], c.get("parity")
     print(json.dumps(out))
@@ -512,6 +532,21 @@ def front_main(args, ctx, dev, rank, world, sdist, torch, launch, comm=None):
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, resident_outputs(q))
     ms = wall / args.steps * 1e3
+    if not args.full:
+        tot = torch.tensor([q.n_loci, q.n_records, q.n_frags], dtype=torch.float64, device=dev)
+        sdist.allreduce_sum_(tot)
+        q.close()
+        if rank != 0:
+            return
+        loci, recs, frags = (float(x) for x in tot.tolist())
+        print(json.dumps({
+            "metric": "loci/s and G records/s, BAM alignment records -> abundances (C3-scale)", "value": loci * args.steps / wall,
+            "unit": "loci/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True,
+            "scaling": "strong" if world > 1 else "weak", "vs_baseline": None, "dtype": "u8 records, u32 intervals, f64", "data": "synthetic",
+            "grecords_per_s": recs * args.steps / wall / 1e9, "mfrags_per_s": frags * args.steps / wall / 1e6,
+            "config": {"workload": WORKLOADS["c3-front"], "loci": int(loci), "read_pairs": int(frags), "records": int(recs)},
+            "insert": "empirical" if q.empirical else "given (-i 250/30)", "launch": launch, "full": False}))
+        return
     if world > 1:
         with_chain = q.compare_with_chain()
         tot = torch.tensor([q.n_loci, q.n_records, q.n_frags, 1 if with_chain["ok"] else 0], dtype=torch.float64, device=dev)
@@ -530,7 +565,7 @@ def front_main(args, ctx, dev, rank, world, sdist, torch, launch, comm=None):
                        "sharding": "locus l (its cluster and its records) on rank l mod N of ONE sample"},
             "insert": "empirical" if q.empirical else "given (-i 250/30)", "tpm": True,
             "law": {k: v for k, v in q.law.items() if k != "emp_hist"}, "total_mapped_reads": q.total_mapped_reads, "total_fpkm": q.total_fpkm,
-            "launch": launch, "per_rank_ms": [p[0] for p in per_rank], "slowest_rank": int(np.argmax([p[0] for p in per_rank])),
+            "launch": launch, "full": True, "per_rank_ms": [p[0] for p in per_rank], "slowest_rank": int(np.argmax([p[0] for p in per_rank])),
             "loci_per_rank": [int(p[1]) for p in per_rank], "records_per_rank": [int(p[2]) for p in per_rank],
             "per_rank_stage_ms": [dict(zip(front.FrontQuantifier.STAGES, p[3:])) for p in per_rank],
             "parity_with_chain": {"ranks_ok": int(oks), "ok": int(oks) == world,
@@ -596,7 +631,7 @@ def front_main(args, ctx, dev, rank, world, sdist, torch, launch, comm=None):
         "config": {"workload": WORKLOADS["c3-front"], "loci": q.n_loci, "read_pairs": q.n_frags, "records": n_rec,
                    "record_bytes": q.n_bytes, "bytes_per_record": q.n_bytes / max(n_rec, 1), "unique_hits": c["unique_hits"],
                    "records_packed_in_s": q.pack_s},
-        "launch": launch, "stage_ms": stage, "stages_sum_ms": float(sum(stage.values())),
+        "launch": launch, "full": True, "stage_ms": stage, "stages_sum_ms": float(sum(stage.values())),
         "insert": "empirical" if q.empirical else "given (-i 250/30)", "tpm": True,
         "law": {k: v for k, v in q.law.items() if k != "emp_hist"}, "total_mapped_reads": q.total_mapped_reads, "total_fpkm": q.total_fpkm,
         "tpm_sum": float(q.tpm[:q.n_iso].sum()),
@@ -659,15 +694,16 @@ def front_host_main(args, ctx, dev, torch, launch):
         q = front.FrontQuantifier(ctx, n_loci=n_loci, n_frags=n_frags / n_parts, seed=31 + 1000 * k, resident=True,
                                   empirical=empirical and n_parts == 1)
         torch.cuda.empty_cache()
-        for _ in range(2):
-            q.step()
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        for _ in range(3):
-            q.step()
-        torch.cuda.synchronize(dev)
-        resident_ms += (time.perf_counter() - t0) / 3 * 1e3
-        want.append(({n: getattr(q, n)[:m].copy() for n, m in size_of(q).items()}, q.front_hit_off.copy()))
+        if args.full:     # the resident pass: its time, and the results the chunked pass must reproduce
+            for _ in range(2):
+                q.step()
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            for _ in range(3):
+                q.step()
+            torch.cuda.synchronize(dev)
+            resident_ms += (time.perf_counter() - t0) / 3 * 1e3
+            want.append(({n: getattr(q, n)[:m].copy() for n, m in size_of(q).items()}, q.front_hit_off.copy()))
         t0 = time.perf_counter()
         host = q.to_host(chunk, pinned=pinned, ref_id=k)
         to_host_s += time.perf_counter() - t0
@@ -679,20 +715,21 @@ def front_host_main(args, ctx, dev, torch, launch):
         parts.append(q)
     n_bytes, n_records = sum(q.n_bytes for q in parts), sum(q.n_records for q in parts)
     free0 = torch.cuda.mem_get_info(dev)[0]
-    # the upload alone: the same chunks, host -> one device buffer, nothing else
-    dbuf = torch.empty(chunk, dtype=torch.uint8, device=dev)
-    up = []
-    for _ in range(2):
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        for q in parts:
-            for (i, j, b0, b1, off) in q.h_chunks:
-                dbuf[:b1 - b0].copy_(q.h_bytes[b0:b1], non_blocking=True)
-        torch.cuda.synchronize(dev)
-        up.append((time.perf_counter() - t0) * 1e3)
-    upload_ms = min(up)
-    del dbuf
-    torch.cuda.empty_cache()
+    if args.full:
+        # the upload alone: the same chunks, host -> one device buffer, nothing else
+        dbuf = torch.empty(chunk, dtype=torch.uint8, device=dev)
+        up = []
+        for _ in range(2):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            for q in parts:
+                for (i, j, b0, b1, off) in q.h_chunks:
+                    dbuf[:b1 - b0].copy_(q.h_bytes[b0:b1], non_blocking=True)
+            torch.cuda.synchronize(dev)
+            up.append((time.perf_counter() - t0) * 1e3)
+        upload_ms = min(up)
+        del dbuf
+        torch.cuda.empty_cache()
     steps = args.steps if args.steps_given else 3
     if n_parts == 1:
         q = parts[0]
@@ -709,6 +746,18 @@ def front_host_main(args, ctx, dev, torch, launch):
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, resident_outputs(q) if n_parts == 1 else
                      {k: res[k] for k in ("theta", "fpkm", "frac", "keep", "tpm", "status", "iters")})
+    if not args.full:
+        n_loci_all, n_pairs_all = sum(q.n_loci for q in parts), sum(q.n_frags for q in parts)
+        print(json.dumps({
+            "metric": "loci/s and G records/s, BAM alignment records in HOST memory -> abundances (C3-scale)", "value": n_loci_all / (ms * 1e-3),
+            "unit": "loci/s", "n_gpus": 1, "steps": steps, "warmup": 1, "ms_per_step": ms, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "u8 records, u32 intervals, f64", "data": "synthetic",
+            "grecords_per_s": n_records / (ms * 1e-3) / 1e9, "mfrags_per_s": n_pairs_all / (ms * 1e-3) / 1e6,
+            "config": {"workload": WORKLOADS["c3-front"] + "; the records start in HOST memory and are pushed in chunks (sbgpu_front_stream_*)",
+                       "loci": n_loci_all, "read_pairs": n_pairs_all, "records": n_records, "record_bytes": n_bytes, "chunk_bytes": chunk,
+                       "host_memory": "page-locked" if pinned_all else "pageable", "parts": n_parts, "note": note},
+            "insert": "empirical" if empirical else "given (-i 250/30)", "launch": launch, "full": False}))
+        return
     if n_parts == 1:
         info = res
         same = bool(np.array_equal(q.front_hit_off, want[0][1]) and all(np.array_equal(getattr(q, n)[:size_of(q)[n]], v) for n, v in want[0][0].items()))
@@ -735,7 +784,7 @@ def front_host_main(args, ctx, dev, torch, launch):
         "config": {"workload": WORKLOADS["c3-front"] + "; the records start in HOST memory and are pushed in chunks (sbgpu_front_stream_*)",
                    "loci": n_loci_all, "read_pairs": n_pairs_all, "records": n_records, "record_bytes": n_bytes, "chunk_bytes": chunk,
                    "chunks": info["chunks"], "host_memory": "page-locked" if pinned_all else "pageable", "parts": n_parts, "note": note},
-        "launch": launch, "insert": "empirical" if empirical else "given (-i 250/30)", "tpm": True,
+        "launch": launch, "full": True, "insert": "empirical" if empirical else "given (-i 250/30)", "tpm": True,
         "law": {k: v for k, v in law.items() if k != "emp_hist"}, "tpm_sum": tpm_sum,
         "from_host": {
             "ms_per_step": ms, "upload_alone_ms": upload_ms, "upload_GBps": n_bytes / upload_ms / 1e6, "resident_pass_ms": resident_ms,
@@ -790,10 +839,51 @@ def dry_run(args):
     if rank == 0:
         print(json.dumps({"dry_run": True, "n_gpus": world, "ranks_seen": int(n[0]), "rank_sum": int(n[1]),
                           "max_over_ranks": float(t.item()), "steps": args.steps, "warmup": args.warmup,
-                          "workload": args.workload, "scaling": args.scaling,
+                          "workload": args.workload, "scaling": args.scaling, "full": args.full,
                           "per_rank_ms": [float(x) for x in tab[:, 0]], "slowest_rank": int(tab[:, 0].argmax()),
                           "capped_loci_per_rank": [int(x) for x in tab[:, 1]], "value_strong": None, "value_weak": None,
                           "note": "SB_BENCH_DRY_RUN: launch + collectives only, nothing measured"}))
+
+
+def em_headline(args, ctx, dev, rank, world, sdist, torch, em, launch, collective, make_quant):
+    """A plain run of an EM workload (c3, c2, c2u, c3t, c5): the headline's batch, its W + K steps, --dump-outputs and the line --
+    the same batch and steps the --full line takes its headline from: weak (every rank its own batch; the one run at N = 1) or,
+    at N > 1 under --scaling strong, ONE batch sharded over the ranks; C5: the fp32 variant on the weak batch."""
+    c5 = args.workload == "c5"
+    strong = world > 1 and args.scaling == "strong" and not c5
+    if strong:
+        whole = make_batch(args.workload, 0)
+        batch = whole.select(sdist.shard_loci(whole.nrow, whole.niso, world)[rank])
+    else:
+        batch = make_batch(args.workload, rank)
+    solver = em.EmBatchSolver(batch, ctx)
+    if c5:
+        from strawberry_amd import bias as sbias
+        rb, ib, _ = sbias.make_c5_bias(ctx, batch, seed=0xB1A5 + rank)
+        solver.set_bias(rb, ib)
+    _, quant = make_quant(batch, f32=c5, solver=solver)
+    wall, _ = timed_steps(quant, args.steps, args.warmup, dev, sdist, torch)
+    if strong:
+        n_loci, n_frags, frags_per_gpu = whole.n_loci, whole.n_frags, whole.n_frags    # (rank 0's own batch is the whole one)
+    else:
+        counts = torch.tensor([batch.n_loci, batch.n_frags], dtype=torch.int64, device=dev)
+        sdist.allreduce_sum_(counts)
+        n_loci, n_frags, frags_per_gpu = int(counts[0].item()), int(counts[1].item()), batch.n_frags
+    if rank != 0:
+        return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, solver.results())
+    sharding = ("independent loci per rank (own batch each), 1 all-reduce (8 B) per step" if args.scaling == "weak" else
+                "one %d-locus batch, LPT shards by elements x predicted iterations (dist.shard_loci), no locus data crosses ranks, "
+                "1 all-reduce (8 B) per step" % (whole.n_loci if strong else batch.n_loci))
+    print(json.dumps({
+        "metric": "loci/s, EM-to-convergence (+ FPKM/TPM epilogue), %s" % args.workload.upper(),
+        "value": n_loci * args.steps / wall, "unit": "loci/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": wall / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+        "dtype": "f32" if c5 else "f64", "data": "synthetic", "mfrags_per_s": n_frags * args.steps / wall / 1e6,
+        "config": {"workload": WORKLOADS[args.workload], "loci_per_gpu": batch.n_loci, "fragments_per_gpu": frags_per_gpu,
+                   "sharding": sharding, "collective": collective, "steps_pipelined": bool(quant.pipelined)},
+        "launch": launch, "full": False}))
 
 
 def main():
@@ -815,6 +905,10 @@ def main():
                     help="after the timed steps, write what the timed path computed in its last one -- the arrays its caller receives "
                          "(theta, FPKM, Frac, keep, TPM per isoform; status, iterations per locus) -- as DIR/<name>.npy in float64, "
                          "at most 64 MB in all; rank 0's share where the loci are sharded (bench_outputs/ is ignored by git for it)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline: the other scaling, the steps one after the other, "
+                         "per-kernel times and rooflines, C5's fp64 twin, the default line's chain and front legs, the CPU baseline "
+                         "and the parity against it (default: a plain run -- set-up, warm-up, the timed steps, --dump-outputs, the line)")
     args = ap.parse_args()
     args.steps_given = args.steps is not None
     em_workload = args.workload in ("c3", "c2", "c5")
@@ -893,6 +987,9 @@ def main():
                                              pipelined=os.environ.get("SB_PIPELINE", "1" if args.steps >= 10 else "0") != "0")  # quant-only (-r): keep all
         # (a run of batches: from ten steps on -- the first steps of a burst run side by side in pairs before the kinds have
         # drifted apart, 5 steps take 0.88 ms each as a run and 0.83 one after the other, 20 take 0.74, 200 take 0.70)
+
+    if not args.full:
+        return em_headline(args, ctx, dev, rank, world, sdist, torch, em, launch, collective, make_quant)
 
     # ---- weak scaling: every rank holds its OWN full-size batch
     batch = make_batch(args.workload, rank)
@@ -1092,7 +1189,7 @@ def main():
         "value_strong": strong["value"], "value_weak": weak["value"],
         "per_rank_ms": strong.get("per_rank_ms"), "slowest_rank": strong.get("slowest_rank"),
         "capped_loci_per_rank": strong.get("capped_loci_per_rank"),
-        "roofline": roofline,
+        "roofline": roofline, "full": True,
     }
     if chain_obj is not None:
         out["chain"] = chain_obj

@@ -69,6 +69,19 @@ def test_default_step_counts_by_workload():
     assert (out["steps"], out["warmup"], out["n_gpus"]) == (200, 20, 2)
 
 
+def test_full_is_off_by_default_and_reaches_the_ranks():
+    """A plain run measures the headline alone; `--full` asks for everything else the line can carry, and the children of
+    `--gpus 2` get it from the parent's command line."""
+    def line(*args):
+        r = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "1", *args], env=_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line()["full"] is False
+    assert line("--full")["full"] is True
+    out = line("--gpus", "2", "--full")
+    assert out["full"] is True and out["n_gpus"] == 2
+
+
 def test_dump_outputs_writes_float64_and_keeps_to_its_size(tmp_path, monkeypatch):
     """--dump-outputs DIR: one DIR/<name>.npy per output, float64 whatever the output's own type, the values as they were; where
     the outputs come to more than the cap, the same seeded positions are kept from run to run and DIR/<name>_index.npy names them."""

@@ -497,3 +497,27 @@ def test_bench_dump_outputs_are_the_timed_steps_results(oracle, tmp_path):
     np.testing.assert_array_equal(got["iters"], iters)
     assert theta_err(got["theta"], theta).max() < THETA_RTOL
     assert got["tpm"].size == theta.size and abs(got["tpm"].sum() - 1e6) < 1e-3
+
+
+def test_bench_plain_line_is_the_headline_and_full_adds_the_rest():
+    """A plain `bench.py` run times the headline alone -- its line has the headline's fields and nothing measured beside
+    them; `--full` adds the per-kernel times, the roofline and the steps one after the other, and the CPU parity where asked."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def line(*args):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "c2", "--steps", "12", "--warmup", "2", *args],
+                           capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return json.loads(r.stdout.strip().splitlines()[-1])
+    plain = line()
+    assert plain["full"] is False and plain["steps"] == 12 and plain["warmup"] == 2 and plain["n_gpus"] == 1
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["unit"] == "loci/s" and plain["dtype"] == "f64"
+    assert plain["higher_is_better"] is True and plain["config"]["loci_per_gpu"] == 10000
+    assert not {"roofline", "cpu_baseline", "parity", "weak_scaling", "strong_scaling", "em_status", "chain", "front"} & set(plain)
+    full = line("--full")
+    assert full["full"] is True and full["metric"] == plain["metric"] and full["config"]["steps_pipelined"] == plain["config"]["steps_pipelined"]
+    assert full["roofline"]["kernel_ms"] > 0 and full["config"]["ms_per_step_one_after_the_other"] > 0
+    assert full["parity"]["ok"] and full["parity"]["checked_loci"] == 10000

@@ -37,12 +37,12 @@ def test_records_to_theta_equals_the_chain_on_the_same_sample():
 
 
 def test_bench_c3_front_shards_the_sample_over_two_ranks():
-    """`bench.py --workload c3-front --gpus 2` (here: two ranks on the one GPU): ONE sample, locus l -- its cluster and its
+    """`bench.py --workload c3-front --gpus 2 --full` (here: two ranks on the one GPU): ONE sample, locus l -- its cluster and its
     records -- on rank l mod 2, every stage on the rank's own records, nothing but the step's barrier between the ranks.
     Every rank's theta must be the chain's on its shard; the line carries the ranks' own times and stage times."""
     env = dict(os.environ, SB_FRONT_LOCI="3000", SB_FRONT_FRAGS="3e6", MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c3-front", "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["parity_with_chain"]["ok"] and d["parity_with_chain"]["ranks_ok"] == 2
@@ -52,11 +52,11 @@ def test_bench_c3_front_shards_the_sample_over_two_ranks():
 
 
 def test_default_bench_line_carries_the_front_leg_and_survives_its_failure():
-    """`python bench.py` (the driver's command) times records -> theta as a leg of the default line ("front").  The leg must never
+    """`python bench.py --full` times records -> theta as a leg of the default line ("front").  The leg must never
     cost the line: where it cannot run (here: a sample that cannot fit the device) the line comes out without its numbers."""
     def run(**kw):
         env = dict(os.environ, MASTER_ADDR="127.0.0.1", **kw)
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-chain", "--no-cpu-baseline", "--steps", "3", "--warmup", "1"],
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-chain", "--no-cpu-baseline", "--steps", "3", "--warmup", "1"],
                            env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         return json.loads(r.stdout.strip().splitlines()[-1])

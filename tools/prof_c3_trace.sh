@@ -5,7 +5,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof_c3_trace
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --output-format csv -d $OUT -o c3 -- python3 $REPO/bench.py --no-front --no-chain --no-cpu-baseline --steps 12 --warmup 3 > $OUT/run.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --output-format csv -d $OUT -o c3 -- python3 $REPO/bench.py --full --no-front --no-chain --no-cpu-baseline --steps 12 --warmup 3 > $OUT/run.log 2>&1
 tail -1 $OUT/run.log | cut -c1-200
 python3 - "$OUT" <<'PY'
 import csv, glob, sys

@@ -10,15 +10,15 @@ cd $REPO
 (timeout 1200 python -m pytest tests -m gpu -q 2>&1 | tail -4) > $SUM/${R}_pytest_gpu.txt
 cd /tmp && export TMPDIR=/tmp
 # kernel trace + stats in their own runs (the bench's own default command: 200 steps as a run of batches); every PMC group in its own run, never with a trace domain
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c3 -o em -- python3 $REPO/bench.py --no-chain --no-front --no-cpu-baseline > $OUT/stats_c3.log 2>&1
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c2 -o em -- python3 $REPO/bench.py --workload c2 --no-cpu-baseline > $OUT/stats_c2.log 2>&1
-timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_c3 -o em -- python3 $REPO/bench.py --no-chain --no-front --no-cpu-baseline --steps 3 --warmup 1 > $OUT/pmc_fetch.log 2>&1
-timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_c3 -o em -- python3 $REPO/bench.py --no-chain --no-front --no-cpu-baseline --steps 3 --warmup 1 > $OUT/pmc_write.log 2>&1
-timeout 600 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY --output-format csv -d $OUT/pmc_sq_c3 -o em -- python3 $REPO/bench.py --no-chain --no-front --no-cpu-baseline --steps 3 --warmup 1 > $OUT/pmc_sq.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c3 -o em -- python3 $REPO/bench.py --full --no-chain --no-front --no-cpu-baseline > $OUT/stats_c3.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c2 -o em -- python3 $REPO/bench.py --full --workload c2 --no-cpu-baseline > $OUT/stats_c2.log 2>&1
+timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_c3 -o em -- python3 $REPO/bench.py --full --no-chain --no-front --no-cpu-baseline --steps 3 --warmup 1 > $OUT/pmc_fetch.log 2>&1
+timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_c3 -o em -- python3 $REPO/bench.py --full --no-chain --no-front --no-cpu-baseline --steps 3 --warmup 1 > $OUT/pmc_write.log 2>&1
+timeout 600 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY --output-format csv -d $OUT/pmc_sq_c3 -o em -- python3 $REPO/bench.py --full --no-chain --no-front --no-cpu-baseline --steps 3 --warmup 1 > $OUT/pmc_sq.log 2>&1
 # the matrix pipe: instructions, busy cycles (north star: "MFMA-busy where used" -- v_mfma_f64_4x4x4 is the cross-lane reducer of every EM kernel)
-timeout 600 rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CYCLES SQ_INST_CYCLES_VMEM --output-format csv -d $OUT/pmc_mfma_c3 -o em -- python3 $REPO/bench.py --no-chain --no-front --no-cpu-baseline --steps 3 --warmup 1 > $OUT/pmc_mfma.log 2>&1
-timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_c2 -o em -- python3 $REPO/bench.py --workload c2 --no-cpu-baseline --steps 3 --warmup 1 > $OUT/pmc_fetch_c2.log 2>&1
-timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_c2 -o em -- python3 $REPO/bench.py --workload c2 --no-cpu-baseline --steps 3 --warmup 1 > $OUT/pmc_write_c2.log 2>&1
+timeout 600 rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CYCLES SQ_INST_CYCLES_VMEM --output-format csv -d $OUT/pmc_mfma_c3 -o em -- python3 $REPO/bench.py --full --no-chain --no-front --no-cpu-baseline --steps 3 --warmup 1 > $OUT/pmc_mfma.log 2>&1
+timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_c2 -o em -- python3 $REPO/bench.py --full --workload c2 --no-cpu-baseline --steps 3 --warmup 1 > $OUT/pmc_fetch_c2.log 2>&1
+timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_c2 -o em -- python3 $REPO/bench.py --full --workload c2 --no-cpu-baseline --steps 3 --warmup 1 > $OUT/pmc_write_c2.log 2>&1
 cd $REPO
 python3 - "$OUT" "$SUM" "$R" <<'PY'
 import collections, csv, glob, json, shutil, sys
@@ -41,19 +41,19 @@ for w in ("c3", "c2"):
     json.dump(summary, open("%s/%s_%s_pmc_summary.json" % (summ, r, w), "w"), indent=1)
 PY
 cd /tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_chain -o ch -- python3 $REPO/bench.py --workload c3-chain --no-cpu-baseline --steps 3 --warmup 1 > $OUT/stats_chain.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_chain -o ch -- python3 $REPO/bench.py --full --workload c3-chain --no-cpu-baseline --steps 3 --warmup 1 > $OUT/stats_chain.log 2>&1
 for pmc in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_INSTS_VALU SQ_INSTS_SALU"; do
   tag=$(echo $pmc | cut -d' ' -f1)
-  timeout 900 rocprofv3 --pmc $pmc --output-format csv -d $OUT/pmc_${tag}_chain -o ch -- python3 $REPO/bench.py --workload c3-chain --no-cpu-baseline --steps 2 --warmup 1 > $OUT/pmc_${tag}_chain.log 2>&1
+  timeout 900 rocprofv3 --pmc $pmc --output-format csv -d $OUT/pmc_${tag}_chain -o ch -- python3 $REPO/bench.py --full --workload c3-chain --no-cpu-baseline --steps 2 --warmup 1 > $OUT/pmc_${tag}_chain.log 2>&1
 done
 # the chain step's timeline on the GPU: every kernel with the idle gap before it (tools/chain_gpu_gaps.py)
-timeout 900 rocprofv3 --kernel-trace -d $OUT/trace_chain -o ch -- python3 $REPO/bench.py --workload c3-chain --no-cpu-baseline --steps 6 --warmup 2 > $OUT/trace_chain.log 2>&1
+timeout 900 rocprofv3 --kernel-trace -d $OUT/trace_chain -o ch -- python3 $REPO/bench.py --full --workload c3-chain --no-cpu-baseline --steps 6 --warmup 2 > $OUT/trace_chain.log 2>&1
 python3 $REPO/tools/chain_gpu_gaps.py $(find $OUT/trace_chain -name "ch_results.db" | head -1) > $SUM/${R}_c3chain_timeline.txt 2>&1
 # the wide-locus kernel on C3-T: stats and counters
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c3t -o w -- python3 $REPO/bench.py --workload c3t --no-cpu-baseline --steps 3 --warmup 1 > $OUT/stats_c3t.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c3t -o w -- python3 $REPO/bench.py --full --workload c3t --no-cpu-baseline --steps 3 --warmup 1 > $OUT/stats_c3t.log 2>&1
 for pmc in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU" "SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CYCLES"; do
   tag=$(echo $pmc | cut -d' ' -f1)
-  timeout 900 rocprofv3 --pmc $pmc --output-format csv -d $OUT/pmc_${tag}_c3t -o w -- python3 $REPO/bench.py --workload c3t --no-cpu-baseline --steps 2 --warmup 1 > $OUT/pmc_${tag}_c3t.log 2>&1
+  timeout 900 rocprofv3 --pmc $pmc --output-format csv -d $OUT/pmc_${tag}_c3t -o w -- python3 $REPO/bench.py --full --workload c3t --no-cpu-baseline --steps 2 --warmup 1 > $OUT/pmc_${tag}_c3t.log 2>&1
 done
 cd $REPO
 for f in $(find $OUT/stats_chain -name "*kernel_stats.csv"); do cp $f $SUM/${R}_c3chain_kernel_stats.csv; done
@@ -75,12 +75,12 @@ for w, name in (("chain", "c3chain"), ("c3t", "c3t")):
 PY
 # the bench lines come after the counter passes: bench.py reads roofline.traffic from profiles/*_pmc_summary.json
 cp $SUM/${R}_c3_pmc_summary.json $SUM/${R}_c2_pmc_summary.json $SUM/${R}_c3chain_pmc_summary.json $SUM/${R}_c3t_pmc_summary.json $REPO/profiles/ 2>/dev/null
-(timeout 900 python bench.py 2>/dev/null | tail -1) > $SUM/${R}_bench_c3.json
-(timeout 600 python bench.py --workload c2 2>/dev/null) > $SUM/${R}_bench_c2.json
-(timeout 900 python bench.py --workload c5 --no-cpu-baseline 2>/dev/null) > $SUM/${R}_bench_c5.json
-(timeout 900 python bench.py --workload c3t --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null) > $SUM/${R}_bench_c3t.json
-(timeout 900 python bench.py --workload c3-chain --steps 10 --warmup 3 2>/dev/null) > $SUM/${R}_bench_c3chain.json
-(SB_DIST_TIMEOUT_S=120 timeout 900 python bench.py --gpus 2 --steps 10 --warmup 3 2>/dev/null | tail -1) > $SUM/${R}_bench_c3_2ranks_one_gpu.json
+(timeout 900 python bench.py --full 2>/dev/null | tail -1) > $SUM/${R}_bench_c3.json
+(timeout 600 python bench.py --full --workload c2 2>/dev/null) > $SUM/${R}_bench_c2.json
+(timeout 900 python bench.py --full --workload c5 --no-cpu-baseline 2>/dev/null) > $SUM/${R}_bench_c5.json
+(timeout 900 python bench.py --full --workload c3t --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null) > $SUM/${R}_bench_c3t.json
+(timeout 900 python bench.py --full --workload c3-chain --steps 10 --warmup 3 2>/dev/null) > $SUM/${R}_bench_c3chain.json
+(SB_DIST_TIMEOUT_S=120 timeout 900 python bench.py --full --gpus 2 --steps 10 --warmup 3 2>/dev/null | tail -1) > $SUM/${R}_bench_c3_2ranks_one_gpu.json
 bash tools/profile_exonbin.sh $R > /dev/null 2>&1
 cp $OUT/exonbin/summary.json $SUM/${R}_exonbin_summary.json
 cp $OUT/exonbin/stats/eb_kernel_stats.csv $SUM/${R}_exonbin_kernel_stats.csv
@@ -112,11 +112,11 @@ for f in $(find $OUT/stats_bamdecode -name "*kernel_stats.csv"); do cp $f $SUM/$
 # (c3-front) with its kernel rows; instructions per algorithmic FMA of the tile kernels by layout; a full wide-locus tile's counters
 ((timeout 600 python tools/probe_strong_kinds.py; echo; echo "# the CHAIN's shards (tools/probe_strong_chain.py)"; timeout 900 python tools/probe_strong_chain.py) 2>/dev/null | grep -v amdgpu.ids) > $SUM/${R}_strong_shards.txt
 ((echo "# records -> theta (bench.py --workload c3-front --gpus N), a rank at a time (tools/probe_strong_front.py)"; timeout 1200 python tools/probe_strong_front.py 2>/dev/null | grep world) > $SUM/${R}_strong_shards_front.txt)
-(cd /tmp && timeout 1500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/stats_front_$R -o fr -- python3 $REPO/bench.py --workload c3-front --steps 2 --warmup 1 --no-cpu-baseline > /tmp/stats_front_$R.log 2>&1)
+(cd $TMPDIR && timeout 1500 rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/stats_front_$R -o fr -- python3 $REPO/bench.py --full --workload c3-front --steps 2 --warmup 1 --no-cpu-baseline > $TMPDIR/stats_front_$R.log 2>&1)
 for f in $(find /tmp/stats_front_$R -name "*kernel_stats.csv"); do cp $f $SUM/${R}_c3front_kernel_stats.csv; done
 # HBM traffic counters of the records -> theta pass (every kernel of one step; separate FETCH / WRITE runs)
 for pmc in FETCH_SIZE WRITE_SIZE; do
-  (cd /tmp && timeout 1500 rocprofv3 --pmc $pmc --output-format csv -d /tmp/pmc_${pmc}_front_$R -o fr -- python3 $REPO/bench.py --workload c3-front --steps 1 --warmup 1 --no-cpu-baseline > /tmp/pmc_${pmc}_front_$R.log 2>&1)
+  (cd $TMPDIR && timeout 1500 rocprofv3 --pmc $pmc --output-format csv -d $TMPDIR/pmc_${pmc}_front_$R -o fr -- python3 $REPO/bench.py --full --workload c3-front --steps 1 --warmup 1 --no-cpu-baseline > $TMPDIR/pmc_${pmc}_front_$R.log 2>&1)
 done
 python3 - "$SUM" "$R" <<'PY'
 import collections, csv, ctypes, glob, json, sys
@@ -133,10 +133,10 @@ summary["_build_id"] = L.sbgpu_build_id().decode()
 json.dump(summary, open("%s/%s_c3front_pmc_summary.json" % (summ, r), "w"), indent=1)
 PY
 cp $SUM/${R}_c3front_pmc_summary.json $REPO/profiles/ 2>/dev/null
-(timeout 1500 python bench.py --workload c3-front --steps 5 --warmup 2 2>/dev/null | tail -1) > $SUM/${R}_bench_c3front.json
+(timeout 1500 python bench.py --full --workload c3-front --steps 5 --warmup 2 2>/dev/null | tail -1) > $SUM/${R}_bench_c3front.json
 # round 6: the records start in HOST memory (sbgpu_front_stream_*): C3's sample, and config 5's size (4e8 read pairs, two parts)
-(timeout 900 python bench.py --workload c3-front --from-host --steps 3 2>/dev/null | tail -1) > $SUM/${R}_bench_c3front_fromhost.json
-(SB_FRONT_FRAGS=4e8 timeout 1200 python bench.py --workload c3-front --from-host --steps 2 2>/dev/null | tail -1) > $SUM/${R}_bench_c5size_fromhost.json
+(timeout 900 python bench.py --full --workload c3-front --from-host --steps 3 2>/dev/null | tail -1) > $SUM/${R}_bench_c3front_fromhost.json
+(SB_FRONT_FRAGS=4e8 timeout 1200 python bench.py --full --workload c3-front --from-host --steps 2 2>/dev/null | tail -1) > $SUM/${R}_bench_c5size_fromhost.json
 bash tools/pmc_em_layouts.sh > $SUM/${R}_em_layout_instr.txt 2>&1
 (bash tools/pmc_wide_one.sh 2>&1 | grep "^gpurun_out/pmcw") > $SUM/${R}_wide_tile_pmc.txt
 # random stress on this build (tails; the library's build id on top)
