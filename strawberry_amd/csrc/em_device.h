@@ -246,7 +246,8 @@ template <> struct ThetaLimitSq<float> { static constexpr float value = 0x1.a36e
 //   gr  "row lane":    owns rows gr, gr+GR, gr+2GR, ... (R of them)
 // so each lane keeps an R x CPL tile of F in registers for the whole solve, plus
 // theta for its own CPL columns.  Per iteration the group needs
-//   - the row denominators: all-reduce over the CL column lanes,
+//   - the row denominators: all-reduce over the CL column lanes (wave form, steady loop: reduce-scatter, one
+//     reciprocal per row, all-gather of the weights -- col_lanes_scatter),
 //   - the weighted column sums: all-reduce over the GR row lanes (in the workgroup
 //     form it continues through LDS across the waves);
 // which lane bits carry gc and gr -- and hence what these reductions cost -- is the "matrix lane map" below
@@ -436,6 +437,74 @@ __device__ __forceinline__ T col_lanes_max(T x)
    if (LB_CL >= 3) x = fmax(x, xor_get<2>(x));
    return x;
 }
+
+// Reduce-scatter and all-gather of N per-row values over the column lanes (lane bits 3, 2, 1 in that order: xor 8, 4,
+// 2), for a tile whose rows sit in a per-column-lane order: slot s of a lane holds row s ^ p, p = the lane's top LBS
+// column-lane bits (col_lanes_perm; N a multiple of P = 2^LBS).  Scatter step t pairs slot s with slot s + P / 2^t,
+// which holds the same row in the partner's order: a lane keeps the slots whose low LBS bits are below P / 2^t and adds
+// the partner's copies of them -- no select anywhere.  After LBS steps a lane holds the complete value of its N / P
+// rows in the slots s = 0, P, 2P, ...: row s + p -- all-reduced over the column-lane bits below the scattered ones,
+// whose lanes hold the same rows.  Each step pairs the same two partial sums as col_lanes_sum does, so a sum is
+// bitwise the one the butterfly gives.  The gather undoes the steps, moving values without arithmetic.
+template <int LB_CL, int LBS>
+__device__ __forceinline__ int col_lanes_perm(int gc) { return gc >> (LB_CL - LBS); }
+// x(lane ^ 4) in two DPP moves per 32 bits: xor_get<4>'s, except that the first move leaves its disabled lanes undefined
+// rather than zero (no register to clear first) -- the second move writes every one of them
+__device__ __forceinline__ int xor4_get_i(int x)
+{
+   const int t = __builtin_amdgcn_mov_dpp(x, 0x104 /*row_shl:4*/, 0xF, 0x5, false);
+   return __builtin_amdgcn_update_dpp(t, x, 0x114 /*row_shr:4*/, 0xF, 0xA, false);
+}
+// column-lane step 1, 2, 3: the partner across lane bit 3, 2, 1
+template <int STEP>
+__device__ __forceinline__ double col_xor(double x)
+{
+   if constexpr (STEP == 2)
+      return __hiloint2double(xor4_get_i(__double2hiint(x)), xor4_get_i(__double2loint(x)));
+   else
+      return xor_get<(8 >> (STEP - 1))>(x);
+}
+template <int STEP, int LB_CL, int LBS, int N, class T, class Op>
+__device__ __forceinline__ void col_scatter_step(T (&x)[N], Op op)
+{
+   constexpr int P = 1 << LBS;
+   if constexpr (STEP <= LBS) {
+      constexpr int D = P >> STEP;
+#pragma unroll
+      for (int s = 0; s < N; ++s)
+         if ((s & (P - 1)) < D) x[s] = op(x[s], col_xor<STEP>(x[s + D]));
+   } else if constexpr (STEP <= LB_CL) {
+#pragma unroll
+      for (int s = 0; s < N; s += P) x[s] = op(x[s], col_xor<STEP>(x[s]));
+   }
+}
+template <int STEP, int LBS, int N, class T>
+__device__ __forceinline__ void col_gather_step(T (&x)[N])
+{
+   constexpr int P = 1 << LBS;
+   if constexpr (STEP <= LBS) {
+      constexpr int D = P >> STEP;
+#pragma unroll
+      for (int s = 0; s < N; ++s)
+         if ((s & (P - 1)) < D) x[s + D] = col_xor<STEP>(x[s]);
+   }
+}
+template <int LB_CL, int LBS, int N, class T, class Op>
+__device__ __forceinline__ void col_lanes_scatter(T (&x)[N], Op op)
+{
+   static_assert(LBS >= 1 && LBS <= LB_CL && LB_CL <= 3 && (N % (1 << LBS)) == 0, "slots split evenly");
+   col_scatter_step<1, LB_CL, LBS>(x, op);
+   col_scatter_step<2, LB_CL, LBS>(x, op);
+   col_scatter_step<3, LB_CL, LBS>(x, op);
+}
+template <int LB_CL, int LBS, int N, class T>
+__device__ __forceinline__ void col_lanes_gather(T (&x)[N])
+{
+   col_gather_step<3, LBS>(x);
+   col_gather_step<2, LBS>(x);
+   col_gather_step<1, LBS>(x);
+}
+constexpr int pow2_factor(int x) { return (x & 1) ? 0 : 1 + pow2_factor(x >> 1); } // x > 0
 
 // all-reduce of NVAL values over the first lbGR row-lane bits (lbGR wave-uniform)
 template <int LB_CL, int NVAL>
@@ -640,6 +709,19 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
    // (the tall tile has no registers for dfix either: it selects the weight of such a row away)
    constexpr bool kDfix = R * CPL <= 64;
    T dfix[kDfix ? R : 1];
+   // Column lanes (wave form, matrix lane map): the row denominators are reduce-scattered over the column-lane bits
+   // that split the R rows evenly, so that a lane takes the reciprocals of R >> kLbScat rows instead of all R, and the
+   // weights are gathered back (col_lanes_scatter).  The tile then holds the rows of a lane in its own order: slot r
+   // holds row r ^ perm of the row lane, set once as the tile is loaded.  (kLbScat = 0: every lane all R rows, in
+   // order, as for one column lane.)  The block form keeps the all-reduce: it skips the row blocks a locus does not
+   // need, and the exchange, which runs over all R slots, cost it more than it saved (profiles/EXPERIMENTS_r07.md).
+   constexpr int kLbScat = (kBatchDiv && !HIMAP && !BLOCK && LB_CL >= 1)
+                              ? (pow2_factor(R) < LB_CL ? pow2_factor(R) : LB_CL)
+                              : 0;
+   constexpr bool kScatter = kLbScat > 0;
+   constexpr int kOwn = R >> kLbScat; // rows whose weights a lane computes: slots 0, P, 2P, ... (P = 2^kLbScat)
+   const int perm = kScatter ? col_lanes_perm<LB_MM, kLbScat>(gc) : 0;
+   auto tile_row = [&](int r) -> int { return kScatter ? (r ^ perm) : r; };
    bool act[R];
    T theta[CPL];
    T theta0 = T(0);
@@ -691,13 +773,14 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
             r_used = r_used < 1 ? 1 : (r_used > R ? R : r_used);
          }
          // EmSolver::init, estimate.cpp:366-391
+         T mxs[kScatter ? R : 1]; // kScatter: the largest weight of each slot's row over the own columns
          T red[2];
          red[0] = T(0); // sum of ALL counts (theta0 precedes the row drop, :374-375)
          red[1] = T(0); // number of kept rows
 #pragma unroll
          for (int r = 0; r < R; ++r) {
             if (BLOCK && (r & ~3) >= r_used) continue; // row block not needed by this locus
-            const int i = r * GR + gr;
+            const int i = tile_row(r) * GR + gr;
             const bool valid = got && i < nrow;
             // clamped indices: loads stay inside the locus (or touch nothing when it
             // has no rows), no per-element branches
@@ -728,6 +811,14 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
             }
 #pragma unroll
             for (int jj = 0; jj < CPL; ++jj) mx = fmax(mx, v[jj]);
+            if constexpr (kScatter) {
+               // the row's maximum needs the other column lanes, which hold the row in other slots: below
+               mxs[r] = mx;
+               nn[r] = cnt;
+#pragma unroll
+               for (int jj = 0; jj < CPL; ++jj) F[r][jj] = v[jj];
+               continue;
+            }
             // any weight of the row > 1e-5 (:380), over all column lanes
             if constexpr (HIMAP) {
                if (CL >= 2) mx = fmax(mx, xor_get<1>(mx));
@@ -744,6 +835,21 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
             nn[r] = keep ? cnt : T(0);
 #pragma unroll
             for (int jj = 0; jj < CPL; ++jj) F[r][jj] = keep ? v[jj] : T(0);
+         }
+         if constexpr (kScatter) {
+            // any weight of the row > 1e-5 (:380), over all column lanes: the same exchange as the denominators'
+            col_lanes_scatter<LB_CL, kLbScat>(mxs, [](T p, T q) { return fmax(p, q); });
+            col_lanes_gather<LB_CL, kLbScat>(mxs);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+               const bool keep = mxs[r] > (T)kRowEps;
+               if (gc == 0 && keep) red[1] += T(1);
+               dfix[r] = keep ? T(0) : T(1);
+               act[r] = keep;
+               nn[r] = keep ? nn[r] : T(0);
+#pragma unroll
+               for (int jj = 0; jj < CPL; ++jj) F[r][jj] = keep ? F[r][jj] : T(0);
+            }
          }
          // group totals: over the column lanes, then over the row lanes
          red[0] = col_sum(red[0]);
@@ -814,6 +920,47 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
          // lane -- and the same row denominator is seen by all column lanes -- so every next_theta of the group and
          // with them ||next - theta||^2 come out as NaN, which is tested once per iteration below.  Nothing else
          // makes a NaN here: denominators are sums of products of non-negative finite numbers.
+         if constexpr (kScatter) {
+            // E-step with the denominators reduce-scattered over the column lanes: a lane completes the denominators
+            // of its slots 0, P, 2P, ..., takes their reciprocals and weights, and the weights are gathered back into
+            // every column lane's own row order.  A zero denominator still makes its owner's weight a NaN, and the
+            // gather hands that NaN to every column lane of the group.
+            static_assert(!BLOCK, "the block form skips row blocks: it keeps the all-reduce");
+            constexpr int P = 1 << kLbScat;
+            T x[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+               T sum = dfix[r];
+#pragma unroll
+               for (int jj = 0; jj < CPL; ++jj) sum = fma_t(F[r][jj], tin[jj], sum); // :450
+               x[r] = sum;
+            }
+            col_lanes_scatter<LB_CL, kLbScat>(x, [](T p, T q) { return p + q; });
+#pragma unroll
+            for (int ib = 0; ib < kOwn; ib += 4) {
+               const int nb = kOwn - ib < 4 ? kOwn - ib : 4;
+               if constexpr (kExact) {
+#pragma unroll
+                  for (int q = 0; q < nb; ++q) x[(ib + q) * P] = fast_div(nn[(ib + q) * P], x[(ib + q) * P]);
+               } else {
+                  double dd[4], inv[4];
+#pragma unroll
+                  for (int q = 0; q < 4; ++q) dd[q] = q < nb ? x[(ib + q) * P] : 1.0;
+                  if (nb == 4) batch_reciprocals<4>(dd, inv);
+                  else if (nb == 3) batch_reciprocals<3>(dd, inv);
+                  else if (nb == 2) batch_reciprocals<2>(dd, inv);
+                  else batch_reciprocals<1>(dd, inv);
+#pragma unroll
+                  for (int q = 0; q < nb; ++q) x[(ib + q) * P] = nn[(ib + q) * P] * inv[q];
+               }
+            }
+            col_lanes_gather<LB_CL, kLbScat>(x);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+#pragma unroll
+               for (int jj = 0; jj < CPL; ++jj) acc[jj] = fma_t(x[r], F[r][jj], acc[jj]);
+            }
+         } else {
          // rows in blocks of 4 to bound the live temporaries
 #pragma unroll
          for (int rb = 0; rb < R; rb += 4) {
@@ -858,6 +1005,7 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
                   }
                }
             }
+         }
          }
          row_lane_sum(acc, std::integral_constant<int, NV>(), lb_tag);
          T p2 = T(0);
