@@ -2,16 +2,15 @@
 // Sample::next_valid_alignment loop (src/alignments.cpp:976-1009: BAMHitFactory::nextRecord + getHitFromBuf,
 // src/read.cpp:455-715) hands to its clusters, for the whole file at once.
 //
-//   g++ -std=c++14 -Iinclude examples/bam_reads.cpp -Lstrawberry_amd/lib -lsbgpu -lz -Wl,-rpath,$PWD/strawberry_amd/lib
+//   g++ -std=c++14 -Iinclude examples/bam_reads.cpp -Lstrawberry_amd/lib -lsbgpu -Wl,-rpath,$PWD/strawberry_amd/lib
 //   ./a.out in.bam [-j min_intron] [-J max_intron] [--allow-multimapped-hits] [--fr | --rf] > reads.tsv
 //
-// The program inflates the BGZF blocks with zlib (gzread walks the chain of gzip members), skips the BAM header, lets
-// sbgpu_bam_index_host find the records and sbgpu_bam_decode_host decide about them (sbgpu_bam_decode_device takes the same
+// The program reads the file, lets the library find its BGZF members (sbgpu_bgzf_index_host) and inflate them on host threads
+// (sbgpu_bgzf_inflate_host: no zlib; sbgpu_bgzf_inflate_device and sbgpu_bam_index_device do the same for a file uploaded as it
+// is), skips the BAM header, lets sbgpu_bam_index_host find the records and sbgpu_bam_decode_host decide about them (sbgpu_bam_decode_device takes the same
 // bytes in device memory and leaves the arrays there for sbgpu_assign_reads_device / sbgpu_pair_mates_device), and prints
 // one line per accepted record: record index, read id, reference name, first and last aligned base, strand, mate position,
 // flags, NH, NM, read length, aligned blocks.  Counts by reason of refusal go to stderr.
-#include <zlib.h>
-
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -42,24 +41,33 @@ int main(int argc, char **argv)
          return 2;
       }
    }
-   // BGZF: a chain of gzip members
-   gzFile f = gzopen(argv[1], "rb");
+   // BGZF: a chain of gzip members, each with its sizes in its header and footer
+   std::FILE *f = std::fopen(argv[1], "rb");
    if (!f) {
       std::fprintf(stderr, "cannot open %s\n", argv[1]);
       return 1;
    }
-   std::vector<uint8_t> raw;
+   std::vector<uint8_t> file;
    std::vector<uint8_t> chunk(1 << 20);
-   for (;;) {
-      const int n = gzread(f, chunk.data(), (unsigned)chunk.size());
-      if (n < 0) {
-         std::fprintf(stderr, "%s: inflate failed\n", argv[1]);
+   for (size_t n; (n = std::fread(chunk.data(), 1, chunk.size(), f)) > 0;) file.insert(file.end(), chunk.begin(), chunk.begin() + n);
+   std::fclose(f);
+   std::vector<int64_t> blk_off(file.size() / 26 + 2), out_off(blk_off.size());
+   const int64_t n_members = sbgpu_bgzf_index_host(file.data(), (int64_t)file.size(), blk_off.data(), out_off.data(), (int64_t)blk_off.size() - 1);
+   if (n_members < 0) {
+      std::fprintf(stderr, "%s: %s\n", argv[1], sbgpu_last_error());
+      return 1;
+   }
+   std::vector<uint8_t> raw((size_t)out_off[(size_t)n_members]), member_status((size_t)n_members + 1);
+   if (sbgpu_bgzf_inflate_host(file.data(), (int64_t)file.size(), blk_off.data(), out_off.data(), 0, n_members, raw.data(), member_status.data()) != SBGPU_OK) {
+      std::fprintf(stderr, "%s\n", sbgpu_last_error());
+      return 1;
+   }
+   for (int64_t b = 0; b < n_members; ++b)
+      if (member_status[(size_t)b] != SBGPU_BGZF_OK) {
+         std::fprintf(stderr, "%s: the BGZF member at byte %" PRId64 " does not inflate (status %d)\n", argv[1], blk_off[(size_t)b], (int)member_status[(size_t)b]);
          return 1;
       }
-      if (n == 0) break;
-      raw.insert(raw.end(), chunk.begin(), chunk.begin() + n);
-   }
-   gzclose(f);
+   std::vector<uint8_t>().swap(file);
    // the header: magic, text, references
    if (raw.size() < 12 || std::memcmp(raw.data(), "BAM\1", 4) != 0) {
       std::fprintf(stderr, "%s: not a BAM file\n", argv[1]);

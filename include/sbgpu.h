@@ -581,7 +581,7 @@ int sbgpu_matepairs_export(const sbgpu_matepairs_t *m, double *pair_mass, int64_
 /* ---- BAM alignment records -> the read stream (replaces BAMHitFactory::getHitFromBuf) --------
  * /root/reference/src/read.cpp:480-715: a BAM record becomes a ReadHit -- or is refused -- on its flag word, its CIGAR,
  * the XS / NM / NH tags and four option globals.  In: the UNCOMPRESSED record stream behind the BAM header (what
- * samtools' bam_read1 reads after BGZF inflate, which stays with the caller): per record int32 block_size, the 32-byte
+ * samtools' bam_read1 reads after BGZF inflate: the BGZF section below): per record int32 block_size, the 32-byte
  * core, read name, CIGAR, sequence, qualities, tags.  Out: the accepted records, in file order, as the arrays
  * sbgpu_assign_reads_* and sbgpu_pair_mates_* take, plus why each of the others was refused.
  *   - refused: unmapped (flag 0x4 or no reference); a CIGAR operation of length 0; an operation other than M I D N S H P;
@@ -646,6 +646,64 @@ int sbgpu_bamreads_reads(const sbgpu_bamreads_t *b, sbgpu_reads_t *reads, const 
 int sbgpu_bamreads_export(const sbgpu_bamreads_t *b, uint8_t *status, int64_t *record, uint64_t *read_id, int32_t *ref, uint32_t *left,
                           uint32_t *right, uint32_t *partner_pos, uint8_t *flags, int32_t *nh, int32_t *nm, int32_t *read_len,
                           uint32_t *sam_flag, int64_t *block_off, uint32_t *block_left, uint32_t *block_right);
+
+/* ---- BGZF: a BAM file's own bytes -> the inflated stream and its records (csrc/bgzf_device.h, bgzf_host.cpp, bgzf_api.hip) ----
+ * A BGZF file is a chain of independent gzip members of at most 64 KiB, each with its compressed size in its header (BSIZE)
+ * and its inflated size in its footer (ISIZE): samtools 0.1.19 bgzf.c.  The library inflates them itself -- no zlib is
+ * linked -- with one RFC 1951 decoder (stored, fixed and dynamic blocks, any number of blocks per member, distances up to
+ * 32768, matches that overlap their own output) that runs per host thread or per wave of the device.
+ *
+ * The block table: blk_off[0 .. n] where every member starts in the file (blk_off[n] = n_bytes), out_off[0 .. n] the running
+ * sum of the ISIZE words: where every member's bytes land in the inflated stream.  Returns n, or -1 (sbgpu_last_error) when a
+ * header fails the reference's check_header (bgzf.c:240-246: magic 31 139 8, FLG & 4, XLEN == 6, subfield 'B' 'C' of length 2;
+ * those tests and no others), when the file ends inside a member, when ISIZE > 65536 or BSIZE leaves no room for the
+ * 8-byte footer, or when there are more than `cap` members.  A member with ISIZE 0 (the EOF marker) is an ordinary entry.  */
+int64_t sbgpu_bgzf_index_host(const uint8_t *file, int64_t n_bytes, int64_t *blk_off, int64_t *out_off, int64_t cap);
+/* Inflate.  Member b's payload is file[blk_off[b] + 18 .. blk_off[b + 1] - 8); its bytes go to out[out_off[b] .. out_off[b + 1])
+ * (`out` is the origin of the out_off coordinates, whichever members a call covers).  A member is SBGPU_BGZF_OK iff zlib's raw
+ * inflate of the same payload reaches the end of the stream AND gives exactly out_off[b + 1] - out_off[b] bytes; otherwise its
+ * status says why.  The reference (bgzf.c:214-238) accepts a member whose ISIZE lies; this library lays the output out by
+ * ISIZE and refuses it (SBGPU_BGZF_ESIZE).  Neither checks the CRC-32 word, and bytes of the payload behind the final block
+ * are ignored, as zlib ignores them.  A failed member never writes outside its own output range and never reads outside its
+ * own bytes of the file; its neighbours are unaffected.  Host and device form take the same decisions (the same decoder),
+ * statuses included.  The calls return SBGPU_OK when members failed -- the statuses are the report -- and SBGPU_EINVAL for
+ * bad arguments.                                                                                                          */
+enum {
+   SBGPU_BGZF_OK = 0,
+   SBGPU_BGZF_EBTYPE = 1,   /* a block of the reserved type 3                                                              */
+   SBGPU_BGZF_ESTORED = 2,  /* a stored block whose LEN and NLEN disagree                                                  */
+   SBGPU_BGZF_ECODELEN = 3, /* a dynamic block's code lengths: over-subscribed or incomplete set, more than 286 / 30 codes,
+                               a repeat with nothing to repeat or past the last length, no end-of-block code               */
+   SBGPU_BGZF_ESYMBOL = 4,  /* a code that stands for no symbol, length symbol 286 / 287, distance symbol 30 / 31           */
+   SBGPU_BGZF_EDIST = 5,    /* a distance that reaches before the member's first byte                                      */
+   SBGPU_BGZF_EINPUT = 6,   /* the payload ran out (also: a member shorter than header + footer or longer than 65536)      */
+   SBGPU_BGZF_ESIZE = 7     /* the output is not ISIZE bytes (also: an out_off range that is negative or exceeds 65536)    */
+};
+/* Host form: members first_block .. first_block + n_blocks - 1 on host threads (SBGPU_HOST_THREADS, default min(16,
+ * hardware threads)); status[0 .. n_blocks) belongs to those members in order.                                            */
+int sbgpu_bgzf_inflate_host(const uint8_t *file, int64_t n_bytes, const int64_t *blk_off, const int64_t *out_off, int64_t first_block,
+                            int64_t n_blocks, uint8_t *out, uint8_t *status);
+/* Device form: all arrays in device memory, one member per wave, launched on `stream` (NULL: the context's).  *n_failed
+ * (host; may be NULL) is the number of members with a nonzero status: asking for it makes the call wait for the stream,
+ * without it the call returns when the kernel is launched.                                                               */
+int sbgpu_bgzf_inflate_device(sbgpu_ctx_t *ctx, const uint8_t *d_file, int64_t n_bytes, const int64_t *d_blk_off,
+                              const int64_t *d_out_off, int64_t n_blocks, uint8_t *d_out, void *stream, uint8_t *d_status,
+                              int64_t *n_failed);
+/* The records' offsets of an inflated stream that lives on the device: what sbgpu_bam_index_host gives on the bytes from
+ * `first_record` (the header's length) on -- d_rec_off[0 .. n] are RELATIVE to first_record, d_rec_off[n] = n_bytes -
+ * first_record, so sbgpu_bam_decode_device takes d_bytes + first_record with them -- including the -1 when the chain meets a
+ * negative size word, ends inside a record, or holds more than `cap` records.  Exact for any input.  `d_guess[0 .. n_guess)`
+ * (ascending; NULL: every 65536 bytes) are offsets in d_bytes where a record PROBABLY starts -- the out_off of the block table:
+ * samtools starts every member on a record boundary -- and only buy speed: the chain of size words is cut there and every
+ * segment is walked in parallel from its guess.  Then, round after round, a segment whose entry is not where its predecessor's
+ * walk ended is walked again from there, provided that predecessor's own entry was right in the same sense (the exit of a
+ * segment that is itself about to be walked again is noise and is not passed on); a round that repairs nothing has found the
+ * true chain, and after 8 repairing rounds one lane walks what is left in order (slow, exact).  Waits for the stream.     */
+int64_t sbgpu_bam_index_device(sbgpu_ctx_t *ctx, const uint8_t *d_bytes, int64_t n_bytes, int64_t first_record, const int64_t *d_guess,
+                               int64_t n_guess, int64_t *d_rec_off, int64_t cap, void *stream);
+/* About this thread's last sbgpu_bam_index_device call: info[0] rounds of walks (1: every guess was right), info[1] segments,
+ * info[2] walks repeated, info[3] the segment the sequential walker started at (-1: it did not run); info[4 .. 8) zero.    */
+void sbgpu_bam_index_device_info(int64_t *info);
 
 /* LocusContext::assign_exon_bin + set_maps (src/estimate.cpp:135-198, estimate.hpp:29-52)
  * on the kernel's results (host copies of compat / key), hits visited in input order inside
@@ -796,7 +854,7 @@ int sbgpu_quantify_resident(sbgpu_ctx_t *ctx, const sbgpu_annotation_t *annot, c
 /* ---- records in HOST memory -> abundances, chunk by chunk, with a bounded footprint on the device -------------------------
  * The reference streams: Sample::nextClusterRefDemand / procSample hold one cluster's reads at a time
  * (src/alignments.cpp:1145-1187, 1736-1811).  The device entries above take a whole sample's records resident; a caller that
- * inflates a BAM file on the host uses this instead (csrc/front_stream_api.hip):
+ * inflates a BAM file on the host, or holds the file's own bytes there (push_bgzf below), uses this instead (csrc/front_stream_api.hip):
  *   begin   the clusters of quant mode (sorted by (reference, left), as sbgpu_assign_reads_*; cluster k = locus k of the
  *           annotation given to end), the decoder's options, and the most bytes one chunk will hold: two device buffers of
  *           twice that (a chunk + room for the records carried over from the chunk before)
@@ -817,7 +875,7 @@ int sbgpu_quantify_resident(sbgpu_ctx_t *ctx, const sbgpu_annotation_t *annot, c
  * info: 0 records pushed, 1 accepted records consumed, 2 pairs, 3 unique hits, 4 their features, 5 pairs the span filter
  * dropped, 6 mapped reads, 7 chunks (non-empty pushes), 8 clusters finished, 9 most bytes carried over, 10 records decoded twice, 11 the LEAST free
  * device memory seen since begin (bytes, hipMemGetInfo after every chunk and after the last stage: blocks the library's pool
- * holds idle count as used), 12 chunk_bytes (the capacity of a chunk and of a carry), 13: 1 once ended, 14 free device memory at begin.               */
+ * holds idle count as used), 12 chunk_bytes (the capacity of a chunk and of a carry), 13: 1 once ended, 14 free device memory at begin, 15 compressed bytes pushed (push_bgzf). */
 typedef struct sbgpu_front_stream sbgpu_front_stream_t;
 int sbgpu_front_stream_begin(sbgpu_ctx_t *ctx, const sbgpu_clusters_t *clusters, const sbgpu_bam_opts_t *opts, int64_t chunk_bytes,
                              sbgpu_front_stream_t **out);
@@ -826,6 +884,22 @@ int sbgpu_front_stream_end(sbgpu_front_stream_t *fs, const sbgpu_annotation_t *a
                            int32_t long_read, const sbgpu_abundance_params_t *params, sbgpu_comm_t *comm, sbgpu_insert_t *insert_used,
                            sbgpu_abundances_t *out, sbgpu_bins_t **bins_out);
 int sbgpu_front_stream_info(const sbgpu_front_stream_t *fs, int64_t info[16]);
+/* push_bgzf: the next chunk as the file's own bytes -- WHOLE BGZF members in file order, from host memory under the rules of
+ * push (page-locked: the upload runs beside the kernels).  file_bytes[0 .. n_bytes) are the members blk_off[0] .. blk_off[n_blocks]
+ * of the block table (sbgpu_bgzf_index_host; blk_off / out_off point at the push's first member, n_bytes = blk_off[n_blocks] -
+ * blk_off[0]; the two tables are copied before the call returns).  The compressed bytes are uploaded; when the chunk's turn
+ * comes -- in the NEXT push, or in end -- it is inflated on the device where an inflated chunk would have landed, behind the
+ * carried bytes, the window's records are found there (sbgpu_bam_index_device's scheme with the members' starts as guesses), and
+ * the per-chunk work of push runs unchanged.  Members need not end on record boundaries: the bytes of a record the chunk's end
+ * cuts join the carry and the next chunk's bytes complete it.  first_record: how many of the push's inflated bytes belong to the
+ * BAM header (nonzero for the pushes up to the one that holds the header's end; a push that is all header passes at least its
+ * span).  chunk_bytes of begin keeps meaning INFLATED bytes: a push whose out_off span exceeds it is SBGPU_ESHAPE, as is a stream
+ * that ends inside a record (from end).  A member with a nonzero SBGPU_BGZF status fails the call that computes its chunk with
+ * SBGPU_EINVAL and the member's offset (blk_off[k]) in sbgpu_last_error; the stream can then only be destroyed.  Results: those of
+ * the same records through push and through the resident entries, bit for bit.  push and push_bgzf are not mixed in one stream
+ * (SBGPU_EINVAL).  sbgpu_front_stream_info: info[15] is the compressed bytes pushed.                                          */
+int sbgpu_front_stream_push_bgzf(sbgpu_front_stream_t *fs, const uint8_t *file_bytes, int64_t n_bytes, const int64_t *blk_off,
+                                 const int64_t *out_off, int64_t n_blocks, int64_t first_record);
 /* the store: the unique hits of the clusters finished so far (device arrays, the stream's), their masses, and where every
  * cluster's hits begin (host, [n_clusters + 1]; complete after end)                                                            */
 int sbgpu_front_stream_hits(const sbgpu_front_stream_t *fs, sbgpu_hits_t *d_hits, const float **d_hit_mass, const int64_t **locus_hit_off);

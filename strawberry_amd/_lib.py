@@ -39,6 +39,7 @@ SYMBOLS = [
     "sbgpu_quantify_resident", "sbgpu_allreduce_max_i64", "sbgpu_allreduce_max_i64_host", "sbgpu_comm_init_host",
     "sbgpu_front_stream_begin", "sbgpu_front_stream_push", "sbgpu_front_stream_end", "sbgpu_front_stream_info", "sbgpu_front_stream_hits",
     "sbgpu_front_stream_destroy", "sbgpu_em_run_device_split",
+    "sbgpu_bgzf_index_host", "sbgpu_bgzf_inflate_host", "sbgpu_bgzf_inflate_device", "sbgpu_bam_index_device", "sbgpu_bam_index_device_info", "sbgpu_front_stream_push_bgzf",
 ]
 
 
@@ -233,6 +234,7 @@ def load():
     L.sbgpu_comm_init_host.argtypes = [vp, C.c_int, C.c_int, HOST_ALLREDUCE_FN, vp, C.POINTER(vp)]
     L.sbgpu_front_stream_begin.argtypes = [vp, C.POINTER(sbgpu_clusters_t), C.POINTER(sbgpu_bam_opts_t), C.c_int64, C.POINTER(vp)]
     L.sbgpu_front_stream_push.argtypes = [vp, vp, C.c_int64, vp, C.c_int64]
+    L.sbgpu_front_stream_push_bgzf.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int64]
     L.sbgpu_front_stream_end.argtypes = [vp, C.POINTER(sbgpu_annotation_t), C.POINTER(sbgpu_insert_t), C.c_int32, C.c_int32,
                                          C.POINTER(sbgpu_abundance_params_t), vp, C.POINTER(sbgpu_insert_t), C.POINTER(sbgpu_abundances_t),
                                          C.POINTER(vp)]
@@ -254,6 +256,14 @@ def load():
     L.sbgpu_bam_index_host.restype = C.c_int64
     L.sbgpu_bam_decode_host.argtypes = [vp, C.c_int64, vp, C.c_int64, C.POINTER(sbgpu_bam_opts_t), C.POINTER(vp)]
     L.sbgpu_bam_decode_device.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.POINTER(sbgpu_bam_opts_t), vp, C.POINTER(vp)]
+    L.sbgpu_bgzf_index_host.argtypes = [vp, C.c_int64, vp, vp, C.c_int64]
+    L.sbgpu_bgzf_index_host.restype = C.c_int64
+    L.sbgpu_bgzf_inflate_host.argtypes = [vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, vp]
+    L.sbgpu_bgzf_inflate_device.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, vp, i64p]
+    L.sbgpu_bam_index_device.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp]
+    L.sbgpu_bam_index_device.restype = C.c_int64
+    L.sbgpu_bam_index_device_info.argtypes = [i64p]
+    L.sbgpu_bam_index_device_info.restype = None
     L.sbgpu_bamreads_destroy.argtypes = [vp]
     L.sbgpu_bamreads_destroy.restype = None
     L.sbgpu_bamreads_info.argtypes = [vp, i64p]

@@ -141,6 +141,13 @@ int exonbin_device_impl(sbgpu_ctx_t *ctx, const sbgpu_annotation_t *annot, const
                         int64_t n_iso = -1, const DeviceSegBasis *seg_basis = nullptr);
 // bamdecode_api.hip: the device array `record` of a device handle (accepted read -> its record's index)
 const int64_t *bamreads_device_record(const sbgpu_bamreads_t *reads);
+// bgzf_api.hip: sbgpu_bam_index_device with the caller's guesses in other coordinates (guess + guess_add is the offset in d_bytes),
+// the offsets' array asked for once the count is known (alloc(n) -> room for n + 1 entries, or null: too many), and -- where
+// `tail_start` is given -- a stream that may end inside its last record: the whole records are indexed and *tail_start is where
+// the cut one begins (n_bytes: none is cut).  Returns the count, or a negative SBGPU_E* code (sbgpu_last_error is set).
+int64_t bam_index_device_impl(sbgpu_ctx_t *ctx, const uint8_t *d_bytes, int64_t n_bytes, int64_t first_record, const int64_t *d_guess,
+                              int64_t n_guess, int64_t guess_add, const std::function<int64_t *(int64_t)> &alloc, int64_t *tail_start,
+                              void *stream);
 int api_fail(int code, const std::string &msg); // records sbgpu_last_error(), returns code
 // Experiment switches: SBGPU_* variables that select paths DESIGN.md / profiles/EXPERIMENTS_*.md record as measured and NOT adopted
 // (phased execution, launch graphs, tile and schedule variants, A/B forms of the grouping ...).  They exist only in a library built

@@ -3,8 +3,8 @@
 //
 // The reference streams too: Sample::nextClusterRefDemand / procSample hold ONE cluster's reads at a time
 // (/root/reference/src/alignments.cpp:1145-1187, 1736-1811).  The device entries of the front end take a whole sample's records
-// resident (196 GB of arenas at 3.9e8 records); here the unit is a chunk of the inflated record stream (BGZF inflate is zlib on
-// host threads and stays the caller's):
+// resident (196 GB of arenas at 3.9e8 records); here the unit is a chunk of the inflated record stream -- inflated by the
+// caller (push), or handed over as the file's own BGZF members and inflated here, behind the link (push_bgzf, at the end):
 //
 //   push(chunk i)   the chunk's bytes start their way to the device (copy stream; two device buffers alternate), then chunk
 //                   i - 1 -- uploaded during the push before -- is computed: sbgpu_bam_decode_device ->
@@ -16,6 +16,13 @@
 //   end()           the last chunk (every remaining cluster is complete now), then ONE sbgpu_quantify_resident over the
 //                   store: pass 1 (the empirical insert-size law is the WHOLE sample's: it cannot be known earlier), bins,
 //                   weights, EM, FPKM, the all-reduce, TPM.  The unique hits are a seventh of the records' bytes.
+//
+//   push_bgzf(chunk i)  the same with WHOLE BGZF members in place of whole records: the compressed bytes and the members' table
+//                   travel; when the chunk's turn to be computed comes it is inflated where an inflated chunk would have
+//                   landed (sbgpu_bgzf_inflate_device, behind the carry), the window [carry | chunk] is indexed on the device
+//                   (sbgpu_bam_index_device's scheme, the members' starts as guesses), and the stages above run unchanged.
+//                   Members do not end on record boundaries in general: the bytes of a record the window cuts join the
+//                   carry and are completed by the next chunk's.
 //
 // So upload and compute overlap chunk by chunk, the arenas are a chunk's, and what grows with the sample is the store.
 // Results: those of the resident entries on the whole sample, bit for bit (same clusters, same order, same kernels).
@@ -119,6 +126,12 @@ struct sbgpu_front_stream {
    int64_t n_records = 0, n_decoded = 0, n_accepted = 0, n_pairs = 0, n_filtered = 0, mapped_reads = 0, n_chunks = 0, carry_max = 0, redecoded = 0;
    size_t free_at_begin = 0, min_free = 0;
    bool ended = false;
+   // push_bgzf: the pending chunk's compressed bytes and its table (blk_off | out_off | statuses) on the device, the table's
+   // host copy (for the message about a member that fails), and what the chunk's computation needs to know
+   int mode = 0;                   // 0: nothing pushed yet, 1: push, 2: push_bgzf (never both in one stream)
+   Grow d_comp[2], d_tab[2];
+   std::vector<int64_t> h_blk[2], h_out[2];
+   int64_t pend_blocks = 0, pend_first = 0, comp_bytes = 0;
    double t_wait = 0, t_compute = 0, t_enqueue = 0, t_last = 0; // seconds: waiting for uploads, computing chunks, enqueuing uploads, the last stage
    void note_memory()
    {
@@ -161,11 +174,62 @@ int compute_pending(sbgpu_front_stream *F, bool last)
    } clock = {F->t_compute, t_arrived};
    // the window: [carry | chunk], its record offsets
    const int64_t n_carry = F->carry_n;
-   const int64_t n_new = F->pending ? F->pend_records : 0;
-   const int64_t n_rec = n_carry + n_new, w_bytes = F->carry_bytes + (F->pending ? F->pend_bytes : 0);
+   int64_t n_new = F->pending ? F->pend_records : 0;
+   int64_t n_rec = n_carry + n_new, w_bytes = F->carry_bytes + (F->pending ? F->pend_bytes : 0); // w_bytes: the window's whole records
+   int64_t w_end = w_bytes;                                                                      // ... and all its bytes
    char *w0 = F->buf[b] + F->room - F->carry_bytes; // (the carry was copied to end where the chunk begins)
    F->n_chunks += F->pending && F->pend_bytes ? 1 : 0; // (an empty push is no chunk)
    F->redecoded += n_carry;
+   Grow &W = F->d_win[F->win], &P = F->d_win[F->win ^ 1];
+   if (F->mode == 2) {
+      // ---- a chunk of BGZF members: inflate it where an inflated chunk would have landed, then find the window's records
+      const int64_t nm = F->pending ? F->pend_blocks : 0;
+      int64_t first = 0;
+      if (nm) {
+         const int64_t *d_blk = (const int64_t *)F->d_tab[b].p, *d_out = d_blk + (nm + 1);
+         uint8_t *d_status = (uint8_t *)(d_out + (nm + 1));
+         const int64_t blk0 = F->h_blk[b][0], out0 = F->h_out[b][0];
+         int64_t failed = 0;
+         SB_RC(sbgpu_bgzf_inflate_device(c, (const uint8_t *)((uintptr_t)F->d_comp[b].p - (uintptr_t)blk0), F->h_blk[b][(size_t)nm], d_blk, d_out, nm,
+                                         (uint8_t *)((uintptr_t)(F->buf[b] + F->room) - (uintptr_t)out0), s, d_status, &failed));
+         if (failed) {
+            std::vector<uint8_t> st((size_t)nm);
+            SB_TRY(hipMemcpyAsync(st.data(), d_status, (size_t)nm, hipMemcpyDeviceToHost, s));
+            SB_TRY(hipStreamSynchronize(s));
+            size_t k = 0;
+            while (k + 1 < st.size() && !st[k]) ++k;
+            return api_fail(SBGPU_EINVAL, "sbgpu_front_stream_push_bgzf: the BGZF member at byte " + std::to_string(F->h_blk[b][k]) +
+                                             " of the file does not inflate to its ISIZE bytes (SBGPU_BGZF status " + std::to_string((int)st[k]) + "; " +
+                                             std::to_string(failed) + " of the push's " + std::to_string(nm) + " members failed)");
+         }
+         first = std::min(F->pend_first, F->pend_bytes); // the header's bytes in this chunk
+         if (first && F->carry_bytes) return api_fail(SBGPU_EINVAL, "sbgpu_front_stream_push_bgzf: first_record in a push behind the first records");
+         w0 += first, w_end -= first;
+      }
+      n_rec = 0, w_bytes = 0;
+      if (w_end > 0) {
+         const int64_t n = sb::bam_index_device_impl(c, (const uint8_t *)w0, w_end, 0, nm ? (const int64_t *)F->d_tab[b].p + (nm + 1) : nullptr, nm ? nm + 1 : 0,
+                                                     F->carry_bytes - first - (nm ? F->h_out[b][0] : 0),
+                                                     [&](int64_t n_records) -> int64_t * {
+                                                        W.used = 0;
+                                                        return W.reserve((size_t)(n_records + 1) * 8, s) == hipSuccess ? (int64_t *)W.p : nullptr;
+                                                     },
+                                                     &w_bytes, s);
+         if (n < 0) return (int)n;
+         n_rec = n;
+      }
+      n_new = n_rec - n_carry;
+      if (last && w_bytes < w_end) return api_fail(SBGPU_ESHAPE, "sbgpu_front_stream_end: the stream ends inside a record");
+      if (n_rec == 0 && w_end > 0) { // no record is whole yet: the window's bytes wait for the next chunk's
+         if (w_end > F->chunk_cap) return api_fail(SBGPU_ESHAPE, "sbgpu_front_stream_push_bgzf: one record exceeds a chunk's capacity: begin the stream with larger chunks");
+         SB_TRY(hipMemcpyAsync(F->buf[b ^ 1] + F->room - w_end, w0, (size_t)w_end, hipMemcpyDeviceToDevice, s));
+         SB_TRY(hipStreamSynchronize(s));
+         F->carry_n = 0, F->carry_rec = 0, F->carry_c0 = 0, F->carry_bytes = w_end;
+         F->carry_max = std::max(F->carry_max, w_end);
+         F->pending = false;
+         return SBGPU_OK;
+      }
+   }
    if (n_rec == 0) {
       if (last) { // nothing more will come: the clusters not yet finished are, without hits
          for (int64_t k = F->k0; k < F->n_clusters; ++k) F->locus_hit_off[(size_t)k + 1] = F->n_hits;
@@ -175,12 +239,13 @@ int compute_pending(sbgpu_front_stream *F, bool last)
       return SBGPU_OK;
    }
    // (made on the device from the window before and the chunk's own offsets: 8 bytes per record never pass through host loops)
-   Grow &W = F->d_win[F->win], &P = F->d_win[F->win ^ 1];
-   W.used = 0;
-   SB_TRY(W.reserve((size_t)(n_rec + 1) * 8, s));
-   hipLaunchKernelGGL(window_off_kernel, dim3((unsigned)((n_rec + 1 + 255) / 256)), dim3(256), 0, s, (int64_t *)W.p,
-                      (const int64_t *)P.p + F->carry_rec, n_carry, F->carry_c0, (const int64_t *)F->d_pend[b].p, n_new, F->carry_bytes);
-   SB_TRY(hipGetLastError());
+   if (F->mode != 2) { // (a window of BGZF members was indexed above)
+      W.used = 0;
+      SB_TRY(W.reserve((size_t)(n_rec + 1) * 8, s));
+      hipLaunchKernelGGL(window_off_kernel, dim3((unsigned)((n_rec + 1 + 255) / 256)), dim3(256), 0, s, (int64_t *)W.p,
+                         (const int64_t *)P.p + F->carry_rec, n_carry, F->carry_c0, (const int64_t *)F->d_pend[b].p, n_new, F->carry_bytes);
+      SB_TRY(hipGetLastError());
+   }
    sbgpu_bamreads_t *R = nullptr;
    SB_RC(sbgpu_bam_decode_device(c, (const uint8_t *)w0, w_bytes, (const int64_t *)W.p, n_rec, &F->opts, s, &R));
    struct ReadsGuard {
@@ -284,7 +349,7 @@ int compute_pending(sbgpu_front_stream *F, bool last)
    F->n_records += n_new, F->n_decoded += n_rec, F->n_accepted += last ? n_reads : reads_done;
    F->k0 += n_done;
    // ---- carry: the window's records from carry_rec on, in front of where the next chunk lands in the OTHER buffer
-   const int64_t cb = w_bytes - c0;
+   const int64_t cb = w_end - c0; // (with it the bytes of a record the window cut: push_bgzf)
    if (cb > F->chunk_cap)
       return api_fail(SBGPU_ESHAPE, "sbgpu_front_stream_push: the records of one cluster exceed a chunk's capacity (" + std::to_string(cb) + " bytes): begin the stream with larger chunks");
    F->carry_n = n_rec - carry_rec, F->carry_rec = carry_rec, F->carry_c0 = c0;
@@ -349,6 +414,8 @@ int sbgpu_front_stream_push(sbgpu_front_stream_t *F, const uint8_t *bytes, int64
 {
    if (!F || F->ended) return api_fail(SBGPU_EINVAL, "sbgpu_front_stream_push: no stream (or it has ended)");
    if (n_bytes < 0 || (n_bytes && !bytes) || n_bytes > F->chunk_cap) return api_fail(SBGPU_EINVAL, "sbgpu_front_stream_push: a chunk holds at most the bytes the stream was begun with");
+   if (F->mode == 2) return api_fail(SBGPU_EINVAL, "sbgpu_front_stream_push: the stream is fed with BGZF members (push_bgzf); the two are not mixed");
+   F->mode = 1;
    SB_TRY(hipSetDevice(F->device));
    // the chunk's record offsets: the caller's (noted while inflating), or found here
    std::vector<int64_t> found;
@@ -381,6 +448,50 @@ int sbgpu_front_stream_push(sbgpu_front_stream_t *F, const uint8_t *bytes, int64
    return SBGPU_OK;
 }
 
+int sbgpu_front_stream_push_bgzf(sbgpu_front_stream_t *F, const uint8_t *file_bytes, int64_t n_bytes, const int64_t *blk_off, const int64_t *out_off,
+                                 int64_t n_blocks, int64_t first_record)
+{
+   if (!F || F->ended) return api_fail(SBGPU_EINVAL, "sbgpu_front_stream_push_bgzf: no stream (or it has ended)");
+   if (F->mode == 1) return api_fail(SBGPU_EINVAL, "sbgpu_front_stream_push_bgzf: the stream is fed with inflated records (push); the two are not mixed");
+   if (n_bytes < 0 || n_blocks < 0 || first_record < 0 || (n_bytes && !file_bytes) || (n_blocks && (!blk_off || !out_off)) || (!n_blocks && n_bytes))
+      return api_fail(SBGPU_EINVAL, "sbgpu_front_stream_push_bgzf: bad argument");
+   for (int64_t k = 0; k < n_blocks; ++k)
+      if (blk_off[k + 1] < blk_off[k] || out_off[k + 1] < out_off[k])
+         return api_fail(SBGPU_EINVAL, "sbgpu_front_stream_push_bgzf: blk_off and out_off must ascend");
+   if (n_blocks && blk_off[n_blocks] - blk_off[0] != n_bytes)
+      return api_fail(SBGPU_EINVAL, "sbgpu_front_stream_push_bgzf: file_bytes must hold exactly the members blk_off[0] .. blk_off[n_blocks] (whole members only)");
+   const int64_t span = n_blocks ? out_off[n_blocks] - out_off[0] : 0;
+   if (span > F->chunk_cap)
+      return api_fail(SBGPU_ESHAPE, "sbgpu_front_stream_push_bgzf: the push inflates to " + std::to_string(span) + " bytes, more than the chunks the stream was begun with");
+   SB_TRY(hipSetDevice(F->device));
+   F->mode = 2;
+   const double t_push = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+   const int nb = F->pending ? F->cur ^ 1 : F->cur;
+   hipStream_t cs = F->up_stream;
+   // the table (kept on the host too: the caller's arrays are free once this returns) and the compressed bytes start their way
+   F->h_blk[nb].assign(blk_off, blk_off + (n_blocks ? n_blocks + 1 : 0));
+   F->h_out[nb].assign(out_off, out_off + (n_blocks ? n_blocks + 1 : 0));
+   if (n_blocks) {
+      const size_t tab = (size_t)(n_blocks + 1) * 8;
+      F->d_tab[nb].used = 0, F->d_comp[nb].used = 0;
+      SB_TRY(F->d_tab[nb].reserve(2 * tab + (size_t)n_blocks, cs));
+      SB_TRY(F->d_comp[nb].reserve((size_t)n_bytes + 16, cs));
+      SB_TRY(hipMemcpyAsync(F->d_tab[nb].p, F->h_blk[nb].data(), tab, hipMemcpyHostToDevice, cs));
+      SB_TRY(hipMemcpyAsync(F->d_tab[nb].p + tab, F->h_out[nb].data(), tab, hipMemcpyHostToDevice, cs));
+      SB_TRY(hipMemcpyAsync(F->d_comp[nb].p, file_bytes, (size_t)n_bytes, hipMemcpyHostToDevice, cs));
+   }
+   SB_TRY(hipEventRecord(F->ev_up[nb], cs));
+   F->t_enqueue += std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t_push;
+   // ... while the pending chunk is inflated and computed (its carry lands in front of where this one will be inflated)
+   if (F->pending) SB_RC(compute_pending(F, false));
+   F->cur = nb;
+   F->pending = true;
+   F->pend_bytes = span, F->pend_records = 0;
+   F->pend_blocks = n_blocks, F->pend_first = first_record;
+   F->comp_bytes += n_bytes;
+   return SBGPU_OK;
+}
+
 int sbgpu_front_stream_end(sbgpu_front_stream_t *F, const sbgpu_annotation_t *an, const sbgpu_insert_t *insert, int32_t read_len, int32_t long_read,
                            const sbgpu_abundance_params_t *params, sbgpu_comm_t *comm, sbgpu_insert_t *insert_used, sbgpu_abundances_t *out,
                            sbgpu_bins_t **bins_out)
@@ -399,7 +510,7 @@ int sbgpu_front_stream_end(sbgpu_front_stream_t *F, const sbgpu_annotation_t *an
       sb::dev_give(F->buf[b], F->buf_cap[b]);
       F->buf[b] = nullptr, F->buf_cap[b] = 0;
    }
-   for (int b = 0; b < 2; ++b) F->d_win[b].release(), F->d_pend[b].release();
+   for (int b = 0; b < 2; ++b) F->d_win[b].release(), F->d_pend[b].release(), F->d_comp[b].release(), F->d_tab[b].release();
    (void)sbgpu_release_idle_memory();
    hipStream_t s = sb::ctx_stream(F->ctx);
    SB_TRY(F->s_foff.reserve(8, s));
@@ -421,7 +532,7 @@ int sbgpu_front_stream_info(const sbgpu_front_stream_t *F, int64_t info[16])
 {
    if (!F || !info) return api_fail(SBGPU_EINVAL, "sbgpu_front_stream_info: null argument");
    const int64_t v[16] = {F->n_records, F->n_accepted, F->n_pairs, F->n_hits, F->n_feat, F->n_filtered, F->mapped_reads, F->n_chunks,
-                          F->k0, F->carry_max, F->redecoded, (int64_t)F->min_free, F->chunk_cap, F->ended ? 1 : 0, (int64_t)F->free_at_begin, 0};
+                          F->k0, F->carry_max, F->redecoded, (int64_t)F->min_free, F->chunk_cap, F->ended ? 1 : 0, (int64_t)F->free_at_begin, F->comp_bytes};
    std::memcpy(info, v, sizeof(v));
    return SBGPU_OK;
 }
@@ -447,7 +558,7 @@ void sbgpu_front_stream_destroy(sbgpu_front_stream_t *F)
       if (F->ev_up[b]) (void)hipEventDestroy(F->ev_up[b]);
    }
    if (F->up_stream) (void)hipStreamDestroy(F->up_stream);
-   for (int b = 0; b < 2; ++b) F->d_win[b].release(), F->d_pend[b].release();
+   for (int b = 0; b < 2; ++b) F->d_win[b].release(), F->d_pend[b].release(), F->d_comp[b].release(), F->d_tab[b].release();
    for (Grow *g : {&F->s_locus, &F->s_foff, &F->s_code, &F->s_left, &F->s_right, &F->s_mass}) g->release();
    delete F;
 }

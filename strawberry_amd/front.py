@@ -268,16 +268,25 @@ class FrontQuantifier(ChainQuantifier):
             i = j
         self.h_chunks, self.chunk_bytes = cuts, int(chunk_bytes)
 
-    def stream_step(self, long_read=0):
+    def stream_step(self, long_read=0, bgzf=None):
         """One pass records (host) -> TPM through sbgpu_front_stream_begin / push / end; the results land where step() puts
-        them (resident mode).  long_read: sbgpu_front_stream_end's flag (1: a long-read sample, bin weights 1 / L).  -> the
-        stream's info (sbgpu_front_stream_info) as a dict."""
+        them (resident mode).  long_read: sbgpu_front_stream_end's flag (1: a long-read sample, bin weights 1 / L).
+        bgzf = (file bytes as a host torch tensor, blk_off, out_off, header length, [(a, b)] member ranges): the same records
+        as a BGZF file, pushed compressed (sbgpu_front_stream_push_bgzf) instead of the inflated chunks.  -> the stream's info
+        (sbgpu_front_stream_info) as a dict."""
         L, ctx = self.ctx.L, self.ctx
         fs = C.c_void_p()
         _lib.check(L.sbgpu_front_stream_begin(ctx.h, C.byref(self._clusters), C.byref(self._opts), self.chunk_bytes, C.byref(fs)), "sbgpu_front_stream_begin")
         try:
-            base = self.h_bytes.data_ptr()
-            for (i, j, b0, b1, off) in self.h_chunks:
+            if bgzf is not None:
+                file, blk, out, first, groups = bgzf
+                base = file.data_ptr()
+                for a, b in groups:
+                    _lib.check(L.sbgpu_front_stream_push_bgzf(fs, base + int(blk[a]), int(blk[b] - blk[a]), blk[a:].ctypes.data, out[a:].ctypes.data,
+                                                              b - a, max(0, first - int(out[a]))), "sbgpu_front_stream_push_bgzf")
+            else:
+                base = self.h_bytes.data_ptr()
+            for (i, j, b0, b1, off) in (self.h_chunks if bgzf is None else ()):
                 _lib.check(L.sbgpu_front_stream_push(fs, base + b0, b1 - b0, off.data_ptr(), j - i), "sbgpu_front_stream_push")
             h = C.c_void_p()
             _lib.check(L.sbgpu_front_stream_end(fs, C.byref(self._an), None if self.empirical else C.byref(self._ins), self.read_len,
@@ -299,7 +308,7 @@ class FrontQuantifier(ChainQuantifier):
             L.sbgpu_front_stream_destroy(fs)
         keys = ("records", "accepted_records", "pairs", "unique_hits", "features", "pairs_dropped_by_the_span_filter", "mapped_reads", "chunks",
                 "clusters_finished", "most_bytes_carried", "records_decoded_twice", "least_free_device_bytes", "chunk_bytes", "ended",
-                "free_device_bytes_at_begin")
+                "free_device_bytes_at_begin", "compressed_bytes_pushed")
         self.stream_info = {k: int(info[i]) for i, k in enumerate(keys)}
         self.counts = dict(self.counts or {}, pairs_dropped_by_the_span_filter=self.stream_info["pairs_dropped_by_the_span_filter"],
                            unique_hits=self.stream_info["unique_hits"])
