@@ -100,6 +100,7 @@ int main(int argc, char **argv)
    int64_t L = 0, P = 0;
    in >> tok >> L;
    sbgpu::LocusBatch batch;
+   batch.keep_handle = true; // (the -f table below reads the handle: sbgpu::ContextTable::host)
    std::vector<std::string> gene_id, gene_strand, gene_chrom;
    std::vector<std::vector<std::string>> tx_id;
    std::vector<std::vector<std::vector<std::pair<uint32_t, uint32_t>>>> tx_exons;
@@ -211,24 +212,20 @@ int main(int argc, char **argv)
    ctxf << "sample\tsample_frag_count\tgene_id\tgene_frag_count\ttranscripts\tFPKMs\tconditional_probabilities\t"
            "class_probabilities\tpath_symbol\tpath_count\tpath_gc_content\tpath_hexmer_entropy\tgc_stretch_0.8_20\t"
            "gc_stretch_0.9_20\tgc_stretch_0.8_40\tgc_stretch_0.9_40\n";
-   // printContext runs after the expression filter, over the surviving isoforms only: a hit counts when
-   // it is compatible with one of them (get_frag_info, include/estimate.hpp:173-196)
+   // printContext runs after the expression filter, over the surviving isoforms only: which bins get a row, in which
+   // order, with how many hits and which probabilities is the library's sbgpu_context_table_host (sbgpu::ContextTable)
    const int64_t n_bins = batch.row_off.back();
-   std::vector<int64_t> last_hit((size_t)n_bins, -1), n_in_bin((size_t)n_bins, 0);
-   for (int64_t h = 0; h < batch.n_hits(); ++h) {
-      const int64_t b = batch.hit_bin[(size_t)h];
-      if (b < 0) continue;
-      const int64_t l = batch.hit_locus[(size_t)h], j0 = batch.iso_off[(size_t)l], niso = batch.iso_off[(size_t)l + 1] - j0;
-      bool any = false;
-      for (int64_t j = 0; j < niso; ++j)
-         any |= ((batch.compat[(size_t)(h * batch.compat_words + (j >> 5))] >> (j & 31)) & 1u) && batch.isoforms[(size_t)(j0 + j)].kept;
-      if (!any) continue;
-      last_hit[(size_t)b] = h;
-      ++n_in_bin[(size_t)b];
+   sbgpu::ContextTable table;
+   try {
+      std::vector<int32_t> keep(batch.isoforms.size() + 1, 0);
+      for (size_t j = 0; j < batch.isoforms.size(); ++j) keep[j] = batch.isoforms[j].kept ? 1 : 0;
+      table = sbgpu::ContextTable::host(batch.bins_handle.get(), batch.compat.data(), batch.compat_words, nullptr, keep.data(), batch.status.data());
+   } catch (const std::exception &e) {
+      std::fprintf(stderr, "error: %s\n", e.what());
+      return 1;
    }
    // -b genome.fa: GC ratio, hexamer entropy and high-GC-stretch flags of every bin's sequence, one kernel launch
-   std::vector<double> bin_gc, bin_entropy;
-   std::vector<uint8_t> bin_flags;
+   sbgpu::BinSequenceStats seq_stats;
    if (argc == 5) {
       for (const std::string &gc : gene_chrom)
          if (gc != chrom) {
@@ -250,65 +247,38 @@ int main(int argc, char **argv)
       }
       try {
          sbgpu::Context ctx(rank % std::max(1, sbgpu_device_count()));
-         sbgpu::BinSequenceStats st = sbgpu::bin_sequence_stats(ctx, batch, genome);
-         bin_gc.swap(st.gc);
-         bin_entropy.swap(st.entropy);
-         bin_flags.swap(st.flags);
+         seq_stats = sbgpu::bin_sequence_stats(ctx, batch, genome);
       } catch (const std::exception &e) {
          std::fprintf(stderr, "error: %s\n", e.what());
          return 1;
       }
    }
    for (int64_t l = 0; l < L; ++l) {
-      const int64_t b0 = batch.row_off[(size_t)l], b1 = batch.row_off[(size_t)l + 1];
       const int64_t j0 = batch.iso_off[(size_t)l], niso = batch.iso_off[(size_t)l + 1] - j0;
       const int64_t s0 = batch.seg_off[(size_t)l], nseg = batch.seg_off[(size_t)l + 1] - s0;
-      uint32_t gene_frags = 0;
-      // bins in std::map order of their coordinate sets (:1552-1563)
-      std::map<std::vector<std::pair<uint32_t, uint32_t>>, int64_t> by_coords;
-      for (int64_t b = b0; b < b1; ++b) {
-         if (n_in_bin[(size_t)b] == 0) continue;
-         std::vector<std::pair<uint32_t, uint32_t>> coords;
-         for (int64_t s = 0; s < nseg; ++s)
-            if ((batch.bin_key[(size_t)(b * batch.key_words + (s >> 5))] >> (s & 31)) & 1u)
-               coords.emplace_back(batch.seg_left[(size_t)(s0 + s)], batch.seg_right[(size_t)(s0 + s)]);
-         by_coords[coords] = b;
-         gene_frags += (uint32_t)n_in_bin[(size_t)b];
-      }
-      std::vector<int64_t> kept;
+      std::vector<int> kept;
       std::vector<const char *> names;
       std::vector<double> fpkm, frac;
       for (int64_t j = 0; j < niso; ++j) {
          if (!batch.isoforms[(size_t)(j0 + j)].kept) continue;
-         kept.push_back(j);
+         kept.push_back((int)j);
          names.push_back(tx_id[(size_t)l][(size_t)j].c_str());
          fpkm.push_back(batch.isoforms[(size_t)(j0 + j)].FPKM);
          frac.push_back(batch.isoforms[(size_t)(j0 + j)].frac);
       }
-      if (kept.empty()) continue;
-      for (const auto &kv : by_coords) {
-         const int64_t b = kv.second, h = last_hit[(size_t)b];
-         std::vector<double> prob;
+      // the locus' rows, already in std::map order of the bins' coordinate sets (:1552-1563)
+      for (int64_t r = table.locus_row_off[(size_t)l]; r < table.locus_row_off[(size_t)l + 1]; ++r) {
+         const int64_t b = table.row_bin[(size_t)r];
          std::vector<uint32_t> sl, sr;
-         for (int64_t j : kept) // the weights of the isoforms the bin's LAST fragment fits (:1556-1563)
-            prob.push_back(((batch.compat[(size_t)(h * batch.compat_words + (j >> 5))] >> (j & 31)) & 1u)
-                              ? batch.F[(size_t)(batch.f_off[(size_t)l] + (b - b0) * niso + j)]
-                              : 0.0);
-         for (const auto &c : kv.first) {
-            sl.push_back(c.first);
-            sr.push_back(c.second);
-         }
-         const int n =
-            bin_gc.empty()
-               ? sbgpu_format_context_row(buf.data(), (int)buf.size(), sample.c_str(), total_mapped, gene_id[(size_t)l].c_str(),
-                                          gene_frags, (int)kept.size(), names.data(), fpkm.data(), prob.data(), frac.data(),
-                                          (int)sl.size(), sl.data(), sr.data(), (uint32_t)n_in_bin[(size_t)b])
-               : sbgpu_format_context_row_seq(buf.data(), (int)buf.size(), sample.c_str(), total_mapped, gene_id[(size_t)l].c_str(),
-                                              gene_frags, (int)kept.size(), names.data(), fpkm.data(), prob.data(), frac.data(),
-                                              (int)sl.size(), sl.data(), sr.data(), (uint32_t)n_in_bin[(size_t)b], bin_gc[(size_t)b],
-                                              bin_entropy[(size_t)b], bin_flags[(size_t)b]);
-         sbgpu::check(n, "sbgpu_format_context_row");
-         ctxf.write(buf.data(), n);
+         for (int64_t s = 0; s < nseg; ++s)
+            if ((batch.bin_key[(size_t)(b * batch.key_words + (s >> 5))] >> (s & 31)) & 1u) {
+               sl.push_back(batch.seg_left[(size_t)(s0 + s)]);
+               sr.push_back(batch.seg_right[(size_t)(s0 + s)]);
+            }
+         const std::string row = table.format_row(l, r, batch.iso_off.data(), batch.f_off.data(), sample.c_str(), total_mapped, gene_id[(size_t)l].c_str(),
+                                                  kept, names, fpkm.data(), frac.data(), (int)sl.size(), sl.data(), sr.data(),
+                                                  seq_stats.gc.empty() ? nullptr : &seq_stats);
+         ctxf.write(row.data(), (std::streamsize)row.size());
       }
    }
    std::fprintf(stderr, "%lld loci, %lld hits, %lld bins, %d mapped reads\n", (long long)L, (long long)batch.n_hits(), (long long)n_bins,

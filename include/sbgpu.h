@@ -907,6 +907,50 @@ void sbgpu_front_stream_destroy(sbgpu_front_stream_t *fs);
 /* F of the EM batch a handle from sbgpu_quantify_host holds: F_out[info[3]] (row-major per locus). */
 int sbgpu_bins_export_weights(const sbgpu_bins_t *bins, double *F_out);
 
+/* ---- the fragment-context table (-f) as arrays ------------------------------------------------
+ * Sample::printContext (src/alignments.cpp:1549-1639) up to the formatting: which bins of every locus get a row, in
+ * which order, with how many hits and which conditional probabilities.  With kept(j) = keep[j] != 0 after the
+ * expression filter (estimate.cpp:346-355):
+ *   - a hit QUALIFIES if it landed in a bin and is compatible with a kept isoform of its locus; a locus whose status is
+ *     SBGPU_EM_INIT_EMPTY, or with no kept isoform, has no qualifying hit and no row;
+ *   - row_hits is a bin's number of qualifying hits (path_count); a bin without one has no row; locus_hits is their sum
+ *     over the locus (gene_frag_count; summed in 32 bits as the reference's uint is);
+ *   - a row holds, for EVERY isoform j of its locus (the caller picks the kept ones, as for FPKM and Frac), the bin's raw
+ *     weight F where the bin's LAST qualifying hit -- the one of the largest index: eb_prob_map[...] = ... overwrites --
+ *     is compatible with j, else 0.0 (estimate.hpp:173-197: that hit's isoforms, not the bin's union);
+ *   - rows of a locus come in std::map order of the bins' coordinate sets (csrc/context_rules.h: ctx_key_less).
+ * The struct: host arrays to fill (any may be NULL) and, on return, the row count and -- device form only -- the device
+ * arrays of all five (the context's memory: valid until its next sbgpu_quantify_* or sbgpu_context_table_device call). */
+typedef struct {
+   int64_t  *locus_row_off;   /* in: [n_loci + 1]  rows of locus l = [off[l], off[l+1])                               */
+   uint32_t *locus_hits;      /* in: [n_loci]      gene_frag_count                                                     */
+   int64_t  *row_bin;         /* in: [n_bins]      global bin of row r (indexes the bin keys, sbgpu_binseq_*'s stats)  */
+   uint32_t *row_hits;        /* in: [n_bins]      path_count                                                          */
+   double   *row_prob;        /* in: [n_elem]      row r of locus l: niso(l) values at                                 */
+                              /*                   f_off[l] + (r - locus_row_off[l]) * niso(l); 0.0 behind a locus' rows */
+   int64_t n_rows;            /* out */
+   const int64_t *d_locus_row_off; const uint32_t *d_locus_hits; const int64_t *d_row_bin; /* out: device form only    */
+   const uint32_t *d_row_hits; const double *d_row_prob;
+} sbgpu_context_table_t;
+/* Host form, the plain statement of the arithmetic: `bins` holds hit -> bin (sbgpu_bins_create, sbgpu_quantify_host),
+ * compat[n_hits * compat_words] are the hits' compat words (sbgpu_exonbin_*, sbgpu_quantify_host's compat_out), F[n_elem]
+ * the bin weights (NULL: the handle's own, sbgpu_quantify_host), keep[n_iso] and status[n_loci] the epilogue's and the
+ * EM's (NULL: everything kept / every locus started).                                                              */
+int sbgpu_context_table_host(const sbgpu_bins_t *bins, const uint32_t *compat, int32_t compat_words, const double *F,
+                             const int32_t *keep, const int32_t *status, sbgpu_context_table_t *out);
+/* on != 0: the context's LATER sbgpu_quantify_resident / sbgpu_front_stream_end calls keep what the table needs -- hit ->
+ * bin as the grouping's 4-byte ranks (made, where the grouping would have left it out), the compat words, F, keep and
+ * status, all where the call had them anyway: nothing is copied, and theta, FPKM, Frac, TPM, keep, status and iters are
+ * the same bits.  Off (the default): those calls are unchanged.                                                    */
+int sbgpu_context_table_keep(sbgpu_ctx_t *ctx, int32_t on);
+/* Device form (csrc/context_device.h): right after such a call, on the handle it returned, before the context's next
+ * call that works in its scratch memory -- every sbgpu_quantify_*, sbgpu_bins_create_device and the other multi-stage
+ * device entries; sbgpu_context_table_device itself and the readers of a handle do not --:
+ * SBGPU_EINVAL otherwise -- a handle made without retention, or a stale one; sbgpu_last_error says which.  One pass over the hits, a sort per locus, a
+ * gather; only the five per-bin / per-locus arrays cross PCIe, whatever the number of hits.  Synchronises on `stream`
+ * (NULL: the context's own).  Loci of more than 4096 isoforms: SBGPU_ESHAPE.                                        */
+int sbgpu_context_table_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins, void *stream, sbgpu_context_table_t *out);
+
 /* ---- per-bin sequence statistics ---------------------------------------
  * What the reference's "bias" option (-b genome.fa) adds to the `-f` table and nothing else
  * (src/bias.cpp holds no code): for every exon bin, over the bases of its segments concatenated

@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <ctime>
 #include <stdexcept>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -175,6 +176,9 @@ public:
    std::vector<float> hit_mass;
    /* results */
    std::vector<int64_t> row_off, f_off, hit_bin;
+   /* keep_handle: quantify() leaves its handle in bins_handle (hit -> bin, F: what ContextTable::host reads) and does not destroy it */
+   bool keep_handle = false;
+   std::shared_ptr<sbgpu_bins_t> bins_handle;
    std::vector<int32_t> count, status, iters;
    std::vector<uint32_t> compat, key, bin_key;
    std::vector<double> F, theta;
@@ -333,7 +337,8 @@ public:
       int rc = sbgpu_bins_export(bins, row_off.data(), nullptr, f_off.data(), count.data(), iso_len.data(), bin_key.data(), nullptr,
                                  hit_bin.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
       if (rc == SBGPU_OK) rc = sbgpu_bins_export_weights(bins, F.data());
-      sbgpu_bins_destroy(bins);
+      bins_handle.reset(bins, sbgpu_bins_destroy);
+      if (!keep_handle) bins_handle.reset();
       check(rc, "sbgpu_bins_export");
       /* the reference's own epilogue, src/estimate.cpp:310-355 */
       isoforms.assign((size_t)n_iso, Isoform());
@@ -492,6 +497,94 @@ inline BinSequenceStats bin_sequence_stats(const Context &ctx, const LocusBatch 
          "sbgpu_binseq_host");
    return out;
 }
+
+/* The `-f` fragment-context table (Sample::printContext, src/alignments.cpp:1549-1639) as arrays, from either form of
+ * sbgpu_context_table_* (include/sbgpu.h): which bins of every locus get a row, in which order, with how many hits and
+ * which conditional probabilities.  host(): on a handle that holds hit -> bin (sbgpu_bins_create, sbgpu_quantify_host).
+ * device(): right after an sbgpu_quantify_resident / sbgpu_front_stream_end call made while sbgpu_context_table_keep was
+ * on, on that call's handle.  format_row() prints one row with the library's formatter; the caller supplies what the
+ * table does not hold: the kept isoforms' names, FPKM and Frac, and the bins' segments (the handle's bin keys).           */
+class ContextTable {
+ public:
+   std::vector<int64_t> locus_row_off, row_bin;
+   std::vector<uint32_t> locus_hits, row_hits;
+   std::vector<double> row_prob;
+   int64_t n_rows = 0;
+
+   static ContextTable host(const sbgpu_bins_t *bins, const uint32_t *compat, int32_t compat_words, const double *F, const int32_t *keep,
+                            const int32_t *status)
+   {
+      ContextTable t;
+      sbgpu_context_table_t s = t.prepare(bins);
+      check(sbgpu_context_table_host(bins, compat, compat_words, F, keep, status, &s), "sbgpu_context_table_host");
+      t.finish(s);
+      return t;
+   }
+   static void keep(const Context &ctx, bool on) { check(sbgpu_context_table_keep(ctx.get(), on ? 1 : 0), "sbgpu_context_table_keep"); }
+   static ContextTable device(const Context &ctx, const sbgpu_bins_t *bins, void *stream = nullptr)
+   {
+      ContextTable t;
+      sbgpu_context_table_t s = t.prepare(bins);
+      check(sbgpu_context_table_device(ctx.get(), bins, stream, &s), "sbgpu_context_table_device");
+      t.finish(s);
+      return t;
+   }
+   /* the probabilities of row r (global) of locus l: one per isoform of the locus */
+   const double *row(int64_t l, int64_t r, const int64_t *iso_off, const int64_t *f_off) const
+   {
+      return row_prob.data() + f_off[l] + (r - locus_row_off[(size_t)l]) * (iso_off[l + 1] - iso_off[l]);
+   }
+   /* Row r of locus l as text.  kept[k]: index (inside the locus) of the k-th surviving isoform; names / fpkm / frac: per
+    * surviving isoform; seg_left / seg_right: the n_seg segments of bin row_bin[r]; stats != nullptr: the six columns of -b. */
+   std::string format_row(int64_t l, int64_t r, const int64_t *iso_off, const int64_t *f_off, const char *sample, int32_t sample_frag_count,
+                          const char *gene_id, const std::vector<int> &kept, const std::vector<const char *> &names, const double *fpkm,
+                          const double *frac, int n_seg, const uint32_t *seg_left, const uint32_t *seg_right,
+                          const BinSequenceStats *stats = nullptr) const
+   {
+      const double *p = row(l, r, iso_off, f_off);
+      std::vector<double> cond(kept.size());
+      for (size_t k = 0; k < kept.size(); ++k) cond[k] = p[kept[k]];
+      const int64_t b = row_bin[(size_t)r];
+      std::string buf(1024, '\0');
+      for (int pass = 0; pass < 2; ++pass) {
+         const int n = stats ? sbgpu_format_context_row_seq(&buf[0], (int)buf.size(), sample, sample_frag_count, gene_id, locus_hits[(size_t)l],
+                                                            (int)kept.size(), names.data(), fpkm, cond.data(), frac, n_seg, seg_left, seg_right,
+                                                            row_hits[(size_t)r], stats->gc[(size_t)b], stats->entropy[(size_t)b], stats->flags[(size_t)b])
+                             : sbgpu_format_context_row(&buf[0], (int)buf.size(), sample, sample_frag_count, gene_id, locus_hits[(size_t)l],
+                                                        (int)kept.size(), names.data(), fpkm, cond.data(), frac, n_seg, seg_left, seg_right,
+                                                        row_hits[(size_t)r]);
+         check(n < 0 ? n : 0, "sbgpu_format_context_row");
+         if (n < (int)buf.size()) {
+            buf.resize((size_t)n);
+            break;
+         }
+         buf.assign((size_t)n + 1, '\0');
+      }
+      return buf;
+   }
+
+ private:
+   sbgpu_context_table_t prepare(const sbgpu_bins_t *bins)
+   {
+      int64_t info[8];
+      check(sbgpu_bins_info(bins, info), "sbgpu_bins_info");
+      locus_row_off.assign((size_t)info[0] + 1, 0);
+      locus_hits.assign((size_t)info[0] + 1, 0);
+      row_bin.assign((size_t)info[2] + 1, 0);
+      row_hits.assign((size_t)info[2] + 1, 0);
+      row_prob.assign((size_t)info[3] + 1, 0.0);
+      sbgpu_context_table_t s = {};
+      s.locus_row_off = locus_row_off.data(), s.locus_hits = locus_hits.data(), s.row_bin = row_bin.data(), s.row_hits = row_hits.data();
+      s.row_prob = row_prob.data();
+      return s;
+   }
+   void finish(const sbgpu_context_table_t &s)
+   {
+      n_rows = s.n_rows;
+      row_bin.resize((size_t)n_rows);
+      row_hits.resize((size_t)n_rows);
+   }
+};
 
 } // namespace sbgpu
 #endif /* SBGPU_HOST_HPP_ */

@@ -40,6 +40,7 @@ SYMBOLS = [
     "sbgpu_front_stream_begin", "sbgpu_front_stream_push", "sbgpu_front_stream_end", "sbgpu_front_stream_info", "sbgpu_front_stream_hits",
     "sbgpu_front_stream_destroy", "sbgpu_em_run_device_split",
     "sbgpu_bgzf_index_host", "sbgpu_bgzf_inflate_host", "sbgpu_bgzf_inflate_device", "sbgpu_bam_index_device", "sbgpu_bam_index_device_info", "sbgpu_front_stream_push_bgzf",
+    "sbgpu_context_table_host", "sbgpu_context_table_keep", "sbgpu_context_table_device",
 ]
 
 
@@ -138,6 +139,11 @@ class sbgpu_hits_t(C.Structure):
         ("feat_left", C.c_void_p),
         ("feat_right", C.c_void_p),
     ]
+
+
+class sbgpu_context_table_t(C.Structure):
+    _fields_ = ([(n, C.c_void_p) for n in ("locus_row_off", "locus_hits", "row_bin", "row_hits", "row_prob")] + [("n_rows", C.c_int64)] +
+                [(n, C.c_void_p) for n in ("d_locus_row_off", "d_locus_hits", "d_row_bin", "d_row_hits", "d_row_prob")])
 
 
 _lib = None
@@ -295,6 +301,9 @@ def load():
     L.sbgpu_binseq_device.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.sbgpu_binseq_host.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp]
     L.sbgpu_binweight_host.argtypes = [vp, C.c_int64, vp, vp, vp, vp, C.POINTER(sbgpu_insert_t), vp]
+    L.sbgpu_context_table_host.argtypes = [vp, vp, C.c_int32, vp, vp, vp, C.POINTER(sbgpu_context_table_t)]
+    L.sbgpu_context_table_keep.argtypes = [vp, C.c_int32]
+    L.sbgpu_context_table_device.argtypes = [vp, vp, vp, C.POINTER(sbgpu_context_table_t)]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("sbgpu_device_count", "sbgpu_plan_classes"):

@@ -9,6 +9,7 @@ uniform along the transcript, mates of 75 bases mapped through the isoform's exo
 isoforms or none (a mate shifted by a few bases; an unspliced left mate that runs into the intron).  Hits come out
 sorted by (locus, left end, right end) -- HitCluster::collapseAndFilterHits' order -- in the layout of sbgpu_hits_t.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -221,11 +222,14 @@ class ChainQuantifier:
     then FPKM / TPM on the host arrays the call returns (the caller's own epilogue, as in the reference)."""
 
     def __init__(self, ctx, n_loci=60000, n_frags=2e8, seed=31, read_len=75, loci_subset=None, pin=True, resident=False,
-                 empirical=False, comm=None, min_isoform_frac=0.0):
+                 empirical=False, comm=None, min_isoform_frac=0.0, keep_context=False):
         """resident=True: step() is sbgpu_quantify_resident -- the chain with the reference's pass 1 in front (empirical=True: no
         insert-size law is given, the device builds it from the hits; Strawberry's default mode) and the FPKM / Frac / TPM
         epilogue behind it, the collectives over `comm` (dist.AbiComm / dist.HostComm; None: a world of one) inside the call;
-        theta, FPKM, Frac, keep and TPM land in the object's host arrays, `law` holds the insert-size law that was used."""
+        theta, FPKM, Frac, keep and TPM land in the object's host arrays, `law` holds the insert-size law that was used.
+        keep_context=True (resident only): every step asks the context to keep what the `-f` table needs (sbgpu_context_table_keep,
+        switched on for the step's own call only: the context may be shared) and the last step's handle lives on in
+        `context_handle`; context_table() builds the table from it on the device."""
         import torch
         self.torch, self.ctx = torch, ctx
         self.dev = torch.device("cuda", ctx.device)
@@ -244,6 +248,10 @@ class ChainQuantifier:
         self._ins = self.insert._struct(read_len)
         self.info = None
         self.resident, self.empirical, self.comm = bool(resident), bool(empirical), comm
+        self.keep_context, self.context_handle = bool(keep_context), None
+        if keep_context:
+            if not resident:
+                raise ValueError("keep_context needs resident=True: only the resident entry keeps the table's inputs")
         if resident:
             self.fpkm, self.frac, self.tpm = np.zeros(self.n_iso + 1), np.zeros(self.n_iso + 1), np.zeros(self.n_iso + 1)
             self.keep = np.zeros(self.n_iso + 1, np.int32)
@@ -279,7 +287,38 @@ class ChainQuantifier:
             bins = eb.LocusBins.__new__(eb.LocusBins)
             bins._export(L, self.annot, h, self.n_hits, self.annot.compat_words, self.annot.key_words, with_hit_bin=False)   # destroys the handle
             return bins
-        L.sbgpu_bins_destroy(h)
+        self._retire(h)
+
+    def _retire(self, h):
+        """The step's handle: destroyed, or -- keep_context -- kept for context_table() until the next step's replaces it."""
+        L = self.ctx.L
+        if self.context_handle is not None:
+            L.sbgpu_bins_destroy(self.context_handle)
+            self.context_handle = None
+        if self.keep_context:
+            self.context_handle = h
+        else:
+            L.sbgpu_bins_destroy(h)
+
+    @contextlib.contextmanager
+    def _retention(self):
+        """keep_context: retention on around this object's own resident call, off behind it (what the call kept stays until the
+        context's next quantify call) -- another quantifier on the same context neither gains nor loses it."""
+        if not self.keep_context:
+            yield
+            return
+        _lib.check(self.ctx.L.sbgpu_context_table_keep(self.ctx.h, 1), "sbgpu_context_table_keep")
+        try:
+            yield
+        finally:
+            self.ctx.L.sbgpu_context_table_keep(self.ctx.h, 0)
+
+    def context_table(self):
+        """The `-f` table of the last step as arrays (context.ContextTable), built on the device."""
+        from . import context
+        if self.context_handle is None:
+            raise _lib.SbgpuError("context_table: no step has run with keep_context=True")
+        return context.context_table_device(self.ctx, self.context_handle)
 
     def set_law(self, insert):
         """Quantify under a GIVEN insert-size law from now on (an InsertSize: -i mean/sd, or an empirical law made elsewhere)."""
@@ -290,10 +329,11 @@ class ChainQuantifier:
         """sbgpu_quantify_resident on device hits; mapped_reads: this rank's part of Sample::total_mapped_reads()."""
         if self.mapped_override is not None:
             mapped_reads = self.mapped_override
-        _lib.check(L.sbgpu_quantify_resident(self.ctx.h, C.byref(self._an), C.byref(hits_struct), d_mass, hit_off,
-                                             None if self.empirical else C.byref(self._ins), self.read_len, 0, int(mapped_reads),
-                                             C.byref(self._par), self.comm.h if self.comm is not None else None,
-                                             C.byref(self._used), C.byref(self._out), C.byref(h)), "sbgpu_quantify_resident")
+        with self._retention():
+            _lib.check(L.sbgpu_quantify_resident(self.ctx.h, C.byref(self._an), C.byref(hits_struct), d_mass, hit_off,
+                                                 None if self.empirical else C.byref(self._ins), self.read_len, 0, int(mapped_reads),
+                                                 C.byref(self._par), self.comm.h if self.comm is not None else None,
+                                                 C.byref(self._used), C.byref(self._out), C.byref(h)), "sbgpu_quantify_resident")
         u = self._used
         self.law = {"mean": u.mean, "sd": u.sd, "use_emp": int(u.use_emp), "start_offset": int(u.start_offset),
                     "end_offset": int(u.end_offset), "total_reads": int(u.total_reads)}
@@ -352,6 +392,9 @@ class ChainQuantifier:
         """Release what this object keeps with the (shared) context: the pinned annotation.  The pin is keyed on the
         annotation arrays' addresses (+ a sampled fingerprint); it must not outlive the arrays.  Also on __exit__ / __del__."""
         self.unpin()
+        if getattr(self, "context_handle", None) is not None:
+            self.ctx.L.sbgpu_bins_destroy(self.context_handle)
+            self.context_handle = None
 
     def unpin(self):
         """Releases THIS object's pin only: another quantifier on the same context may have pinned its own annotation since
@@ -368,6 +411,6 @@ class ChainQuantifier:
 
     def __del__(self):
         try:
-            self.unpin()
+            self.close()
         except Exception:       # interpreter shutdown: the library may be gone already
             pass

@@ -128,6 +128,9 @@ struct GroupingHooks {
    std::function<void(const int64_t *row_off, const int64_t *f_off)> rows_known;
    // called once the pairs' fill kernel is launched, before the host-side handle is built
    std::function<int(const DeviceGrouping &)> after_pairs;
+   // non-null: every hit's bin as its rank inside its locus (int32, -1: in no bin) is made -- the single-pass kernels leave
+   // it out otherwise -- and *d_hit_bin_local says where it is: the context's scratch, valid until its next grouping
+   const int32_t **d_hit_bin_local = nullptr;
 };
 // sbgpu_bins_create_device with the segment lists made beforehand (nullptr: made inside)
 int bins_create_device_impl(sbgpu_ctx_t *ctx, const sbgpu_annotation_t *annot, const sbgpu_hits_t *d_hits, const float *d_mass,
@@ -168,7 +171,7 @@ hipStream_t ctx_stream(const sbgpu_ctx_t *ctx); // the context's own stream
 hipStream_t ctx_aux_stream(const sbgpu_ctx_t *ctx, int i); // one of the context's side streams (0..7; the EM's kinds use 0, 1, 2, 6)
 int ctx_cu_count(const sbgpu_ctx_t *ctx);
 int ctx_device(const sbgpu_ctx_t *ctx);        // the HIP device the context was made on
-// device scratch that lives with the context (slot 0..7, grows on demand, never shrinks): valid until the next
+// device scratch that lives with the context (slot 0..8; 8 is the context table's, grows on demand, never shrinks): valid until the next
 // request for the same slot; one host thread per context
 hipError_t ctx_scratch(sbgpu_ctx_t *ctx, int slot, size_t bytes, char **out);
 // Device allocations that change hands (a handle's arenas, a plan's arena): a hipMalloc / hipFree pair per call costs a
@@ -224,4 +227,29 @@ void bins_set_grouping(sbgpu_bins_t *bins, bool on_device, const std::string &wh
 void bins_set_hit_bin(sbgpu_bins_t *bins, std::vector<int64_t> &&hit_bin);
 void bins_set_device_hit_bin(sbgpu_bins_t *bins, char *arena, size_t capacity, int64_t n); // hit -> bin left in HBM (the handle owns the arena)
 const double *bins_weights_tail(const sbgpu_bins_t *bins, size_t at); // F.data() + at (the empirical histogram lives there)
+// What the fragment-context table (context_api.hip, context_host.cpp) reads of a handle
+struct BinsContextView {
+   int64_t n_loci = 0, n_iso = 0, n_bins = 0, n_elem = 0, n_hits = 0; // n_hits: entries of hit -> bin the handle holds (host or device)
+   int32_t key_words = 0, compat_words = 0;
+   const int64_t *row_off = nullptr, *iso_off = nullptr, *f_off = nullptr; // host, [n_loci + 1]
+   const double *F = nullptr;       // host, [n_elem]: the weights of a handle from sbgpu_quantify_host, else null
+   const uint32_t *d_key = nullptr; // device, [n_bins * key_words]: the bin keys of a device grouping, else null
+   uint64_t context_serial = 0;     // the resident call that kept the table's inputs for this handle (0: none did)
+};
+BinsContextView bins_context_view(const sbgpu_bins_t *bins);
+void bins_set_context_serial(sbgpu_bins_t *bins, uint64_t serial);
+// What a resident call leaves for sbgpu_context_table_device when the context was asked to (sbgpu_context_table_keep): device
+// pointers into the context's scratch, valid until the context's next sbgpu_quantify_* call (which clears the record).
+struct ContextKeep {
+   bool on = false;      // later resident calls retain
+   uint64_t serial = 0;  // the retaining call's number, shared with its handle; 0: nothing is retained
+   int64_t n_hits = 0, n_loci = 0, n_iso = 0;
+   int32_t compat_words = 0;
+   const uint32_t *d_compat = nullptr;      // [n_hits * compat_words]
+   const int32_t *d_hit_bin_local = nullptr; // [n_hits] rank of the hit's bin inside its locus, -1: none
+   const double *d_F = nullptr;             // [n_elem] the raw bin weights (no EM kernel writes them)
+   const int32_t *d_keep = nullptr, *d_status = nullptr;
+   std::vector<int64_t> locus_hit_off;      // host copy, [n_loci + 1]
+};
+ContextKeep *ctx_context_keep(sbgpu_ctx_t *ctx);
 } // namespace sb

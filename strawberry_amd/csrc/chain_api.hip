@@ -6,6 +6,7 @@
 #include <climits>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -54,6 +55,11 @@ static int quantify_impl(sbgpu_ctx_t *c, const sbgpu_annotation_t *an, const sbg
    if (!c || !an || !hits || !bins_out || (!ro && (!theta_out || !status_out || !iters_out)))
       return api_fail(SBGPU_EINVAL, "sbgpu_quantify_host: null argument");
    *bins_out = nullptr;
+   // what an earlier resident call kept for sbgpu_context_table_device lives in the scratch this call reuses: gone from here on
+   sb::ContextKeep *const keep_rec = sb::ctx_context_keep(c);
+   keep_rec->serial = 0;
+   const bool retain = keep_rec->on && ro && on_dev;
+   const int32_t *d_hit_bin_local = nullptr;
    const int64_t nl = an->n_loci, nh = hits->n_hits;
    if (nl < 1 || nh < 0) return api_fail(SBGPU_EINVAL, "sbgpu_quantify_host: bad counts");
    if (!an->iso_off || !an->exon_off || !an->seg_off || (nh && (!hits->hit_locus || !hits->feat_off || !hit_mass)))
@@ -561,6 +567,7 @@ static int quantify_impl(sbgpu_ctx_t *c, const sbgpu_annotation_t *an, const sbg
          rest_launched = true;
          return launch_weights(g.pairs);
       };
+      if (retain) hooks.d_hit_bin_local = &d_hit_bin_local; // (the context table reads hit -> bin as the grouping's 4-byte local ranks)
       // (hits given on the device: the caller did not ask for hit -> bin, so it is not made)
       rc = sb::bins_create_device_impl(c, an, &dh, d_mass, locus_hit_off.data(), cw, kw, d_compat, d_key, on_dev ? nullptr : d_hit_bin, s,
                                        res ? &res->iso : &iso_pre, &bins, d_span, d_fhash, &hooks);
@@ -663,6 +670,17 @@ static int quantify_impl(sbgpu_ctx_t *c, const sbgpu_annotation_t *an, const sbg
    }
 #undef SB_TRY
 #undef SB_RC
+   if (retain) {
+      // sbgpu_context_table_keep: say where the table's inputs are (all of them this call's scratch, nothing is copied)
+      static std::atomic<uint64_t> serial{0};
+      keep_rec->serial = ++serial;
+      keep_rec->n_hits = nh, keep_rec->n_loci = nl, keep_rec->n_iso = n_iso, keep_rec->compat_words = cw;
+      keep_rec->d_compat = d_compat, keep_rec->d_hit_bin_local = d_hit_bin_local;
+      keep_rec->d_F = (const double *)(w.p + q_F);
+      keep_rec->d_keep = (const int32_t *)(w.p + q_keep), keep_rec->d_status = (const int32_t *)(w.p + q_st);
+      keep_rec->locus_hit_off = locus_hit_off;
+      sb::bins_set_context_serial(bins, keep_rec->serial);
+   }
    guard.b = nullptr;
    *bins_out = bins;
    stage("results + handle");

@@ -701,7 +701,8 @@ int bins_create_device_impl(sbgpu_ctx_t *c, const sbgpu_annotation_t *an, const 
    }
    // hit -> bin: the single-pass kernels leave it out; it is made where somebody reads it (the caller's hit_bin, the
    // ordered masses below).  Loci the big table served have theirs already.
-   if (single_pass && (d_hit_bin || flags == sb::kBinsFractional) && nh) {
+   const bool want_local = hooks && hooks->d_hit_bin_local;
+   if (single_pass && (d_hit_bin || want_local || flags == sb::kBinsFractional) && nh) {
       std::vector<int32_t> todo;
       for (int64_t l = 0; l < nl; ++l)
          if (nb[(size_t)l] <= sb::kBinsMaxMid) todo.push_back((int32_t)l);
@@ -803,6 +804,7 @@ int bins_create_device_impl(sbgpu_ctx_t *c, const sbgpu_annotation_t *an, const 
    sb::ctx_stage_end(c, s);
    SB_TRY3(hipGetLastError());
    stage("pairs fill launch");
+   if (want_local) *hooks->d_hit_bin_local = a.hit_bin_local;
    // the caller's kernels behind the grouping (bin weights, EM) go into the stream now
    if (hooks && hooks->after_pairs) {
       const sb::DeviceGrouping g = {row_off.data(), f_off.data(), n_bins, f_off[(size_t)nl], (const int32_t *)(d2 + p_cnt), &dp};

@@ -55,6 +55,7 @@ struct sbgpu_bins {
    // was not used (empty: nobody asked it, e.g. sbgpu_bins_create called directly)
    bool grouped_on_device = false;
    std::string host_grouping_reason;
+   uint64_t context_serial = 0; // the resident call that kept the context table's inputs for this handle (sbgpu_context_table_keep)
    ~sbgpu_bins()
    {
       sb::dev_give(dev.arena, dev.capacity);
@@ -606,6 +607,19 @@ void bins_set_device_hit_bin(sbgpu_bins_t *b, char *arena, size_t capacity, int6
    b->n_dev_hit_bin = n;
 }
 const double *bins_weights_tail(const sbgpu_bins_t *b, size_t at) { return b->F.data() + at; }
+void bins_set_context_serial(sbgpu_bins_t *b, uint64_t serial) { b->context_serial = serial; }
+BinsContextView bins_context_view(const sbgpu_bins_t *b)
+{
+   BinsContextView v;
+   v.n_loci = b->n_loci, v.n_iso = b->n_iso, v.n_bins = b->n_bins, v.n_elem = b->n_elem;
+   v.n_hits = b->hit_bin.empty() ? b->n_dev_hit_bin : (int64_t)b->hit_bin.size();
+   v.key_words = b->key_words, v.compat_words = b->compat_words;
+   v.row_off = b->row_off.data(), v.iso_off = b->iso_off.data(), v.f_off = b->f_off.data();
+   if ((int64_t)b->F.size() >= b->n_elem && !(b->F.empty() && b->n_bins > 0)) v.F = b->F.data();
+   if (b->dev_bins.arena) v.d_key = (const uint32_t *)(b->dev_bins.arena + b->dev_bins.o_key);
+   v.context_serial = b->context_serial;
+   return v;
+}
 const DevicePairs *bins_device_pairs(const sbgpu_bins_t *b) { return b && b->pairs_on_device ? &b->dev : nullptr; }
 int bins_from_groups(const sbgpu_annotation_t *an, int32_t compat_words, int32_t key_words, const int64_t *row_off,
                      const DeviceBinArrays &arrays, int64_t n_hits_used, const DevicePairs *pairs, const std::vector<int32_t> *iso_len,

@@ -129,7 +129,7 @@ class FrontQuantifier(ChainQuantifier):
     def __init__(self, ctx, n_loci=60000, n_frags=2e8, seed=31, read_len=75, loci_subset=None, **resident_kw):
         """loci_subset = (rank, world): this rank's loci of ONE sample (locus l on rank l mod world, as the chain shards) --
         its records only; the clusters, like the reference's, are the shard's own gene models.  resident_kw: ChainQuantifier's
-        resident / empirical / comm / min_isoform_frac (the last stage is then sbgpu_quantify_resident: records -> TPM)."""
+        resident / empirical / comm / min_isoform_frac / keep_context (the last stage is then sbgpu_quantify_resident: records -> TPM)."""
         super().__init__(ctx, n_loci=n_loci, n_frags=n_frags, seed=seed, read_len=read_len, loci_subset=loci_subset, pin=True, **resident_kw)
         torch = self.torch
         t = time.perf_counter()
@@ -215,7 +215,7 @@ class FrontQuantifier(ChainQuantifier):
             info = (C.c_int64 * 8)()
             _lib.check(L.sbgpu_bins_info(h, info), "sbgpu_bins_info")
             self.info = {"n_bins": int(info[2]), "n_elem": int(info[3]), "n_pairs": int(info[4]), "hits_in_bins": int(info[6])}
-        L.sbgpu_bins_destroy(h)
+        self._retire(h)         # (the table reads the hits' compat words, not the hits: the unique hits' handle may go)
         L.sbgpu_uniq_dev_destroy(hu)
         self.stage_wall_ms = ms
 
@@ -289,9 +289,10 @@ class FrontQuantifier(ChainQuantifier):
             for (i, j, b0, b1, off) in (self.h_chunks if bgzf is None else ()):
                 _lib.check(L.sbgpu_front_stream_push(fs, base + b0, b1 - b0, off.data_ptr(), j - i), "sbgpu_front_stream_push")
             h = C.c_void_p()
-            _lib.check(L.sbgpu_front_stream_end(fs, C.byref(self._an), None if self.empirical else C.byref(self._ins), self.read_len,
-                                                int(long_read), C.byref(self._par), self.comm.h if self.comm is not None else None, C.byref(self._used),
-                                                C.byref(self._out), C.byref(h)), "sbgpu_front_stream_end")
+            with self._retention():
+                _lib.check(L.sbgpu_front_stream_end(fs, C.byref(self._an), None if self.empirical else C.byref(self._ins), self.read_len,
+                                                    int(long_read), C.byref(self._par), self.comm.h if self.comm is not None else None, C.byref(self._used),
+                                                    C.byref(self._out), C.byref(h)), "sbgpu_front_stream_end")
             u = self._used
             self.law = {"mean": u.mean, "sd": u.sd, "use_emp": int(u.use_emp), "start_offset": int(u.start_offset),
                         "end_offset": int(u.end_offset), "total_reads": int(u.total_reads)}
@@ -303,7 +304,7 @@ class FrontQuantifier(ChainQuantifier):
             self.front_hit_off = np.ctypeslib.as_array(C.cast(hoff, C.POINTER(C.c_int64)), shape=(self.n_loci + 1,)).copy()
             info = (C.c_int64 * 16)()
             _lib.check(L.sbgpu_front_stream_info(fs, info), "sbgpu_front_stream_info")
-            L.sbgpu_bins_destroy(h)
+            self._retire(h)
         finally:
             L.sbgpu_front_stream_destroy(fs)
         keys = ("records", "accepted_records", "pairs", "unique_hits", "features", "pairs_dropped_by_the_span_filter", "mapped_reads", "chunks",

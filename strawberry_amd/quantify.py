@@ -127,9 +127,11 @@ class LocusQuantifier:
         return self.solve(total_mapped_reads, **abundance_kw)
 
 
-def quantify_host(annot, hits, insert, read_len, long_read=False, ctx=None, device=0):
+def quantify_host(annot, hits, insert, read_len, long_read=False, ctx=None, device=0, context_keep=None, context_status=None):
     """sbgpu_quantify_host: the whole chain as one C-ABI call on host arrays (what a C / C++ driver uses).
     insert=None: build the empirical insert-size distribution from the hits.
+    context_keep (per isoform, from the caller's epilogue; context_status: the EM's per locus, default this call's): also the
+    `-f` table's arrays from the handle, through the host form (context.context_table_host) -> "context".
     -> dict(theta, status, iters, compat, bins (LocusBins incl. hit_bin), F, insert (mean, sd, use_emp, ...))"""
     from .exonbin import LocusBins
     ctx = ctx or default_context(device)
@@ -156,19 +158,30 @@ def quantify_host(annot, hits, insert, read_len, long_read=False, ctx=None, devi
     if used.use_emp:
         n = used.end_offset - used.start_offset + 1
         emp = np.ctypeslib.as_array(used.emp_hist, shape=(n,)).copy()
+    table = None
+    if context_keep is not None:
+        from . import context
+        try:
+            table = context.context_table_host(handle, compat[:hits.n_hits], keep=context_keep,
+                                               status=status[:annot.n_loci] if context_status is None else context_status)
+        except Exception:
+            L.sbgpu_bins_destroy(handle)
+            raise
     bins = LocusBins.__new__(LocusBins)
     bins._export(L, annot, handle, hits.n_hits, cw, kw, with_hit_bin=True)   # destroys the handle
     return {"theta": theta[:n_iso], "status": status[:annot.n_loci], "iters": iters[:annot.n_loci],
-            "compat": compat[:hits.n_hits], "bins": bins, "F": F[:int(info[3])],
+            "compat": compat[:hits.n_hits], "bins": bins, "F": F[:int(info[3])], "context": table,
             "insert": {"mean": used.mean, "sd": used.sd, "use_emp": bool(used.use_emp), "start_offset": used.start_offset,
                        "end_offset": used.end_offset, "total_reads": used.total_reads, "emp_hist": emp}}
 
 
 def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=False, ctx=None, device=0, comm=None,
-                      min_isoform_frac=0.0, filter_by_expression=True, effective_len_norm=False):
+                      min_isoform_frac=0.0, filter_by_expression=True, effective_len_norm=False, with_context=False):
     """sbgpu_quantify_resident on host hits brought to the device first (torch owns the copies): pass 1 (insert=None: the
     empirical insert-size law, built on the device), bins, weights, EM, FPKM / Frac / keep, the FPKM all-reduce over `comm`
     (dist.AbiComm / dist.HostComm; None: a world of one), TPM.  The hits must come grouped by locus.
+    with_context: the call keeps what the `-f` table needs (sbgpu_context_table_keep) and the table is built on the device
+    (context.context_table_device) -> "context"; "bins": the handle's LocusBins (the rows index its bins).
     -> dict(theta, fpkm, frac, tpm, keep, status, iters, insert, total_fpkm, total_mapped_reads, n_frag_lens, info)"""
     import torch
     ctx = ctx or default_context(device)
@@ -198,19 +211,39 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     ins = insert._struct(read_len, long_read) if insert is not None else None
     handle = C.c_void_p()
     torch.cuda.synchronize(dev)
-    _lib.check(L.sbgpu_quantify_resident(ctx.h, C.byref(a), C.byref(hs), d_mass.data_ptr(), off.ctypes.data,
-                                         C.byref(ins) if ins is not None else None, int(read_len), int(long_read), int(mapped_reads),
-                                         C.byref(par), comm.h if comm is not None else None, C.byref(used), C.byref(out),
-                                         C.byref(handle)), "sbgpu_quantify_resident")
+    if with_context:
+        _lib.check(L.sbgpu_context_table_keep(ctx.h, 1), "sbgpu_context_table_keep")
+    try:
+        _lib.check(L.sbgpu_quantify_resident(ctx.h, C.byref(a), C.byref(hs), d_mass.data_ptr(), off.ctypes.data,
+                                             C.byref(ins) if ins is not None else None, int(read_len), int(long_read), int(mapped_reads),
+                                             C.byref(par), comm.h if comm is not None else None, C.byref(used), C.byref(out),
+                                             C.byref(handle)), "sbgpu_quantify_resident")
+    finally:
+        if with_context:
+            L.sbgpu_context_table_keep(ctx.h, 0)    # (what the call kept stays until the context's next quantify call)
     emp = None
     if used.use_emp:
         emp = np.ctypeslib.as_array(used.emp_hist, shape=(used.end_offset - used.start_offset + 1,)).copy()
     info = (C.c_int64 * 8)()
     _lib.check(L.sbgpu_bins_info(handle, info), "sbgpu_bins_info")
-    L.sbgpu_bins_destroy(handle)
+    table = bins = None
+    if with_context:
+        from . import context
+        from .exonbin import LocusBins
+        try:
+            table = context.context_table_device(ctx, handle)
+        except Exception:
+            L.sbgpu_bins_destroy(handle)
+            raise
+        bins = LocusBins.__new__(LocusBins)
+        bins._export(L, annot, handle, hits.n_hits, annot.compat_words, annot.key_words, with_hit_bin=False)   # destroys the handle
+    else:
+        L.sbgpu_bins_destroy(handle)
     r = {k: (v[:n_iso] if k not in ("status", "iters") else v[:nl]) for k, v in res.items()}
     r.update({"insert": {"mean": used.mean, "sd": used.sd, "use_emp": bool(used.use_emp), "start_offset": used.start_offset,
                          "end_offset": used.end_offset, "total_reads": used.total_reads, "emp_hist": emp},
               "total_fpkm": float(out.total_fpkm), "total_mapped_reads": int(out.total_mapped_reads), "n_frag_lens": int(out.n_frag_lens),
               "info": {"n_bins": int(info[2]), "n_elem": int(info[3]), "n_pairs": int(info[4])}})
+    if with_context:
+        r.update(context=table, bins=bins)
     return r
