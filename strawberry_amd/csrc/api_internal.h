@@ -152,6 +152,13 @@ int64_t bam_index_device_impl(sbgpu_ctx_t *ctx, const uint8_t *d_bytes, int64_t 
                               int64_t n_guess, int64_t guess_add, const std::function<int64_t *(int64_t)> &alloc, int64_t *tail_start,
                               void *stream);
 int api_fail(int code, const std::string &msg); // records sbgpu_last_error(), returns code
+// a HIP call that failed: "<what>: <HIP's text>", and the code an allocation's failure gets (SBGPU_ENOMEM when the device is full);
+// static: the library exports no C++ helper of its own
+static inline std::string hip_error_text(const char *what, hipError_t e) { return std::string(what) + ": " + hipGetErrorString(e); }
+static inline int api_fail_hip(hipError_t e, const char *what)
+{
+   return api_fail(e == hipErrorOutOfMemory ? SBGPU_ENOMEM : SBGPU_EHIP, hip_error_text(what, e));
+}
 // Experiment switches: SBGPU_* variables that select paths DESIGN.md / profiles/EXPERIMENTS_*.md record as measured and NOT adopted
 // (phased execution, launch graphs, tile and schedule variants, A/B forms of the grouping ...).  They exist only in a library built
 // with -DSB_EXPERIMENTS (`make experiments` -> libsbgpu_exp.so, never shipped, never timed by bench.py); the shipped library does

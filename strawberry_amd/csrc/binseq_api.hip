@@ -113,7 +113,7 @@ int sbgpu_binseq_host(sbgpu_ctx_t *c, const uint8_t *genome, int64_t genome_star
    char *d = nullptr;
    hipError_t e = hipMalloc(&d, total);
    if (e != hipSuccess)
-      return api_fail(e == hipErrorOutOfMemory ? SBGPU_ENOMEM : SBGPU_EHIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+      return sb::api_fail_hip(e, "hipMalloc");
    hipStream_t s = sb::ctx_stream(c);
    auto bail = [&](hipError_t err, const char *what) {
       (void)hipFree(d);

@@ -86,7 +86,7 @@ int sbgpu_context_table_device(sbgpu_ctx_t *c, const sbgpu_bins_t *bins, void *s
    const size_t o_prob = off; off += up(ne1 * 8);
    char *d = nullptr;
    if (hipError_t e = sb::ctx_scratch(c, 8, off, &d); e != hipSuccess)
-      return api_fail(e == hipErrorOutOfMemory ? SBGPU_ENOMEM : SBGPU_EHIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+      return sb::api_fail_hip(e, "hipMalloc");
    // (one host block for the uploads: it lives until the call's last synchronisation; SB_TRY synchronises before it leaves early)
    std::vector<char> host(upload_bytes, 0);
    std::memcpy(host.data() + o_hoff, k->locus_hit_off.data(), nl1 * 8);

@@ -404,7 +404,7 @@ int sbgpu_front_stream_begin(sbgpu_ctx_t *c, const sbgpu_clusters_t *cl, const s
    }
    if (e != hipSuccess) {
       sbgpu_front_stream_destroy(F);
-      return api_fail(e == hipErrorOutOfMemory ? SBGPU_ENOMEM : SBGPU_EHIP, std::string("sbgpu_front_stream_begin: ") + hipGetErrorString(e));
+      return sb::api_fail_hip(e, "sbgpu_front_stream_begin");
    }
    *out = F;
    return SBGPU_OK;

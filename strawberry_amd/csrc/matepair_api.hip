@@ -469,7 +469,7 @@ int sbgpu_assign_reads_device(sbgpu_ctx_t *c, const sbgpu_clusters_t *cl, int64_
    const size_t o_ub = t; t += up256(nc1 * 8);
    const size_t o_pos = t; t += up256(nc1 * 8);
    hipError_t e = sb::ctx_scratch(c, 5, t, &w);
-   if (e != hipSuccess) return api_fail(e == hipErrorOutOfMemory ? SBGPU_ENOMEM : SBGPU_EHIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+   if (e != hipSuccess) return sb::api_fail_hip(e, "hipMalloc");
 #define SB_TRY(expr)                                                                                        \
    do {                                                                                                     \
       hipError_t e_ = (expr);                                                                               \
