@@ -951,6 +951,53 @@ int sbgpu_context_table_keep(sbgpu_ctx_t *ctx, int32_t on);
  * (NULL: the context's own).  Loci of more than 4096 isoforms: SBGPU_ESHAPE.                                        */
 int sbgpu_context_table_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins, void *stream, sbgpu_context_table_t *out);
 
+/* ---- the EM bootstrap: how far theta can be trusted -------------------------
+ * The reference prints theta with no statement of its spread.  The bootstrap resamples every locus' fragments over its
+ * bins, solves again, and reports mean and variance of theta over the replicates.
+ *
+ * The resampling rule (csrc/bootstrap_rules.h; the host form and the kernels call the same functions).  A locus has a
+ * global id g, rows with counts n_i >= 0, N = sum n_i and prefix sums P_i = n_0 + ... + n_{i-1}.  Replicate r (0 <= r <
+ * 2^24) under seed s makes N draws d = 0 .. N-1: with q = d >> 1, Philox4x32-10 (Random123 constants) runs on the counter
+ * (q & 0xffffffff, (q >> 32) | (r << 8), g & 0xffffffff, g >> 32) under the key (s & 0xffffffff, s >> 32); an even d
+ * takes u = o0 | o1 << 32 of its four output words, an odd d takes u = o2 | o3 << 32; t = (u * N) >> 64, and the draw lands
+ * on the row i with P_i <= t < P_{i+1}.  The replicate's count of a row is the number of draws that land on it.  So: a
+ * replicate's total is N, a zero row stays zero, and the result depends on (g, r, s) and the locus' counts only -- not on
+ * the batch the locus sits in, its place there, the number of replicates of the call, or how the work is split.
+ * A locus of N >= 2^40: SBGPU_ESHAPE.  A negative count, a replicate number outside [0, 2^24), n_rep < 1: SBGPU_EINVAL.  */
+typedef struct {
+   int32_t n_rep;            /* B >= 1 replicates, numbered rep_first .. rep_first + B - 1 */
+   int32_t rep_first;
+   uint64_t seed;
+   const int64_t *locus_id;  /* HOST [n_loci] global ids, or NULL: the locus' index in the batch */
+} sbgpu_bootstrap_params_t;
+
+/* One replicate's counts, host arrays (csrc/bootstrap_host.cpp; no GPU needed).  row_off: HOST [n_loci + 1].            */
+int sbgpu_bootstrap_counts_host(int64_t n_loci, const int64_t *row_off, const int32_t *count,
+                                const int64_t *locus_id, uint64_t seed, int32_t rep, int32_t *count_out);
+/* n_rep replicates' counts on the device: d_count_out[n_rep][row_off[n_loci]], bit for bit the host form's; d_count is
+ * not written.  row_off: HOST.  Returns once `stream` has finished them.                                               */
+int sbgpu_bootstrap_counts_device(sbgpu_ctx_t *ctx, int64_t n_loci, const int64_t *row_off, const int32_t *d_count,
+                                  const sbgpu_bootstrap_params_t *params, int32_t *d_count_out, void *stream);
+/* Resample -> EM for every replicate -> statistics.  Replicate k is exactly sbgpu_em_run_device on the counts of
+ * replicate rep_first + k and d_F: the same kernels, the same status and iteration contract, failures reported through
+ * sbgpu_synchronize.  d_mean / d_var [n_iso]: Welford's recurrence over the replicates in replicate order,
+ *    m_k = m_{k-1} + (x_k - m_{k-1}) / k,  M2_k = M2_{k-1} + (x_k - m_{k-1}) (x_k - m_k),  var = M2_B / (B - 1)  (0 for B = 1).
+ * Every replicate enters, whatever its status (a DENOM_ZERO replicate carries theta_0, as in the reference; an INIT_EMPTY
+ * locus depends on F alone and has that status in all replicates).  d_status_count [n_loci][4]: replicates per SBGPU_EM_*
+ * status.  d_theta_rep [n_rep][n_iso], d_status_rep / d_iters_rep [n_rep][n_loci]: every replicate's results, each may be
+ * NULL.  Nothing depends on how the call schedules its replicates; d_count, d_F and the plan are left as they were (the
+ * replicates' counts live in the context's pooled scratch, two sets: replicate k + 1 is resampled and solved while the
+ * statistics of replicate k run).  The call waits once, at its start, for `stream` and the counts' totals (a negative
+ * count or a locus of 2^40 fragments is reported by the call itself); the replicates are then queued: asynchronous on
+ * `stream`.  One bootstrap per context at a time (a second call's work queues behind the first's).                     */
+int sbgpu_em_bootstrap_device(sbgpu_ctx_t *ctx, const sbgpu_plan_t *plan, const int32_t *d_count, const double *d_F,
+                              const sbgpu_bootstrap_params_t *params,
+                              double *d_mean, double *d_var,          /* [n_iso] */
+                              int32_t *d_status_count,                /* [n_loci][4] */
+                              double *d_theta_rep,                    /* [n_rep][n_iso] or NULL */
+                              int32_t *d_status_rep, int32_t *d_iters_rep, /* [n_rep][n_loci] or NULL */
+                              void *stream);
+
 /* ---- per-bin sequence statistics ---------------------------------------
  * What the reference's "bias" option (-b genome.fa) adds to the `-f` table and nothing else
  * (src/bias.cpp holds no code): for every exon bin, over the bases of its segments concatenated

@@ -92,6 +92,55 @@ public:
    /* the two bools of the reference, src/estimate.cpp:307-308 */
    bool init_ok(int64_t l) const { return status[(size_t)l] != SBGPU_EM_INIT_EMPTY; }
    bool run_ok(int64_t l) const { return status[(size_t)l] == SBGPU_EM_OK || status[(size_t)l] == SBGPU_EM_MAXITER; }
+
+#ifdef HIP_INCLUDE_HIP_HIP_RUNTIME_API_H
+   /* The EM bootstrap of the batch (sbgpu_em_bootstrap_device): replicates rep_first .. rep_first + n_rep - 1 under `seed`.
+    * The C ABI's bootstrap works on device arrays, and this header allocates nothing on the device by itself: the member
+    * exists for a translation unit that included <hip/hip_runtime_api.h> before this header (and links the HIP runtime).
+    * locus_id: the loci's global ids (size() entries), or empty: their index in the batch.                           */
+   struct Bootstrap {
+      std::vector<double> mean, var;     /* per isoform */
+      std::vector<int32_t> status_count; /* [size()][4]: replicates per SBGPU_EM_* status */
+   };
+   Bootstrap bootstrap(const Context &ctx, int n_rep, uint64_t seed, int rep_first = 0, const std::vector<int64_t> &locus_id = {}) const
+   {
+      const int64_t n = size();
+      const size_t n_iso = (size_t)iso_off.back();
+      if (!locus_id.empty() && (int64_t)locus_id.size() != n) throw std::invalid_argument("EmBatch::bootstrap: one id per locus");
+      Bootstrap out;
+      out.mean.assign(n_iso, 0.0), out.var.assign(n_iso, 0.0), out.status_count.assign((size_t)n * 4, 0);
+      if (n == 0) return out;
+      struct Dev { /* frees on every way out */
+         void *p = nullptr;
+         ~Dev() { if (p) (void)hipFree(p); }
+         void up(const void *src, size_t bytes, const char *what)
+         {
+            if (hipMalloc(&p, bytes ? bytes : 8) != hipSuccess || (bytes && hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) != hipSuccess))
+               throw std::runtime_error(std::string("EmBatch::bootstrap: ") + what);
+         }
+      } d_count, d_F;
+      d_count.up(count.data(), count.size() * sizeof(int32_t), "count");
+      d_F.up(F.data(), F.size() * sizeof(double), "F");
+      Dev d_m, d_v, d_s;
+      d_m.up(out.mean.data(), n_iso * sizeof(double), "mean");
+      d_v.up(out.var.data(), n_iso * sizeof(double), "var");
+      d_s.up(out.status_count.data(), out.status_count.size() * sizeof(int32_t), "status counts");
+      sbgpu_plan_t *plan = nullptr;
+      check(sbgpu_plan_create(ctx.get(), n, row_off.data(), iso_off.data(), f_off.data(), &plan), "sbgpu_plan_create");
+      const sbgpu_bootstrap_params_t par = {n_rep, rep_first, seed, locus_id.empty() ? nullptr : locus_id.data()};
+      int rc = sbgpu_em_bootstrap_device(ctx.get(), plan, (const int32_t *)d_count.p, (const double *)d_F.p, &par, (double *)d_m.p, (double *)d_v.p,
+                                         (int32_t *)d_s.p, nullptr, nullptr, nullptr, nullptr);
+      if (rc == SBGPU_OK) rc = sbgpu_synchronize(ctx.get(), nullptr);
+      const bool copied = rc != SBGPU_OK || (hipMemcpy(out.mean.data(), d_m.p, n_iso * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
+                                             hipMemcpy(out.var.data(), d_v.p, n_iso * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
+                                             hipMemcpy(out.status_count.data(), d_s.p, out.status_count.size() * sizeof(int32_t),
+                                                       hipMemcpyDeviceToHost) == hipSuccess);
+      sbgpu_plan_destroy(plan);
+      check(rc, "sbgpu_em_bootstrap_device");
+      if (!copied) throw std::runtime_error("EmBatch::bootstrap: the results could not be copied back");
+      return out;
+   }
+#endif
 };
 
 /* include/estimate.hpp:230-257 for a single locus (tests; a caller with one locus at hand).

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("SBGPU_LIB") or os.path.join(HERE, "lib", "libsbgpu.so
 
 SBGPU_OK = 0
 SBGPU_EINVAL = -1
+SBGPU_ESHAPE = -5
 SBGPU_EUNSUPPORTED = -6
 SBGPU_ERCCL = -7
 EM_UNSOLVED = -1
@@ -41,6 +42,7 @@ SYMBOLS = [
     "sbgpu_front_stream_destroy", "sbgpu_em_run_device_split",
     "sbgpu_bgzf_index_host", "sbgpu_bgzf_inflate_host", "sbgpu_bgzf_inflate_device", "sbgpu_bam_index_device", "sbgpu_bam_index_device_info", "sbgpu_front_stream_push_bgzf",
     "sbgpu_context_table_host", "sbgpu_context_table_keep", "sbgpu_context_table_device",
+    "sbgpu_bootstrap_counts_host", "sbgpu_bootstrap_counts_device", "sbgpu_em_bootstrap_device",
 ]
 
 
@@ -144,6 +146,10 @@ class sbgpu_hits_t(C.Structure):
 class sbgpu_context_table_t(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("locus_row_off", "locus_hits", "row_bin", "row_hits", "row_prob")] + [("n_rows", C.c_int64)] +
                 [(n, C.c_void_p) for n in ("d_locus_row_off", "d_locus_hits", "d_row_bin", "d_row_hits", "d_row_prob")])
+
+
+class sbgpu_bootstrap_params_t(C.Structure):
+    _fields_ = [("n_rep", C.c_int32), ("rep_first", C.c_int32), ("seed", C.c_uint64), ("locus_id", C.c_void_p)]
 
 
 _lib = None
@@ -304,6 +310,9 @@ def load():
     L.sbgpu_context_table_host.argtypes = [vp, vp, C.c_int32, vp, vp, vp, C.POINTER(sbgpu_context_table_t)]
     L.sbgpu_context_table_keep.argtypes = [vp, C.c_int32]
     L.sbgpu_context_table_device.argtypes = [vp, vp, vp, C.POINTER(sbgpu_context_table_t)]
+    L.sbgpu_bootstrap_counts_host.argtypes = [C.c_int64, vp, vp, vp, C.c_uint64, C.c_int32, vp]
+    L.sbgpu_bootstrap_counts_device.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp]
+    L.sbgpu_em_bootstrap_device.argtypes = [vp, vp, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("sbgpu_device_count", "sbgpu_plan_classes"):

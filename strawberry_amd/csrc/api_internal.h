@@ -259,4 +259,14 @@ struct ContextKeep {
    std::vector<int64_t> locus_hit_off;      // host copy, [n_loci + 1]
 };
 ContextKeep *ctx_context_keep(sbgpu_ctx_t *ctx);
+// What the EM bootstrap (bootstrap_api.hip) reads of a plan: the totals, and the rows' offsets in device memory
+struct PlanShape {
+   int64_t n_loci = 0, n_rows = 0, n_iso = 0;
+   const int64_t *d_row_off = nullptr; // device, [n_loci + 1]
+};
+PlanShape plan_shape(const sbgpu_plan_t *plan);
+// The bootstrap's working set: one block from the pool (sb::dev_take) that stays with the context -- the call is asynchronous, and
+// a block only goes back to the pool behind a device-wide wait -- and grows when a call needs more; valid until the context's
+// next request.  One host thread per context.
+hipError_t ctx_boot_scratch(sbgpu_ctx_t *ctx, size_t bytes, char **out);
 } // namespace sb

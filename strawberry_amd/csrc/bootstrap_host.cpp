@@ -1,0 +1,52 @@
+// strawberry_amd/csrc/bootstrap_host.cpp -- sbgpu_bootstrap_counts_host (include/sbgpu.h): one bootstrap replicate's bin
+// counts on the host.  The one CPU statement of what csrc/bootstrap_device.h computes: every draw is a function of
+// bootstrap_rules.h, which the kernels call too.  No kernels here.
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/sbgpu.h"
+#include "api_internal.h"
+#include "bootstrap_rules.h"
+
+using sb::api_fail;
+
+extern "C" int sbgpu_bootstrap_counts_host(int64_t n_loci, const int64_t *row_off, const int32_t *count, const int64_t *locus_id, uint64_t seed,
+                                           int32_t rep, int32_t *count_out)
+{
+   if (n_loci < 0 || !row_off) return api_fail(SBGPU_EINVAL, "sbgpu_bootstrap_counts_host: null offsets or a negative locus count");
+   if (rep < 0 || rep >= sb::kBootMaxRep) return api_fail(SBGPU_EINVAL, "sbgpu_bootstrap_counts_host: the replicate number must lie in [0, 2^24)");
+   for (int64_t l = 0; l < n_loci; ++l)
+      if (row_off[l + 1] < row_off[l] || row_off[l + 1] - row_off[l] > INT32_MAX)
+         return api_fail(SBGPU_EINVAL, "sbgpu_bootstrap_counts_host: row_off must not decrease (locus " + std::to_string(l) + ")");
+   if (n_loci && row_off[n_loci] > row_off[0] && (!count || !count_out)) return api_fail(SBGPU_EINVAL, "sbgpu_bootstrap_counts_host: null count array");
+   // all of the input is looked at before anything is written
+   for (int64_t l = 0; l < n_loci; ++l) {
+      int64_t N = 0;
+      for (int64_t i = row_off[l]; i < row_off[l + 1]; ++i) {
+         if (count[i] < 0) return api_fail(SBGPU_EINVAL, "sbgpu_bootstrap_counts_host: negative count in row " + std::to_string(i));
+         N += count[i];
+      }
+      if (N >= sb::kBootMaxDraws) return api_fail(SBGPU_ESHAPE, "sbgpu_bootstrap_counts_host: locus " + std::to_string(l) + " holds 2^40 fragments or more");
+   }
+   std::vector<int64_t> incl;
+   for (int64_t l = 0; l < n_loci; ++l) {
+      const int64_t r0 = row_off[l];
+      const int32_t nr = (int32_t)(row_off[l + 1] - r0);
+      incl.resize((size_t)nr);
+      int64_t N = 0;
+      for (int32_t i = 0; i < nr; ++i) {
+         N += count[r0 + i];
+         incl[(size_t)i] = N;
+         count_out[r0 + i] = 0;
+      }
+      const int64_t g = locus_id ? locus_id[l] : l;
+      for (int64_t q = 0; 2 * q < N; ++q) {
+         uint64_t t[2];
+         sb::boot_draw_pair(g, rep, seed, q, N, t);
+         ++count_out[r0 + sb::boot_row_of(incl.data(), nr, t[0])];
+         if (2 * q + 1 < N) ++count_out[r0 + sb::boot_row_of(incl.data(), nr, t[1])];
+      }
+   }
+   return SBGPU_OK;
+}

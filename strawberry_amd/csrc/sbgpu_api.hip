@@ -86,6 +86,8 @@ struct sbgpu_ctx {
    size_t pairs_hint = 0;
    sb::ResidentAnnotation *resident = nullptr; // sbgpu_annotation_pin
    sb::ContextKeep context_keep;               // sbgpu_context_table_keep
+   char *boot_scratch = nullptr;               // sb::ctx_boot_scratch (sb::dev_take'n)
+   size_t boot_scratch_cap = 0;
 };
 
 namespace sb {
@@ -314,6 +316,18 @@ hipError_t ctx_scratch(sbgpu_ctx_t *ctx, int slot, size_t bytes, char **out)
    *out = ctx->scratch[slot];
    return hipSuccess;
 }
+hipError_t ctx_boot_scratch(sbgpu_ctx_t *ctx, size_t bytes, char **out)
+{
+   *out = nullptr;
+   if (ctx->boot_scratch_cap < bytes) {
+      dev_give(ctx->boot_scratch, ctx->boot_scratch_cap); // (waits for the device: an earlier call may still work in it)
+      ctx->boot_scratch = nullptr, ctx->boot_scratch_cap = 0;
+      hipError_t e = dev_take(bytes, &ctx->boot_scratch, &ctx->boot_scratch_cap);
+      if (e != hipSuccess) return e;
+   }
+   *out = ctx->boot_scratch;
+   return hipSuccess;
+}
 bool ctx_take_wide_error(sbgpu_ctx_t *ctx)
 {
    if (!ctx->wide_error || !*ctx->wide_error) return false;
@@ -370,6 +384,16 @@ struct sbgpu_plan {
    mutable unsigned wide_epoch = 0;    // bumped by every run: the tag space of its exchange granules
    int32_t n_wide_desc = 0, n_wide_loci = 0; // the first n_wide_loci of the stream class' list go to the wide kernel
 };
+
+namespace sb {
+PlanShape plan_shape(const sbgpu_plan_t *plan)
+{
+   PlanShape s;
+   s.n_loci = plan->host.n_loci, s.n_rows = plan->host.n_rows, s.n_iso = plan->host.n_iso;
+   s.d_row_off = plan->d_row_off;
+   return s;
+}
+} // namespace sb
 
 namespace {
 
@@ -631,6 +655,7 @@ int sbgpu_finalize(sbgpu_ctx_t *c)
       if (ev) (void)hipEventDestroy(ev);
    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
    sb::ctx_set_resident_annotation(c, nullptr);
+   sb::dev_give(c->boot_scratch, c->boot_scratch_cap);
    delete c;
    return SBGPU_OK;
 }

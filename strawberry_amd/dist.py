@@ -267,13 +267,16 @@ class ShardQuantifier:
     as in a run over many batches.  pipelined=False: one stream, one buffer set (the steps strictly one after the other)."""
 
     def __init__(self, solver, total_mapped_reads, min_isoform_frac=0.01, effective_len_norm=False,
-                 insert_mean=0.0, filter_by_expression=True, comm=None, f32=False, pipelined=True, inputs=None):
+                 insert_mean=0.0, filter_by_expression=True, comm=None, f32=False, pipelined=True, inputs=None, locus_id=None):
         """comm: an AbiComm (the C-ABI collective); None: torch.distributed's default group.
         f32: run the EM's fp32 variant (BASELINE config 5; not a parity path), the epilogue stays fp64.
         inputs: optional list of device input sets [(d_count, d_F), ...] of the solver's plan: step i solves set i % K (the
         sets are read only, so consecutive steps differ without a write the pipeline would have to order); None: the
-        solver's own d_count / d_F every step."""
+        solver's own d_count / d_F every step.
+        locus_id: this shard's loci as indices into the whole sample (what shard_loci dealt to the rank): bootstrap() resamples
+        a locus under its global id, so a sharded run's replicates are the single-process run's."""
         self.s = solver
+        self.locus_id = None if locus_id is None else np.ascontiguousarray(locus_id, np.int64)
         self.comm = comm
         self.f32 = f32
         if inputs is not None and (f32 or not len(inputs)):
@@ -340,6 +343,13 @@ class ShardQuantifier:
             done = torch.cuda.Event()
             done.record(self._epi)
         self._read_done[k] = done
+
+    def bootstrap(self, n_rep, seed, rep_first=0, keep_replicates=False):
+        """The EM bootstrap of this rank's loci (EmBatchSolver.run_bootstrap) under their global ids.  No collective: theta's
+        mean and variance are per isoform, and every rank draws the replicates the whole sample would have drawn."""
+        if self.inputs is not None:
+            self.s.d_count, self.s.d_F = self.inputs[0]
+        return self.s.run_bootstrap(n_rep, seed, rep_first=rep_first, locus_id=self.locus_id, keep_replicates=keep_replicates)
 
     def finish(self):
         """Wait for the step(s) issued so far; raises if a run failed on the device (SbgpuError)."""

@@ -228,6 +228,46 @@ class EmBatchSolver:
                                                self.d_keep.data_ptr(), tot.data_ptr(), self.d_tpm.data_ptr(),
                                                self._stream()), "sbgpu_tpm_device")
 
+    def run_bootstrap(self, n_rep, seed, rep_first=0, locus_id=None, keep_replicates=False):
+        """The EM bootstrap (sbgpu_em_bootstrap_device): replicates rep_first .. rep_first + n_rep - 1 of the batch's counts under
+        `seed` (the rule of csrc/bootstrap_rules.h), the EM on each, mean and variance of theta over them.  locus_id: the loci's
+        global ids (a shard passes its loci's indices in the whole sample; None: their index here).  Asynchronous on torch's
+        current stream; d_count, d_F, d_theta are not touched.
+        -> dict of device tensors: mean, var [n_iso]; status_count [n_loci, 4]; with keep_replicates also theta [n_rep, n_iso],
+        status, iters [n_rep, n_loci]"""
+        torch, n, k, B = self.torch, self.batch.n_loci, self.n_iso, int(n_rep)
+        ids = None if locus_id is None else np.ascontiguousarray(locus_id, np.int64)
+        if ids is not None and ids.shape != (n,):
+            raise ValueError("locus_id must have one entry per locus")
+        par = _lib.sbgpu_bootstrap_params_t(B, int(rep_first), int(seed), None if ids is None or not n else ids.ctypes.data)
+        rows = max(B, 1)
+        out = {"mean": torch.zeros(max(k, 1), dtype=torch.float64, device=self.dev),
+               "var": torch.zeros(max(k, 1), dtype=torch.float64, device=self.dev),
+               "status_count": torch.zeros((max(n, 1), 4), dtype=torch.int32, device=self.dev)}
+        if keep_replicates:
+            out["theta"] = torch.zeros((rows, max(k, 1)), dtype=torch.float64, device=self.dev)
+            out["status"] = torch.full((rows, max(n, 1)), -1, dtype=torch.int32, device=self.dev)
+            out["iters"] = torch.zeros((rows, max(n, 1)), dtype=torch.int32, device=self.dev)
+        ptr = lambda name: out[name].data_ptr() if name in out else None  # noqa: E731
+        _lib.check(self.ctx.L.sbgpu_em_bootstrap_device(
+            self.ctx.h, self.plan.h, self.d_count.data_ptr(), self.d_F.data_ptr(), C.byref(par), out["mean"].data_ptr(),
+            out["var"].data_ptr(), out["status_count"].data_ptr(), ptr("theta"), ptr("status"), ptr("iters"), self._stream()),
+            "sbgpu_em_bootstrap_device")
+        out["mean"], out["var"], out["status_count"] = out["mean"][:k], out["var"][:k], out["status_count"][:n]
+        if keep_replicates:
+            out["theta"], out["status"], out["iters"] = out["theta"][:, :k], out["status"][:, :n], out["iters"][:, :n]
+        return out
+
+    def bootstrap_counts(self, n_rep, seed, rep_first=0, locus_id=None):
+        """The replicates' counts alone (sbgpu_bootstrap_counts_device) -> int32 device tensor [n_rep, total rows]"""
+        n = self.batch.n_loci
+        ids = None if locus_id is None else np.ascontiguousarray(locus_id, np.int64)
+        par = _lib.sbgpu_bootstrap_params_t(int(n_rep), int(rep_first), int(seed), None if ids is None or not n else ids.ctypes.data)
+        out = self.torch.zeros((max(int(n_rep), 1), max(int(self.plan.row_off[-1]), 1)), dtype=self.torch.int32, device=self.dev)
+        _lib.check(self.ctx.L.sbgpu_bootstrap_counts_device(self.ctx.h, n, self.plan.row_off.ctypes.data, self.d_count.data_ptr(), C.byref(par),
+                                                            out.data_ptr(), self._stream()), "sbgpu_bootstrap_counts_device")
+        return out[:, :int(self.plan.row_off[-1])]
+
     def results(self):
         """-> dict of host numpy arrays (synchronises; raises if the last run failed)."""
         self.synchronize()
@@ -262,6 +302,22 @@ def em_batch_host(batch, ctx=None, device=0):
     _lib.check(ctx.L.sbgpu_em_batch(ctx.h, C.byref(b), theta.ctypes.data, status.ctypes.data, iters.ctypes.data),
                "sbgpu_em_batch")
     return theta[:n_iso], status[:n], iters[:n]
+
+
+def bootstrap_counts_host(row_off, count, seed, rep, locus_id=None):
+    """sbgpu_bootstrap_counts_host: one bootstrap replicate's counts on the host (no GPU needed) -> int32[total rows]"""
+    L = _lib.load()
+    row_off = np.ascontiguousarray(row_off, np.int64)
+    count = np.ascontiguousarray(count, np.int32)
+    n = len(row_off) - 1
+    ids = None if locus_id is None else np.ascontiguousarray(locus_id, np.int64)
+    if ids is not None and ids.shape != (n,):
+        raise ValueError("locus_id must have one entry per locus")
+    out = np.zeros(max(len(count), 1), np.int32)
+    _lib.check(L.sbgpu_bootstrap_counts_host(n, row_off.ctypes.data, count.ctypes.data if count.size else None,
+                                             None if ids is None or not n else ids.ctypes.data, int(seed), int(rep), out.ctypes.data),
+               "sbgpu_bootstrap_counts_host")
+    return out[:len(count)]
 
 
 class EmSolver:

@@ -121,6 +121,17 @@ class LocusQuantifier:
         s.run_tpm()
         return s.results()
 
+    def bootstrap(self, n_rep, seed, rep_first=0, locus_id=None, keep_replicates=False):
+        """The EM bootstrap on the bins' counts and the weights the chain holds on the device (after assign_bins and
+        bin_weights): EmBatchSolver.run_bootstrap on solve()'s batch -> its dict of device tensors.  locus_id: the loci's
+        global ids where this annotation is a part of a sample."""
+        if self.bins is None or getattr(self, "d_F", None) is None:
+            raise _lib.SbgpuError("bootstrap: assign_bins() and bin_weights() come first")
+        if self.solver is None or self.solver.d_F is not self.d_F:   # (solve() leaves one; new weights make it stale)
+            b = self.bins
+            self.solver = EmBatchSolver(LocusBatch(b.row_off, b.iso_off, b.f_off, b.count, None, b.iso_len, "hits"), self.ctx, d_F=self.d_F)
+        return self.solver.run_bootstrap(n_rep, seed, rep_first=rep_first, locus_id=locus_id, keep_replicates=keep_replicates)
+
     def run(self, total_mapped_reads, **abundance_kw):
         self.assign_bins()
         self.bin_weights()
