@@ -998,6 +998,70 @@ int sbgpu_em_bootstrap_device(sbgpu_ctx_t *ctx, const sbgpu_plan_t *plan, const 
                               int32_t *d_status_rep, int32_t *d_iters_rep, /* [n_rep][n_loci] or NULL */
                               void *stream);
 
+/* ---- the bootstrap of the resident path: FPKM / TPM mean, spread and intervals -----------------------------
+ * Statistics over the replicates of one column (csrc/bootstrap_rules.h; the host form and boot_interval_kernel call the same
+ * functions).  x[n_rep][n] is replicate-major.  For column j: mean and var are Welford's recurrence in replicate order, as
+ * above; lo[j] / hi[j] are the elements at the 0-based positions rank_lo / rank_hi of the column sorted ascending under <,
+ * NaNs last: pure order statistics, no interpolation, so lo and hi are bits of input elements (ties: -0.0 sorts in front of
+ * +0.0; a NaN comes back with its sign bit cleared), and the ranks are integers, so no rounding decides which replicate is
+ * picked.  SBGPU_EINVAL unless n_rep >= 1 and 0 <= rank_lo <= rank_hi < n_rep.  mean / var / lo / hi: [n], each may be NULL.
+ * Device form: device pointers, asynchronous on `stream`; n_rep <= 1024 (a wave sorts a column in its registers), above:
+ * SBGPU_ESHAPE.  The host form has no cap.                                                                                 */
+int sbgpu_replicate_stats_host(int32_t n_rep, int64_t n, const double *x, int32_t rank_lo, int32_t rank_hi,
+                               double *mean, double *var, double *lo, double *hi);
+int sbgpu_replicate_stats_device(sbgpu_ctx_t *ctx, int32_t n_rep, int64_t n, const double *d_x, int32_t rank_lo, int32_t rank_hi,
+                                 double *d_mean, double *d_var, double *d_lo, double *d_hi, void *stream);
+/* on != 0: the context's LATER sbgpu_quantify_resident / sbgpu_front_stream_end calls leave what
+ * sbgpu_abundance_bootstrap_device needs: the call's EM plan (the context owns it from then on: destroyed by its next
+ * sbgpu_quantify_* call and by sbgpu_finalize) and device pointers the call had anyway -- the bins' counts, the bin weights,
+ * the isoforms' lengths -- with the epilogue's parameters as the call filled them in.  Nothing is copied, and theta, FPKM,
+ * Frac, TPM, keep, status and iters are the same bits.  Off (the default): those calls are unchanged.  May be on together
+ * with sbgpu_context_table_keep.                                                                                            */
+int sbgpu_bootstrap_keep(sbgpu_ctx_t *ctx, int32_t on);
+/* Right after such a call, on the handle it returned (which must still live), before the context's next call that works in
+ * its scratch memory (as for sbgpu_context_table_device): SBGPU_EINVAL otherwise -- a handle made without retention, or a
+ * stale one; sbgpu_last_error says which.  The call itself works in the context's bootstrap scratch and pooled blocks only:
+ * sbgpu_context_table_device stays valid before and after it, and it may be repeated.
+ * For replicate k (number rep_first + k; seed, locus_id and the double buffering as sbgpu_em_bootstrap_device): resample,
+ * the EM, step k of theta's statistics and the status counts, then the reference's epilogue (abundance_kernel, the call's
+ * retained parameters) on this replicate's theta and status: FPKM into row k of d_fpkm_rep, keep into row k of d_keep_rep
+ * (one int32 per isoform, 0 / 1 / 2 as sbgpu_abundances_t's keep: not packed), this rank's kept-FPKM sum into entry k of the
+ * totals.  total_mapped_reads and the insert law are the SAMPLE's and are not resampled.  After the last replicate: ONE
+ * all-reduce(sum) of the n_rep totals over `comm` (NULL: a world of one; otherwise every rank of the communicator makes this
+ * call with the same n_rep; argument checks and every allocation happen before the first kernel, so a rank that is going to
+ * fail fails before its peers wait), then the statistics above over the columns of d_fpkm_rep, twice:
+ *    fpkm_*  on x_k = fpkm_rep[k][j], whatever keep says;
+ *    tpm_*   on x_k = keep_rep[k][j] ? 1e6 * fpkm_rep[k][j] / total[k] : 0.0 (tpm_kernel's expression; no TPM matrix is written),
+ *            and keep_count[j] = the number of k with keep_rep[k][j] != 0.
+ * theta_mean / theta_var / status_count are sbgpu_em_bootstrap_device's d_mean / d_var / d_status_count.
+ * The struct: host arrays to fill (any may be NULL) and, on return, the device arrays of all of them and the replicates' own:
+ * one pooled block of the context's, valid until its next sbgpu_abundance_bootstrap_device or sbgpu_quantify_* call.  The
+ * replicates' matrices take n_rep * n_iso * (8 + 4) bytes (+ n_rep * n_iso * 8 with keep_theta_rep): SBGPU_ENOMEM when they do
+ * not fit.  SBGPU_EINVAL: n_rep < 1, ranks outside 0 <= rank_lo <= rank_hi < n_rep, a NULL `out`.  SBGPU_ESHAPE: n_rep > 1024.
+ * Returns synchronised on `stream` (NULL: the context's own).  Nothing depends on how the replicates are scheduled.        */
+typedef struct {
+   double *theta_mean, *theta_var, *fpkm_mean, *fpkm_var, *fpkm_lo, *fpkm_hi,
+          *tpm_mean, *tpm_var, *tpm_lo, *tpm_hi;        /* in: host [n_iso], or NULL                                  */
+   int32_t *keep_count;                                 /* in: host [n_iso], or NULL: replicates with keep != 0       */
+   int32_t *status_count;                               /* in: host [n_loci][4], or NULL                              */
+   double *total_fpkm_rep;                              /* in: host [n_rep], or NULL: the total TPM divided by, all ranks */
+   double *fpkm_rep;                                    /* in: host [n_rep][n_iso], or NULL: every replicate's FPKM       */
+   int32_t *keep_rep;                                   /* in: host [n_rep][n_iso], or NULL: every replicate's keep       */
+   double *theta_rep;                                   /* in: host [n_rep][n_iso], or NULL (filled with keep_theta_rep)  */
+   const double *d_theta_mean, *d_theta_var, *d_fpkm_mean, *d_fpkm_var, *d_fpkm_lo, *d_fpkm_hi,
+                *d_tpm_mean, *d_tpm_var, *d_tpm_lo, *d_tpm_hi; /* out: device [n_iso]                                 */
+   const int32_t *d_keep_count, *d_status_count;        /* out: device [n_iso], [n_loci][4]                           */
+   const double *d_total_fpkm_rep;                      /* out: device [n_rep]                                        */
+   const double *d_fpkm_rep;                            /* out: device [n_rep][n_iso]                                 */
+   const int32_t *d_keep_rep;                           /* out: device [n_rep][n_iso]                                 */
+   const double *d_theta_rep;                           /* out: device [n_rep][n_iso], or NULL unless keep_theta_rep  */
+   int64_t n_iso, n_loci;                               /* out */
+   int32_t n_rep, reserved;                             /* out */
+} sbgpu_abundance_bootstrap_t;
+int sbgpu_abundance_bootstrap_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins, const sbgpu_bootstrap_params_t *params,
+                                     int32_t rank_lo, int32_t rank_hi, int32_t keep_theta_rep, sbgpu_comm_t *comm, void *stream,
+                                     sbgpu_abundance_bootstrap_t *out);
+
 /* ---- per-bin sequence statistics ---------------------------------------
  * What the reference's "bias" option (-b genome.fa) adds to the `-f` table and nothing else
  * (src/bias.cpp holds no code): for every exon bin, over the bases of its segments concatenated

@@ -635,5 +635,58 @@ class ContextTable {
    }
 };
 
+/* The bootstrap of the resident path (sbgpu_bootstrap_keep / sbgpu_abundance_bootstrap_device, include/sbgpu.h): FPKM and TPM
+ * mean, variance and percentile interval over resampled bin counts, with the replicates in which the expression filter kept
+ * each isoform.  keep(): before the resident call; device(): right after it, on that call's handle.  interval_ranks(): the two
+ * integer positions of the central `level` interval, level given as a fraction num / den so that no rounding picks the rank.   */
+class AbundanceBootstrap {
+ public:
+   std::vector<double> theta_mean, theta_var, fpkm_mean, fpkm_var, fpkm_lo, fpkm_hi, tpm_mean, tpm_var, tpm_lo, tpm_hi; /* [n_iso] */
+   std::vector<int32_t> keep_count;    /* [n_iso] */
+   std::vector<int32_t> status_count;  /* [n_loci][4] */
+   std::vector<double> total_fpkm_rep; /* [n_rep] */
+   std::vector<double> fpkm_rep;       /* [n_rep][n_iso], with keep_replicates */
+   std::vector<int32_t> keep_rep;      /* [n_rep][n_iso], with keep_replicates */
+   int32_t rank_lo = 0, rank_hi = 0;
+   sbgpu_abundance_bootstrap_t raw{};  /* the device arrays: the context's, valid until its next bootstrap or quantify call */
+
+   static void keep(const Context &ctx, bool on) { check(sbgpu_bootstrap_keep(ctx.get(), on ? 1 : 0), "sbgpu_bootstrap_keep"); }
+   static void interval_ranks(int32_t n_rep, int64_t level_num, int64_t level_den, int32_t *lo, int32_t *hi)
+   {
+      int64_t l = (int64_t)n_rep * (level_den - level_num) / (2 * level_den); /* floor(n_rep (1 - level) / 2) */
+      if (l > (n_rep - 1) / 2) l = (n_rep - 1) / 2;
+      *lo = (int32_t)l, *hi = n_rep - 1 - (int32_t)l;
+   }
+   static AbundanceBootstrap device(const Context &ctx, const sbgpu_bins_t *bins, int32_t n_rep, uint64_t seed, int32_t rank_lo, int32_t rank_hi,
+                                    int32_t rep_first = 0, const int64_t *locus_id = nullptr, bool keep_theta_rep = false,
+                                    sbgpu_comm_t *comm = nullptr, void *stream = nullptr, bool keep_replicates = false)
+   {
+      AbundanceBootstrap b;
+      int64_t info[8];
+      check(sbgpu_bins_info(bins, info), "sbgpu_bins_info");
+      const size_t ni = (size_t)info[1] + 1, nl = (size_t)info[0] + 1;
+      sbgpu_abundance_bootstrap_t &o = b.raw;
+      std::vector<double> *stat[10] = {&b.theta_mean, &b.theta_var, &b.fpkm_mean, &b.fpkm_var, &b.fpkm_lo, &b.fpkm_hi, &b.tpm_mean, &b.tpm_var, &b.tpm_lo, &b.tpm_hi};
+      double **slot[10] = {&o.theta_mean, &o.theta_var, &o.fpkm_mean, &o.fpkm_var, &o.fpkm_lo, &o.fpkm_hi, &o.tpm_mean, &o.tpm_var, &o.tpm_lo, &o.tpm_hi};
+      for (int i = 0; i < 10; ++i) {
+         stat[i]->assign(ni, 0.0);
+         *slot[i] = stat[i]->data();
+      }
+      b.keep_count.assign(ni, 0), b.status_count.assign(nl * 4, 0), b.total_fpkm_rep.assign((size_t)(n_rep > 0 ? n_rep : 1), 0.0);
+      o.keep_count = b.keep_count.data(), o.status_count = b.status_count.data(), o.total_fpkm_rep = b.total_fpkm_rep.data();
+      if (keep_replicates && n_rep > 0 && info[1] > 0) {
+         b.fpkm_rep.assign((size_t)n_rep * (size_t)info[1], 0.0), b.keep_rep.assign((size_t)n_rep * (size_t)info[1], 0);
+         o.fpkm_rep = b.fpkm_rep.data(), o.keep_rep = b.keep_rep.data();
+      }
+      const sbgpu_bootstrap_params_t par = {n_rep, rep_first, seed, locus_id};
+      check(sbgpu_abundance_bootstrap_device(ctx.get(), bins, &par, rank_lo, rank_hi, keep_theta_rep ? 1 : 0, comm, stream, &o),
+            "sbgpu_abundance_bootstrap_device");
+      for (int i = 0; i < 10; ++i) stat[i]->resize(ni - 1);
+      b.keep_count.resize(ni - 1), b.status_count.resize((nl - 1) * 4);
+      b.rank_lo = rank_lo, b.rank_hi = rank_hi;
+      return b;
+   }
+};
+
 } // namespace sbgpu
 #endif /* SBGPU_HOST_HPP_ */

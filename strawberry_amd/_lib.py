@@ -43,6 +43,7 @@ SYMBOLS = [
     "sbgpu_bgzf_index_host", "sbgpu_bgzf_inflate_host", "sbgpu_bgzf_inflate_device", "sbgpu_bam_index_device", "sbgpu_bam_index_device_info", "sbgpu_front_stream_push_bgzf",
     "sbgpu_context_table_host", "sbgpu_context_table_keep", "sbgpu_context_table_device",
     "sbgpu_bootstrap_counts_host", "sbgpu_bootstrap_counts_device", "sbgpu_em_bootstrap_device",
+    "sbgpu_replicate_stats_host", "sbgpu_replicate_stats_device", "sbgpu_bootstrap_keep", "sbgpu_abundance_bootstrap_device",
 ]
 
 
@@ -150,6 +151,15 @@ class sbgpu_context_table_t(C.Structure):
 
 class sbgpu_bootstrap_params_t(C.Structure):
     _fields_ = [("n_rep", C.c_int32), ("rep_first", C.c_int32), ("seed", C.c_uint64), ("locus_id", C.c_void_p)]
+
+
+class sbgpu_abundance_bootstrap_t(C.Structure):
+    _fields_ = ([(n, C.c_void_p) for n in ("theta_mean", "theta_var", "fpkm_mean", "fpkm_var", "fpkm_lo", "fpkm_hi", "tpm_mean", "tpm_var",
+                                           "tpm_lo", "tpm_hi", "keep_count", "status_count", "total_fpkm_rep", "fpkm_rep", "keep_rep", "theta_rep",
+                                           "d_theta_mean", "d_theta_var", "d_fpkm_mean", "d_fpkm_var", "d_fpkm_lo", "d_fpkm_hi", "d_tpm_mean",
+                                           "d_tpm_var", "d_tpm_lo", "d_tpm_hi", "d_keep_count", "d_status_count", "d_total_fpkm_rep",
+                                           "d_fpkm_rep", "d_keep_rep", "d_theta_rep")] +
+                [("n_iso", C.c_int64), ("n_loci", C.c_int64), ("n_rep", C.c_int32), ("reserved", C.c_int32)])
 
 
 _lib = None
@@ -313,6 +323,11 @@ def load():
     L.sbgpu_bootstrap_counts_host.argtypes = [C.c_int64, vp, vp, vp, C.c_uint64, C.c_int32, vp]
     L.sbgpu_bootstrap_counts_device.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp]
     L.sbgpu_em_bootstrap_device.argtypes = [vp, vp, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp, vp, vp, vp, vp, vp]
+    L.sbgpu_replicate_stats_host.argtypes = [C.c_int32, C.c_int64, vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
+    L.sbgpu_replicate_stats_device.argtypes = [vp, C.c_int32, C.c_int64, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
+    L.sbgpu_bootstrap_keep.argtypes = [vp, C.c_int32]
+    L.sbgpu_abundance_bootstrap_device.argtypes = [vp, vp, C.POINTER(sbgpu_bootstrap_params_t), C.c_int32, C.c_int32, C.c_int32, vp, vp,
+                                                   C.POINTER(sbgpu_abundance_bootstrap_t)]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("sbgpu_device_count", "sbgpu_plan_classes"):

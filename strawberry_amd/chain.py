@@ -222,14 +222,16 @@ class ChainQuantifier:
     then FPKM / TPM on the host arrays the call returns (the caller's own epilogue, as in the reference)."""
 
     def __init__(self, ctx, n_loci=60000, n_frags=2e8, seed=31, read_len=75, loci_subset=None, pin=True, resident=False,
-                 empirical=False, comm=None, min_isoform_frac=0.0, keep_context=False):
+                 empirical=False, comm=None, min_isoform_frac=0.0, keep_context=False, keep_bootstrap=False):
         """resident=True: step() is sbgpu_quantify_resident -- the chain with the reference's pass 1 in front (empirical=True: no
         insert-size law is given, the device builds it from the hits; Strawberry's default mode) and the FPKM / Frac / TPM
         epilogue behind it, the collectives over `comm` (dist.AbiComm / dist.HostComm; None: a world of one) inside the call;
         theta, FPKM, Frac, keep and TPM land in the object's host arrays, `law` holds the insert-size law that was used.
         keep_context=True (resident only): every step asks the context to keep what the `-f` table needs (sbgpu_context_table_keep,
         switched on for the step's own call only: the context may be shared) and the last step's handle lives on in
-        `context_handle`; context_table() builds the table from it on the device."""
+        `context_handle`; context_table() builds the table from it on the device.
+        keep_bootstrap=True (resident only): likewise for the bootstrap (sbgpu_bootstrap_keep); abundance_bootstrap() runs it on the
+        last step's handle."""
         import torch
         self.torch, self.ctx = torch, ctx
         self.dev = torch.device("cuda", ctx.device)
@@ -249,9 +251,10 @@ class ChainQuantifier:
         self.info = None
         self.resident, self.empirical, self.comm = bool(resident), bool(empirical), comm
         self.keep_context, self.context_handle = bool(keep_context), None
-        if keep_context:
+        self.keep_bootstrap = bool(keep_bootstrap)
+        if keep_context or keep_bootstrap:
             if not resident:
-                raise ValueError("keep_context needs resident=True: only the resident entry keeps the table's inputs")
+                raise ValueError("keep_context / keep_bootstrap need resident=True: only the resident entry keeps their inputs")
         if resident:
             self.fpkm, self.frac, self.tpm = np.zeros(self.n_iso + 1), np.zeros(self.n_iso + 1), np.zeros(self.n_iso + 1)
             self.keep = np.zeros(self.n_iso + 1, np.int32)
@@ -290,12 +293,13 @@ class ChainQuantifier:
         self._retire(h)
 
     def _retire(self, h):
-        """The step's handle: destroyed, or -- keep_context -- kept for context_table() until the next step's replaces it."""
+        """The step's handle: destroyed, or -- keep_context / keep_bootstrap -- kept for context_table() / abundance_bootstrap()
+        until the next step's replaces it."""
         L = self.ctx.L
         if self.context_handle is not None:
             L.sbgpu_bins_destroy(self.context_handle)
             self.context_handle = None
-        if self.keep_context:
+        if self.keep_context or self.keep_bootstrap:
             self.context_handle = h
         else:
             L.sbgpu_bins_destroy(h)
@@ -304,14 +308,21 @@ class ChainQuantifier:
     def _retention(self):
         """keep_context: retention on around this object's own resident call, off behind it (what the call kept stays until the
         context's next quantify call) -- another quantifier on the same context neither gains nor loses it."""
-        if not self.keep_context:
+        if not self.keep_context and not self.keep_bootstrap:
             yield
             return
-        _lib.check(self.ctx.L.sbgpu_context_table_keep(self.ctx.h, 1), "sbgpu_context_table_keep")
+        L = self.ctx.L
+        if self.keep_context:
+            _lib.check(L.sbgpu_context_table_keep(self.ctx.h, 1), "sbgpu_context_table_keep")
+        if self.keep_bootstrap:
+            _lib.check(L.sbgpu_bootstrap_keep(self.ctx.h, 1), "sbgpu_bootstrap_keep")
         try:
             yield
         finally:
-            self.ctx.L.sbgpu_context_table_keep(self.ctx.h, 0)
+            if self.keep_context:
+                L.sbgpu_context_table_keep(self.ctx.h, 0)
+            if self.keep_bootstrap:
+                L.sbgpu_bootstrap_keep(self.ctx.h, 0)
 
     def context_table(self):
         """The `-f` table of the last step as arrays (context.ContextTable), built on the device."""
@@ -319,6 +330,15 @@ class ChainQuantifier:
         if self.context_handle is None:
             raise _lib.SbgpuError("context_table: no step has run with keep_context=True")
         return context.context_table_device(self.ctx, self.context_handle)
+
+    def abundance_bootstrap(self, n_rep, seed, **kw):
+        """The bootstrap of the last step (keep_bootstrap=True): bootstrap.abundance_bootstrap_device on its handle, over this
+        object's communicator -> its dict (FPKM / TPM mean, variance, interval; keep and status counts)."""
+        from . import bootstrap
+        if self.context_handle is None or not self.keep_bootstrap:
+            raise _lib.SbgpuError("abundance_bootstrap: no step has run with keep_bootstrap=True")
+        kw.setdefault("comm", self.comm)
+        return bootstrap.abundance_bootstrap_device(self.ctx, self.context_handle, n_rep, seed, **kw)
 
     def set_law(self, insert):
         """Quantify under a GIVEN insert-size law from now on (an InsertSize: -i mean/sd, or an empirical law made elsewhere)."""

@@ -79,6 +79,7 @@ def context_table_keep(ctx, on=True):
 def context_table_device(ctx, handle, stream=None):
     """Right after a resident call made with retention on, on its handle, before the context's next quantify call."""
     L = ctx.L
+    handle = getattr(handle, "h", handle)      # (a quantify.BinsHandle, or the raw handle)
     n_loci, n_bins, n_elem = _sizes(L, handle)
     t = ContextTable(n_loci, n_bins, n_elem)
     s = t._struct()

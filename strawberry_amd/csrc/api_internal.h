@@ -242,9 +242,11 @@ struct BinsContextView {
    const double *F = nullptr;       // host, [n_elem]: the weights of a handle from sbgpu_quantify_host, else null
    const uint32_t *d_key = nullptr; // device, [n_bins * key_words]: the bin keys of a device grouping, else null
    uint64_t context_serial = 0;     // the resident call that kept the table's inputs for this handle (0: none did)
+   uint64_t boot_serial = 0;        // the resident call that kept the bootstrap's inputs for this handle (0: none did)
 };
 BinsContextView bins_context_view(const sbgpu_bins_t *bins);
 void bins_set_context_serial(sbgpu_bins_t *bins, uint64_t serial);
+void bins_set_boot_serial(sbgpu_bins_t *bins, uint64_t serial);
 // What a resident call leaves for sbgpu_context_table_device when the context was asked to (sbgpu_context_table_keep): device
 // pointers into the context's scratch, valid until the context's next sbgpu_quantify_* call (which clears the record).
 struct ContextKeep {
@@ -269,4 +271,25 @@ PlanShape plan_shape(const sbgpu_plan_t *plan);
 // a block only goes back to the pool behind a device-wide wait -- and grows when a call needs more; valid until the context's
 // next request.  One host thread per context.
 hipError_t ctx_boot_scratch(sbgpu_ctx_t *ctx, size_t bytes, char **out);
+// What a resident call leaves for sbgpu_abundance_bootstrap_device when the context was asked to (sbgpu_bootstrap_keep): the
+// call's EM plan, which the context owns from then on, and device pointers the call had anyway -- into the context's scratch,
+// the handle's arena or the pinned annotation; nothing is copied.  Valid until the context's next call that works in the
+// chain's scratch (ctx_scratch ends the record, as it ends ContextKeep's); the plan is destroyed by the context's next
+// sbgpu_quantify_* call and by sbgpu_finalize (ctx_boot_release).
+struct BootKeep {
+   bool on = false;      // later resident calls retain
+   uint64_t serial = 0;  // the retaining call's number, shared with its handle; 0: nothing is retained
+   sbgpu_plan_t *plan = nullptr;
+   int64_t n_loci = 0, n_iso = 0;
+   const int32_t *d_count = nullptr;   // [n_bins] the bins' fragment counts
+   const double *d_F = nullptr;        // [n_elem] the raw bin weights
+   const int32_t *d_iso_len = nullptr; // [n_iso] the isoforms' exonic lengths
+   sbgpu_abundance_params_t params{};  // as the call's epilogue used them (total_mapped_reads and insert_mean filled in)
+};
+BootKeep *ctx_boot_keep(sbgpu_ctx_t *ctx);
+// the record's plan and the bootstrap's result block go back (both wait for the device); the record ends
+void ctx_boot_release(sbgpu_ctx_t *ctx);
+// The results of sbgpu_abundance_bootstrap_device: one block from the pool that stays with the context until its next
+// bootstrap or sbgpu_quantify_* call
+hipError_t ctx_boot_result(sbgpu_ctx_t *ctx, size_t bytes, char **out);
 } // namespace sb

@@ -1,10 +1,12 @@
-// strawberry_amd/csrc/bootstrap_api.hip -- sbgpu_bootstrap_counts_device / sbgpu_em_bootstrap_device (include/sbgpu.h):
-// the EM bootstrap on the device (bootstrap_device.h; DESIGN 3.17).  Replicates' counts by the rule of bootstrap_rules.h, the
+// strawberry_amd/csrc/bootstrap_api.hip -- sbgpu_bootstrap_counts_device / sbgpu_em_bootstrap_device, and the bootstrap of the
+// resident path: sbgpu_bootstrap_keep / sbgpu_abundance_bootstrap_device / sbgpu_replicate_stats_device (include/sbgpu.h):
+// the EM bootstrap on the device (bootstrap_device.h; DESIGN 3.17, 3.18).  Replicates' counts by the rule of bootstrap_rules.h, the
 // existing EM entry replicate after replicate, Welford's recurrence over the replicates' theta.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
+#include <functional>
 #include <string>
 
 #include "../../include/sbgpu.h"
@@ -115,55 +117,22 @@ int check_params(const char *who, const sbgpu_bootstrap_params_t *p)
    return SBGPU_OK;
 }
 
-} // namespace
+// What follows the statistics step of a replicate on the join stream: replicate k's theta and status are in the set it is handed;
+// the set is free again once what the hook queues on `js` is through.
+using AfterStats = std::function<int(int32_t k, const double *d_theta, const int32_t *d_status, hipStream_t js)>;
 
-extern "C" {
-
-int sbgpu_bootstrap_counts_device(sbgpu_ctx_t *c, int64_t n_loci, const int64_t *row_off, const int32_t *d_count, const sbgpu_bootstrap_params_t *params,
-                                  int32_t *d_count_out, void *stream)
+// The replicates of a call, shared by sbgpu_em_bootstrap_device and sbgpu_abundance_bootstrap_device: prefix sums once (the
+// call's one wait), then per replicate a resample, the EM through the split entry, and on the join stream one step of the
+// statistics and `after` (may be empty).  Two sets of counts and results in the context's bootstrap scratch, allocated before
+// the first kernel.  On return `s` continues behind the last replicate's join-stream work.
+int run_replicates(sbgpu_ctx_t *c, const char *who, const sbgpu_plan_t *plan, const int32_t *d_count, const double *d_F,
+                   const sbgpu_bootstrap_params_t *params, double *d_mean, double *d_var, int32_t *d_status_count, double *d_theta_rep,
+                   int32_t *d_status_rep, int32_t *d_iters_rep, hipStream_t s, const AfterStats &after)
 {
-   const char *who = "sbgpu_bootstrap_counts_device";
-   if (const int rc = check_params(who, params); rc != SBGPU_OK) return rc;
-   if (!c || n_loci < 0 || !row_off) return api_fail(SBGPU_EINVAL, std::string(who) + ": null context or offsets, or a negative locus count");
-   for (int64_t l = 0; l < n_loci; ++l)
-      if (row_off[l + 1] < row_off[l] || row_off[l + 1] - row_off[l] > INT32_MAX)
-         return api_fail(SBGPU_EINVAL, std::string(who) + ": row_off must not decrease (locus " + std::to_string(l) + ")");
-   if (n_loci == 0) return SBGPU_OK;
-   if (row_off[0] != 0) return api_fail(SBGPU_EINVAL, std::string(who) + ": row_off[0] must be 0");
-   const int64_t n_rows = row_off[n_loci];
-   if (n_rows && (!d_count || !d_count_out)) return api_fail(SBGPU_EINVAL, std::string(who) + ": null count array");
-   hipStream_t s = (hipStream_t)stream;
-   hipError_t e = hipSetDevice(sb::ctx_device(c));
-   if (e != hipSuccess) return api_fail_hip(e, "hipSetDevice");
-   char *mem = nullptr;
-   if ((e = sb::ctx_boot_scratch(c, BootPrep::bytes(n_loci, n_rows, params->locus_id != nullptr, true), &mem)) != hipSuccess)
-      return api_fail_hip(e, "hipMalloc(bootstrap scratch)");
-   BootPrep w;
-   w.lay(mem, n_loci, n_rows, params->locus_id != nullptr, true);
-   if ((e = hipMemcpyAsync(w.row_off, row_off, (size_t)(n_loci + 1) * 8, hipMemcpyHostToDevice, s)) != hipSuccess) {
-      (void)hipStreamSynchronize(s);
-      return api_fail_hip(e, "hipMemcpyAsync(row_off)");
-   }
-   if (const int rc = prepare(c, who, w, n_loci, w.row_off, d_count, params->locus_id, s); rc != SBGPU_OK) return rc;
-   if (const int rc = resample(w, n_loci, n_rows, w.row_off, params->seed, params->rep_first, params->n_rep, d_count_out, s); rc != SBGPU_OK) return rc;
-   // the scratch is the context's: the next call on it may start at once
-   if ((e = hipStreamSynchronize(s)) != hipSuccess) return api_fail_hip(e, "hipStreamSynchronize");
-   return SBGPU_OK;
-}
-
-int sbgpu_em_bootstrap_device(sbgpu_ctx_t *c, const sbgpu_plan_t *plan, const int32_t *d_count, const double *d_F, const sbgpu_bootstrap_params_t *params,
-                              double *d_mean, double *d_var, int32_t *d_status_count, double *d_theta_rep, int32_t *d_status_rep, int32_t *d_iters_rep,
-                              void *stream)
-{
-   const char *who = "sbgpu_em_bootstrap_device";
-   if (const int rc = check_params(who, params); rc != SBGPU_OK) return rc;
-   if (!c || !plan) return api_fail(SBGPU_EINVAL, std::string(who) + ": null ctx/plan");
    const sb::PlanShape ps = sb::plan_shape(plan);
    const int64_t nl = ps.n_loci, n_rows = ps.n_rows, n_iso = ps.n_iso;
-   if (nl == 0) return SBGPU_OK;
-   if (!d_mean || !d_var || !d_status_count || (!d_count && n_rows) || !d_F) return api_fail(SBGPU_EINVAL, std::string(who) + ": null device pointer");
    const int32_t B = params->n_rep;
-   hipStream_t s = (hipStream_t)stream, js = nullptr;
+   hipStream_t js = nullptr;
    hipEvent_t ev[3];
 #define SB_TRY(expr)                                    \
    do {                                                 \
@@ -218,6 +187,13 @@ int sbgpu_em_bootstrap_device(sbgpu_ctx_t *c, const sbgpu_plan_t *plan, const in
       a.iters_rep = d_iters_rep ? d_iters_rep + (size_t)k * (size_t)nl : nullptr;
       hipLaunchKernelGGL(sb::boot_stats_kernel, dim3((unsigned)((n_threads + 255) / 256)), dim3(256), 0, js, a);
       SB_TRY(hipGetLastError());
+      if (after) {
+         if (const int rc = after(k, theta[b], status[b], js); rc != SBGPU_OK) {
+            (void)hipStreamSynchronize(s);
+            (void)hipStreamSynchronize(js);
+            return rc;
+         }
+      }
       SB_TRY(hipEventRecord(ev[b], js));
    }
    // the caller's stream continues behind the last replicate's statistics
@@ -225,6 +201,210 @@ int sbgpu_em_bootstrap_device(sbgpu_ctx_t *c, const sbgpu_plan_t *plan, const in
    SB_TRY(hipStreamWaitEvent(s, ev[2], 0));
    return SBGPU_OK;
 #undef SB_TRY
+}
+
+// boot_interval_kernel over the columns of x[n_rep][n] on `s` (the arguments are checked by the callers)
+int launch_interval(const sb::BootIntervalArgs &a, hipStream_t s)
+{
+   if (a.n == 0) return SBGPU_OK;
+   const unsigned grid = (unsigned)((a.n + sb::kBootTile - 1) / sb::kBootTile);
+   const size_t lds = (size_t)sb::kBootTile * (size_t)a.n_rep * sizeof(double);
+   const dim3 block(sb::kBootIntervalThreads);
+   if (a.n_rep <= 64) hipLaunchKernelGGL(sb::boot_interval_kernel<1>, dim3(grid), block, lds, s, a);
+   else if (a.n_rep <= 128) hipLaunchKernelGGL(sb::boot_interval_kernel<2>, dim3(grid), block, lds, s, a);
+   else if (a.n_rep <= 256) hipLaunchKernelGGL(sb::boot_interval_kernel<4>, dim3(grid), block, lds, s, a);
+   else if (a.n_rep <= 512) hipLaunchKernelGGL(sb::boot_interval_kernel<8>, dim3(grid), block, lds, s, a);
+   else hipLaunchKernelGGL(sb::boot_interval_kernel<16>, dim3(grid), block, lds, s, a);
+   if (hipError_t e = hipGetLastError(); e != hipSuccess) return api_fail_hip(e, "boot_interval_kernel");
+   return SBGPU_OK;
+}
+
+int check_ranks(const char *who, int32_t n_rep, int32_t rank_lo, int32_t rank_hi)
+{
+   if (rank_lo < 0 || rank_lo > rank_hi || rank_hi >= n_rep)
+      return api_fail(SBGPU_EINVAL, std::string(who) + ": the ranks must satisfy 0 <= rank_lo <= rank_hi < n_rep");
+   if (n_rep > sb::kBootMaxStatRep)
+      return api_fail(SBGPU_ESHAPE, std::string(who) + ": more than " + std::to_string(sb::kBootMaxStatRep) + " replicates (the order statistics sort a column in one wave's registers)");
+   return SBGPU_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int sbgpu_bootstrap_counts_device(sbgpu_ctx_t *c, int64_t n_loci, const int64_t *row_off, const int32_t *d_count, const sbgpu_bootstrap_params_t *params,
+                                  int32_t *d_count_out, void *stream)
+{
+   const char *who = "sbgpu_bootstrap_counts_device";
+   if (const int rc = check_params(who, params); rc != SBGPU_OK) return rc;
+   if (!c || n_loci < 0 || !row_off) return api_fail(SBGPU_EINVAL, std::string(who) + ": null context or offsets, or a negative locus count");
+   for (int64_t l = 0; l < n_loci; ++l)
+      if (row_off[l + 1] < row_off[l] || row_off[l + 1] - row_off[l] > INT32_MAX)
+         return api_fail(SBGPU_EINVAL, std::string(who) + ": row_off must not decrease (locus " + std::to_string(l) + ")");
+   if (n_loci == 0) return SBGPU_OK;
+   if (row_off[0] != 0) return api_fail(SBGPU_EINVAL, std::string(who) + ": row_off[0] must be 0");
+   const int64_t n_rows = row_off[n_loci];
+   if (n_rows && (!d_count || !d_count_out)) return api_fail(SBGPU_EINVAL, std::string(who) + ": null count array");
+   hipStream_t s = (hipStream_t)stream;
+   hipError_t e = hipSetDevice(sb::ctx_device(c));
+   if (e != hipSuccess) return api_fail_hip(e, "hipSetDevice");
+   char *mem = nullptr;
+   if ((e = sb::ctx_boot_scratch(c, BootPrep::bytes(n_loci, n_rows, params->locus_id != nullptr, true), &mem)) != hipSuccess)
+      return api_fail_hip(e, "hipMalloc(bootstrap scratch)");
+   BootPrep w;
+   w.lay(mem, n_loci, n_rows, params->locus_id != nullptr, true);
+   if ((e = hipMemcpyAsync(w.row_off, row_off, (size_t)(n_loci + 1) * 8, hipMemcpyHostToDevice, s)) != hipSuccess) {
+      (void)hipStreamSynchronize(s);
+      return api_fail_hip(e, "hipMemcpyAsync(row_off)");
+   }
+   if (const int rc = prepare(c, who, w, n_loci, w.row_off, d_count, params->locus_id, s); rc != SBGPU_OK) return rc;
+   if (const int rc = resample(w, n_loci, n_rows, w.row_off, params->seed, params->rep_first, params->n_rep, d_count_out, s); rc != SBGPU_OK) return rc;
+   // the scratch is the context's: the next call on it may start at once
+   if ((e = hipStreamSynchronize(s)) != hipSuccess) return api_fail_hip(e, "hipStreamSynchronize");
+   return SBGPU_OK;
+}
+
+int sbgpu_em_bootstrap_device(sbgpu_ctx_t *c, const sbgpu_plan_t *plan, const int32_t *d_count, const double *d_F, const sbgpu_bootstrap_params_t *params,
+                              double *d_mean, double *d_var, int32_t *d_status_count, double *d_theta_rep, int32_t *d_status_rep, int32_t *d_iters_rep,
+                              void *stream)
+{
+   const char *who = "sbgpu_em_bootstrap_device";
+   if (const int rc = check_params(who, params); rc != SBGPU_OK) return rc;
+   if (!c || !plan) return api_fail(SBGPU_EINVAL, std::string(who) + ": null ctx/plan");
+   const sb::PlanShape ps = sb::plan_shape(plan);
+   if (ps.n_loci == 0) return SBGPU_OK;
+   if (!d_mean || !d_var || !d_status_count || (!d_count && ps.n_rows) || !d_F) return api_fail(SBGPU_EINVAL, std::string(who) + ": null device pointer");
+   return run_replicates(c, who, plan, d_count, d_F, params, d_mean, d_var, d_status_count, d_theta_rep, d_status_rep, d_iters_rep, (hipStream_t)stream, AfterStats());
+}
+
+int sbgpu_replicate_stats_device(sbgpu_ctx_t *c, int32_t n_rep, int64_t n, const double *d_x, int32_t rank_lo, int32_t rank_hi, double *d_mean,
+                                 double *d_var, double *d_lo, double *d_hi, void *stream)
+{
+   const char *who = "sbgpu_replicate_stats_device";
+   if (!c) return api_fail(SBGPU_EINVAL, std::string(who) + ": null context");
+   if (n_rep < 1 || n < 0) return api_fail(SBGPU_EINVAL, std::string(who) + ": n_rep must be at least 1 and n at least 0");
+   if (const int rc = check_ranks(who, n_rep, rank_lo, rank_hi); rc != SBGPU_OK) return rc;
+   if (n && !d_x) return api_fail(SBGPU_EINVAL, std::string(who) + ": null matrix");
+   if (hipError_t e = hipSetDevice(sb::ctx_device(c)); e != hipSuccess) return api_fail_hip(e, "hipSetDevice");
+   sb::BootIntervalArgs a{};
+   a.n = n, a.n_rep = n_rep, a.rank_lo = rank_lo, a.rank_hi = rank_hi;
+   a.x = d_x, a.mean = d_mean, a.var = d_var, a.lo = d_lo, a.hi = d_hi;
+   return launch_interval(a, (hipStream_t)stream);
+}
+
+int sbgpu_bootstrap_keep(sbgpu_ctx_t *c, int32_t on)
+{
+   if (!c) return api_fail(SBGPU_EINVAL, "sbgpu_bootstrap_keep: null context");
+   sb::ctx_boot_keep(c)->on = on != 0; // (what the last call kept stays valid until the context's next sbgpu_quantify_* call either way)
+   return SBGPU_OK;
+}
+
+int sbgpu_abundance_bootstrap_device(sbgpu_ctx_t *c, const sbgpu_bins_t *bins, const sbgpu_bootstrap_params_t *params, int32_t rank_lo, int32_t rank_hi,
+                                     int32_t keep_theta_rep, sbgpu_comm_t *comm, void *stream, sbgpu_abundance_bootstrap_t *out)
+{
+   const char *who = "sbgpu_abundance_bootstrap_device";
+   if (const int rc = check_params(who, params); rc != SBGPU_OK) return rc;
+   if (!c || !bins || !out) return api_fail(SBGPU_EINVAL, std::string(who) + ": null argument");
+   if (const int rc = check_ranks(who, params->n_rep, rank_lo, rank_hi); rc != SBGPU_OK) return rc;
+   const sb::BootKeep *rec = sb::ctx_boot_keep(c);
+   const sb::BinsContextView v = sb::bins_context_view(bins);
+   if (!v.boot_serial)
+      return api_fail(SBGPU_EINVAL, std::string(who) + ": this handle was made without retention (sbgpu_bootstrap_keep was off for its call, or it is not "
+                                                       "from sbgpu_quantify_resident / sbgpu_front_stream_end)");
+   if (v.boot_serial != rec->serial || !rec->plan)
+      return api_fail(SBGPU_EINVAL, std::string(who) + ": a stale handle: a later call on this context (sbgpu_quantify_*, or another entry that works in the "
+                                                       "context's scratch) has reused what its call kept");
+   const sb::PlanShape ps = sb::plan_shape(rec->plan);
+   const int64_t nl = ps.n_loci, n_iso = ps.n_iso;
+   if (nl != v.n_loci || n_iso != v.n_iso || nl != rec->n_loci || n_iso != rec->n_iso) return api_fail(SBGPU_EINVAL, std::string(who) + ": the handle and the context's record disagree");
+   const int32_t B = params->n_rep;
+   hipStream_t s = stream ? (hipStream_t)stream : sb::ctx_stream(c);
+   if (hipError_t e = hipSetDevice(sb::ctx_device(c)); e != hipSuccess) return api_fail_hip(e, "hipSetDevice");
+   // ---- the results' block, before any kernel: [ten statistics | frac of one replicate | totals | keep and status counts | the replicates' matrices]
+   const size_t ni = (size_t)std::max<int64_t>(n_iso, 1), col = up256(ni * 8);
+   size_t off = 0;
+   auto take = [&off](size_t bytes) {
+      const size_t at = off;
+      off += up256(bytes);
+      return at;
+   };
+   size_t o_stat[10];
+   for (size_t &o : o_stat) o = take(col);
+   const size_t o_frac = take(col), o_total = take((size_t)B * 8), o_keep_count = take(ni * 4), o_status_count = take((size_t)nl * 16);
+   const size_t o_fpkm_rep = take((size_t)B * ni * 8), o_keep_rep = take((size_t)B * ni * 4);
+   const size_t o_theta_rep = keep_theta_rep ? take((size_t)B * ni * 8) : 0;
+   char *d = nullptr;
+   if (hipError_t e = sb::ctx_boot_result(c, off, &d); e != hipSuccess) return api_fail_hip(e, "hipMalloc(the replicates' FPKM and keep matrices)");
+   double *stat[10];
+   for (int i = 0; i < 10; ++i) stat[i] = (double *)(d + o_stat[i]);
+   double *d_theta_mean = stat[0], *d_theta_var = stat[1], *d_fpkm_mean = stat[2], *d_fpkm_var = stat[3], *d_fpkm_lo = stat[4], *d_fpkm_hi = stat[5];
+   double *d_tpm_mean = stat[6], *d_tpm_var = stat[7], *d_tpm_lo = stat[8], *d_tpm_hi = stat[9];
+   double *d_frac = (double *)(d + o_frac), *d_total = (double *)(d + o_total), *d_fpkm_rep = (double *)(d + o_fpkm_rep);
+   int32_t *d_keep_count = (int32_t *)(d + o_keep_count), *d_status_count = (int32_t *)(d + o_status_count), *d_keep_rep = (int32_t *)(d + o_keep_rep);
+   double *d_theta_rep = keep_theta_rep ? (double *)(d + o_theta_rep) : nullptr;
+#define SB_TRY(expr)                                    \
+   do {                                                 \
+      hipError_t e_ = (expr);                           \
+      if (e_ != hipSuccess) {                           \
+         (void)hipStreamSynchronize(s);                 \
+         return api_fail_hip(e_, #expr);                \
+      }                                                 \
+   } while (0)
+   // ---- the replicates: behind each one's statistics step, the reference's epilogue on its theta and status -- FPKM and keep into
+   // row k of the matrices, this rank's kept-FPKM sum into d_total[k].  The mapped-read total and the insert law are the sample's.
+   const sbgpu_abundance_params_t par = rec->params;
+   const sbgpu_plan_t *plan = rec->plan;
+   const int32_t *d_len = rec->d_iso_len;
+   const AfterStats epilogue = [&](int32_t k, const double *d_theta, const int32_t *d_status, hipStream_t js) {
+      return sbgpu_abundance_device(c, plan, d_theta, d_status, d_len, &par, d_fpkm_rep + (size_t)k * (size_t)n_iso, d_frac,
+                                    d_keep_rep + (size_t)k * (size_t)n_iso, d_total + k, js);
+   };
+   if (const int rc = run_replicates(c, who, plan, rec->d_count, rec->d_F, params, d_theta_mean, d_theta_var, d_status_count, d_theta_rep, nullptr, nullptr, s,
+                                     epilogue);
+       rc != SBGPU_OK)
+      return rc;
+   // ---- the total TPM divides by: ONE collective per call, over all replicates
+   if (comm) {
+      if (const int rc = sbgpu_allreduce_sum_f64(comm, d_total, B, s); rc != SBGPU_OK) {
+         (void)hipStreamSynchronize(s);
+         return rc;
+      }
+   }
+   // ---- the replicates' statistics, twice over the columns: the raw FPKM; the TPM (made while staging) with the kept replicates' count
+   SB_TRY(hipMemsetAsync(d_keep_count, 0, ni * 4, s));
+   sb::BootIntervalArgs a{};
+   a.n = n_iso, a.n_rep = B, a.rank_lo = rank_lo, a.rank_hi = rank_hi, a.x = d_fpkm_rep;
+   a.mean = d_fpkm_mean, a.var = d_fpkm_var, a.lo = d_fpkm_lo, a.hi = d_fpkm_hi;
+   if (const int rc = launch_interval(a, s); rc != SBGPU_OK) {
+      (void)hipStreamSynchronize(s);
+      return rc;
+   }
+   a.keep = d_keep_rep, a.total = d_total, a.keep_count = d_keep_count;
+   a.mean = d_tpm_mean, a.var = d_tpm_var, a.lo = d_tpm_lo, a.hi = d_tpm_hi;
+   if (const int rc = launch_interval(a, s); rc != SBGPU_OK) {
+      (void)hipStreamSynchronize(s);
+      return rc;
+   }
+   // ---- what was asked for comes down; the call returns synchronised
+   auto get = [&](void *dst, const void *src, size_t bytes) { return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess; };
+   double *const host_stat[10] = {out->theta_mean, out->theta_var, out->fpkm_mean, out->fpkm_var, out->fpkm_lo, out->fpkm_hi, out->tpm_mean, out->tpm_var, out->tpm_lo, out->tpm_hi};
+   for (int i = 0; i < 10; ++i) SB_TRY(get(host_stat[i], stat[i], (size_t)n_iso * 8));
+   SB_TRY(get(out->keep_count, d_keep_count, (size_t)n_iso * 4));
+   SB_TRY(get(out->status_count, d_status_count, (size_t)nl * 16));
+   SB_TRY(get(out->total_fpkm_rep, d_total, (size_t)B * 8));
+   SB_TRY(get(out->fpkm_rep, d_fpkm_rep, (size_t)B * (size_t)n_iso * 8));
+   SB_TRY(get(out->keep_rep, d_keep_rep, (size_t)B * (size_t)n_iso * 4));
+   if (d_theta_rep) SB_TRY(get(out->theta_rep, d_theta_rep, (size_t)B * (size_t)n_iso * 8));
+   SB_TRY(hipStreamSynchronize(s));
+#undef SB_TRY
+   if (sb::ctx_take_wide_error(c)) return api_fail(SBGPU_EHIP, std::string(who) + ": a barrier of the wide-locus EM kernel timed out: the loci it served have no result");
+   out->n_rep = B, out->n_iso = n_iso, out->n_loci = nl;
+   out->d_theta_mean = d_theta_mean, out->d_theta_var = d_theta_var;
+   out->d_fpkm_mean = d_fpkm_mean, out->d_fpkm_var = d_fpkm_var, out->d_fpkm_lo = d_fpkm_lo, out->d_fpkm_hi = d_fpkm_hi;
+   out->d_tpm_mean = d_tpm_mean, out->d_tpm_var = d_tpm_var, out->d_tpm_lo = d_tpm_lo, out->d_tpm_hi = d_tpm_hi;
+   out->d_keep_count = d_keep_count, out->d_status_count = d_status_count, out->d_total_fpkm_rep = d_total;
+   out->d_fpkm_rep = d_fpkm_rep, out->d_keep_rep = d_keep_rep, out->d_theta_rep = d_theta_rep;
+   return SBGPU_OK;
 }
 
 } // extern "C"

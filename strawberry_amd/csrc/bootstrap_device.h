@@ -6,6 +6,9 @@
 //   boot_item_scan_kernel  once per call: the loci's first work items (exclusive scan; one workgroup)
 //   boot_resample_kernel   per replicate: one workgroup per (replicate, locus, slice); integers only
 //   boot_stats_kernel      per replicate: one thread per isoform (mean, M2 -> variance) and per locus (status counts)
+//   boot_interval_kernel   once per statistic: mean, variance and two order statistics of every column of a replicate-major
+//                          matrix [n_rep][n] (sbgpu_replicate_stats_device; the FPKM and TPM intervals of
+//                          sbgpu_abundance_bootstrap_device)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -205,6 +208,134 @@ __global__ __launch_bounds__(256) void boot_stats_kernel(const BootStatsArgs a)
       if (st >= 0 && st < 4) a.status_count[i * 4 + st] += 1;
       if (a.status_rep) a.status_rep[i] = st;
       if (a.iters_rep) a.iters_rep[i] = a.iters[i];
+   }
+}
+
+// ---- statistics over the replicates, column by column (rules: bootstrap_rules.h)
+//
+// The matrix is replicate-major: a column's elements lie 8 n bytes apart.  A workgroup stages a tile of kBootTile neighbouring
+// columns through LDS -- sixteen lanes read the tile's 128 contiguous bytes of a row, a wave four rows at once -- and every wave
+// then owns kBootTile / 4 of the columns, one after the other: a lane runs Welford's recurrence over the staged column in
+// replicate order; the wave takes the column into registers as sort keys (element e = v * 64 + lane in key[v], padded to the
+// next power of two with kBootKeyPad), sorts it with a bitonic network -- lane exchanges for strides below 64, register swaps
+// above, every index known at compile time -- and reads the two requested positions out.  With `keep` the staged value is the
+// replicate's TPM (boot_tpm_value of the FPKM, its keep flag and the replicate's total), so no TPM matrix is ever written, and
+// the staging lanes count the column's kept replicates.  A column in LDS is rotated by its index within the tile: the tile's
+// columns of one row would otherwise share a bank whenever n_rep is a multiple of 32 (rotated by c mod n_rep: n_rep may be below the tile's width).
+constexpr int kBootTile = 16;             // columns of a workgroup's tile: 16 * n_rep * 8 bytes of LDS, 128 KB of gfx950's 160 at the cap
+constexpr int kBootIntervalThreads = 256; // four waves, kBootTile / 4 columns each
+
+struct BootIntervalArgs {
+   int64_t n;                    // columns
+   int32_t n_rep, rank_lo, rank_hi;
+   const double *x;              // [n_rep][n]
+   const int32_t *keep;          // [n_rep][n], or null: x is taken as it stands
+   const double *total;          // [n_rep] (with keep)
+   double *mean, *var, *lo, *hi; // [n], each may be null
+   int32_t *keep_count;          // [n], zero on entry, or null (with keep)
+};
+
+template <int V> // keys per lane: the column padded to 64 V elements
+__global__ __launch_bounds__(kBootIntervalThreads) void boot_interval_kernel(const BootIntervalArgs a)
+{
+   extern __shared__ double s_col[]; // [kBootTile][n_rep]
+   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+   const int B = a.n_rep;
+   const int64_t j0 = (int64_t)blockIdx.x * kBootTile;
+   {
+      const int c = tid & (kBootTile - 1), rot = c % B;
+      const int64_t j = j0 + c;
+      int32_t kept = 0;
+      for (int r = tid / kBootTile; r < B; r += kBootIntervalThreads / kBootTile) {
+         double v = 0.0;
+         if (j < a.n) {
+            const size_t at = (size_t)r * (size_t)a.n + (size_t)j;
+            v = a.x[at];
+            if (a.keep) {
+               const int32_t kp = a.keep[at];
+               kept += kp != 0;
+               v = boot_tpm_value(v, kp, a.total[r]);
+            }
+         }
+         int pos = r + rot;
+         if (pos >= B) pos -= B;
+         s_col[c * B + pos] = v;
+      }
+      if (a.keep_count) { // (whole waves arrive here) the lanes of a wave that staged the same column: the lane bits above the tile's
+#pragma unroll
+         for (int d = kBootTile; d < 64; d <<= 1) kept += __shfl_xor(kept, d);
+         if (lane < kBootTile && j < a.n && kept) atomicAdd(&a.keep_count[j], kept);
+      }
+   }
+   __syncthreads();
+   constexpr int kPerWave = kBootTile / (kBootIntervalThreads / 64);
+   if (lane < kPerWave && (a.mean || a.var)) {
+      const int c = wave * kPerWave + lane, rot = c % B;
+      const int64_t j = j0 + c;
+      if (j < a.n) {
+         double m = 0.0, q = 0.0;
+         for (int k = 0; k < B; ++k) {
+            int pos = k + rot;
+            if (pos >= B) pos -= B;
+            boot_welford_step(s_col[c * B + pos], k, m, q);
+         }
+         if (a.mean) a.mean[j] = m;
+         if (a.var) a.var[j] = boot_welford_var(q, B);
+      }
+   }
+   if (!a.lo && !a.hi) return;
+   for (int ci = 0; ci < kPerWave; ++ci) {
+      const int c = wave * kPerWave + ci, rot = c % B;
+      const int64_t j = j0 + c;
+      if (j >= a.n) break; // (uniform over the wave)
+      uint64_t key[V];
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+         const int e = v * 64 + lane;
+         int pos = e + rot;
+         if (pos >= B) pos -= B;
+         key[v] = e < B ? boot_sort_key(s_col[c * B + pos]) : kBootKeyPad;
+      }
+#pragma unroll
+      for (int size = 2; size <= 64 * V; size <<= 1) {
+#pragma unroll
+         for (int d = size >> 1; d > 0; d >>= 1) {
+            if (d >= 64) { // both elements in this lane (size >= 128: the direction depends on v alone)
+               const int dv = d >> 6;
+#pragma unroll
+               for (int v = 0; v < V; ++v) {
+                  if (v & dv) continue;
+                  const bool asc = ((v * 64) & size) == 0;
+                  const uint64_t p = key[v], q = key[v | dv];
+                  const uint64_t mn = p < q ? p : q, mx = p < q ? q : p;
+                  key[v] = asc ? mn : mx;
+                  key[v | dv] = asc ? mx : mn;
+               }
+            } else {
+               const bool lower = (lane & d) == 0;
+#pragma unroll
+               for (int v = 0; v < V; ++v) {
+                  const uint64_t other = (uint64_t)__shfl_xor((unsigned long long)key[v], d);
+                  const bool asc = ((v * 64 + lane) & size) == 0;
+                  const uint64_t mn = key[v] < other ? key[v] : other, mx = key[v] < other ? other : key[v];
+                  key[v] = asc == lower ? mn : mx;
+               }
+            }
+         }
+      }
+      // element e of the sorted column lives in key[e >> 6] of lane e & 63
+      uint64_t k_lo = 0, k_hi = 0;
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+         if (v == (a.rank_lo >> 6)) k_lo = key[v];
+         if (v == (a.rank_hi >> 6)) k_hi = key[v];
+      }
+      k_lo = (uint64_t)__shfl((unsigned long long)k_lo, a.rank_lo & 63);
+      k_hi = (uint64_t)__shfl((unsigned long long)k_hi, a.rank_hi & 63);
+      if (lane == 0) {
+         if (a.lo) a.lo[j] = boot_key_value(k_lo);
+         if (a.hi) a.hi[j] = boot_key_value(k_hi);
+      }
    }
 }
 

@@ -1,6 +1,7 @@
 // strawberry_amd/csrc/bootstrap_host.cpp -- sbgpu_bootstrap_counts_host (include/sbgpu.h): one bootstrap replicate's bin
-// counts on the host.  The one CPU statement of what csrc/bootstrap_device.h computes: every draw is a function of
+// counts on the host, and sbgpu_replicate_stats_host: the replicates' statistics.  The one CPU statement of what csrc/bootstrap_device.h computes: every draw is a function of
 // bootstrap_rules.h, which the kernels call too.  No kernels here.
+#include <algorithm>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -47,6 +48,32 @@ extern "C" int sbgpu_bootstrap_counts_host(int64_t n_loci, const int64_t *row_of
          ++count_out[r0 + sb::boot_row_of(incl.data(), nr, t[0])];
          if (2 * q + 1 < N) ++count_out[r0 + sb::boot_row_of(incl.data(), nr, t[1])];
       }
+   }
+   return SBGPU_OK;
+}
+
+// sbgpu_replicate_stats_host: mean, variance and two order statistics of every column of x[n_rep][n], by the rules of
+// bootstrap_rules.h (the kernel boot_interval_kernel calls the same functions).  No cap on n_rep here.
+extern "C" int sbgpu_replicate_stats_host(int32_t n_rep, int64_t n, const double *x, int32_t rank_lo, int32_t rank_hi, double *mean, double *var,
+                                          double *lo, double *hi)
+{
+   if (n_rep < 1 || n < 0) return api_fail(SBGPU_EINVAL, "sbgpu_replicate_stats_host: n_rep must be at least 1 and n at least 0");
+   if (rank_lo < 0 || rank_lo > rank_hi || rank_hi >= n_rep)
+      return api_fail(SBGPU_EINVAL, "sbgpu_replicate_stats_host: the ranks must satisfy 0 <= rank_lo <= rank_hi < n_rep");
+   if (n && !x) return api_fail(SBGPU_EINVAL, "sbgpu_replicate_stats_host: null matrix");
+   std::vector<uint64_t> key((size_t)n_rep);
+   for (int64_t j = 0; j < n; ++j) {
+      double m = 0.0, q = 0.0;
+      for (int32_t k = 0; k < n_rep; ++k) {
+         const double v = x[(size_t)k * (size_t)n + (size_t)j];
+         sb::boot_welford_step(v, k, m, q);
+         key[(size_t)k] = sb::boot_sort_key(v);
+      }
+      if (mean) mean[j] = m;
+      if (var) var[j] = sb::boot_welford_var(q, n_rep);
+      if (lo || hi) std::sort(key.begin(), key.end());
+      if (lo) lo[j] = sb::boot_key_value(key[(size_t)rank_lo]);
+      if (hi) hi[j] = sb::boot_key_value(key[(size_t)rank_hi]);
    }
    return SBGPU_OK;
 }

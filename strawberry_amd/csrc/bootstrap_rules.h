@@ -71,4 +71,41 @@ __host__ __device__ inline int32_t boot_row_of(const Prefix *incl, int32_t n, ui
    return lo;
 }
 
+// ---- statistics over the replicates of one column x_0 .. x_{B-1} (sbgpu_replicate_stats_*, the FPKM / TPM intervals)
+//
+// Mean and variance: Welford's recurrence in replicate order, as boot_stats_kernel states it (step k is 0-based here):
+//    m_k = m_{k-1} + (x_k - m_{k-1}) / (k + 1),   M2_k = M2_{k-1} + (x_k - m_{k-1}) (x_k - m_k),   var = M2 / (B - 1)  (0 for B = 1).
+// Order statistics: the column sorted ascending under <, NaNs last; lo / hi are the elements at two 0-based integer positions,
+// no interpolation.  The order is made total by sorting boot_sort_key(x), an unsigned integer that rises with x: -0.0 sorts in
+// front of +0.0, a NaN of either sign behind +infinity (by its payload).  boot_key_value gives the element back: its own bits,
+// except that a NaN comes back with the sign bit cleared.  The key of all ones is the padding of the kernel's sorting network:
+// it sorts behind (or, for the one NaN with these bits, equal to) every element.
+constexpr int32_t kBootMaxStatRep = 1024; // replicates of one column the kernel sorts in a wave's registers; above: SBGPU_ESHAPE
+constexpr uint64_t kBootKeyPad = ~(uint64_t)0;
+
+__host__ __device__ inline void boot_welford_step(double x, int32_t step, double &m, double &q)
+{
+   const double d = x - m;
+   m = m + d / (double)(step + 1);
+   q = q + d * (x - m);
+}
+__host__ __device__ inline double boot_welford_var(double q, int32_t n_rep) { return n_rep > 1 ? q / (double)(n_rep - 1) : 0.0; }
+
+__host__ __device__ inline uint64_t boot_sort_key(double x)
+{
+   uint64_t b;
+   __builtin_memcpy(&b, &x, 8);
+   if (x != x) b &= ~((uint64_t)1 << 63);
+   return (b >> 63) ? ~b : (b | ((uint64_t)1 << 63));
+}
+__host__ __device__ inline double boot_key_value(uint64_t k)
+{
+   const uint64_t b = (k >> 63) ? (k & ~((uint64_t)1 << 63)) : ~k;
+   double x;
+   __builtin_memcpy(&x, &b, 8);
+   return x;
+}
+// The TPM of one replicate's isoform: the expression tpm_kernel (sbgpu_api.hip) evaluates
+__host__ __device__ inline double boot_tpm_value(double fpkm, int32_t keep, double total) { return keep ? 1e6 * fpkm / total : 0.0; }
+
 } // namespace sb

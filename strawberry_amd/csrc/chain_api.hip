@@ -271,6 +271,11 @@ struct QuantifyCall {
    sb::ContextKeep *keep_rec = nullptr;
    bool retain = false;
    const int32_t *d_hit_bin_local = nullptr;
+   // -- what the call leaves for sbgpu_abundance_bootstrap_device (sbgpu_bootstrap_keep)
+   sb::BootKeep *boot_rec = nullptr;
+   bool boot_retain = false;
+   const int32_t *d_iso_len = nullptr;     // the isoforms' lengths as the epilogue read them
+   sbgpu_abundance_params_t epi_params{};  // the epilogue's parameters as it filled them in
    // -- SBGPU_HOST_TIMING: stage times on stderr; =2: host clock only, no synchronisation
    bool timing = false, timing_sync = false;
    double t_stage = 0;
@@ -367,6 +372,10 @@ int QuantifyCall::check_arguments()
    keep_rec = sb::ctx_context_keep(c);
    keep_rec->serial = 0;
    retain = keep_rec->on && ro && on_dev;
+   // likewise what was kept for sbgpu_abundance_bootstrap_device: that call's plan and the bootstrap's results go back
+   sb::ctx_boot_release(c);
+   boot_rec = sb::ctx_boot_keep(c);
+   boot_retain = boot_rec->on && ro && on_dev;
    nl = an->n_loci, nh = a.hits->n_hits;
    if (nl < 1 || nh < 0) return api_fail(SBGPU_EINVAL, "sbgpu_quantify_host: bad counts");
    if (!an->iso_off || !an->exon_off || !an->seg_off || (nh && (!a.hits->hit_locus || !a.hits->feat_off || !a.hit_mass)))
@@ -692,6 +701,7 @@ int QuantifyCall::launch_epilogue(const WorkArena &w)
    par.total_mapped_reads = (int32_t)law.mapped_total;
    par.insert_mean = law.ins.mean; // _sample._insert_size_dist->_mean (estimate.cpp:318)
    sb::ctx_stage_begin(c, "abundance + tpm", s);
+   d_iso_len = d_len, epi_params = par;
    SB_RC(sbgpu_abundance_device(c, plan, w.theta(), w.status(), d_len, &par, w.fpkm(), w.frac(), w.keep(), w.fpkm_sum(), s));
    if (ro->comm) SB_RC(sbgpu_allreduce_sum_f64(ro->comm, w.fpkm_sum(), 1, s));
    SB_RC(sbgpu_tpm_device(c, n_iso, w.fpkm(), w.keep(), w.fpkm_sum(), w.tpm(), s));
@@ -849,9 +859,19 @@ int QuantifyCall::finish_handle(const WorkArena &w)
    } else {
       sb::bins_set_weights(bins, std::move(F));
    }
+   static std::atomic<uint64_t> serial{0};
+   if (boot_retain && plan) {
+      // sbgpu_bootstrap_keep: the plan changes hands, the rest is said where it lies (nothing is copied)
+      boot_rec->serial = ++serial;
+      boot_rec->plan = plan, plan = nullptr;
+      boot_rec->n_loci = nl, boot_rec->n_iso = n_iso;
+      boot_rec->d_count = d_count_dev ? d_count_dev : w.count(); // (the handle's arena / the no-hits route's upload)
+      boot_rec->d_F = w.F(), boot_rec->d_iso_len = d_iso_len;
+      boot_rec->params = epi_params;
+      sb::bins_set_boot_serial(bins, boot_rec->serial);
+   }
    if (retain) {
       // sbgpu_context_table_keep: say where the table's inputs are (all of them this call's scratch, nothing is copied)
-      static std::atomic<uint64_t> serial{0};
       keep_rec->serial = ++serial;
       keep_rec->n_hits = nh, keep_rec->n_loci = nl, keep_rec->n_iso = n_iso, keep_rec->compat_words = cw;
       keep_rec->d_compat = in->compat(), keep_rec->d_hit_bin_local = d_hit_bin_local;

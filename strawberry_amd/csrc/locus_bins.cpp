@@ -56,6 +56,7 @@ struct sbgpu_bins {
    bool grouped_on_device = false;
    std::string host_grouping_reason;
    uint64_t context_serial = 0; // the resident call that kept the context table's inputs for this handle (sbgpu_context_table_keep)
+   uint64_t boot_serial = 0;    // the resident call that kept the bootstrap's inputs for this handle (sbgpu_bootstrap_keep)
    ~sbgpu_bins()
    {
       sb::dev_give(dev.arena, dev.capacity);
@@ -608,6 +609,7 @@ void bins_set_device_hit_bin(sbgpu_bins_t *b, char *arena, size_t capacity, int6
 }
 const double *bins_weights_tail(const sbgpu_bins_t *b, size_t at) { return b->F.data() + at; }
 void bins_set_context_serial(sbgpu_bins_t *b, uint64_t serial) { b->context_serial = serial; }
+void bins_set_boot_serial(sbgpu_bins_t *b, uint64_t serial) { b->boot_serial = serial; }
 BinsContextView bins_context_view(const sbgpu_bins_t *b)
 {
    BinsContextView v;
@@ -618,6 +620,7 @@ BinsContextView bins_context_view(const sbgpu_bins_t *b)
    if ((int64_t)b->F.size() >= b->n_elem && !(b->F.empty() && b->n_bins > 0)) v.F = b->F.data();
    if (b->dev_bins.arena) v.d_key = (const uint32_t *)(b->dev_bins.arena + b->dev_bins.o_key);
    v.context_serial = b->context_serial;
+   v.boot_serial = b->boot_serial;
    return v;
 }
 const DevicePairs *bins_device_pairs(const sbgpu_bins_t *b) { return b && b->pairs_on_device ? &b->dev : nullptr; }

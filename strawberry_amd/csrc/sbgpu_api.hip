@@ -88,6 +88,9 @@ struct sbgpu_ctx {
    sb::ContextKeep context_keep;               // sbgpu_context_table_keep
    char *boot_scratch = nullptr;               // sb::ctx_boot_scratch (sb::dev_take'n)
    size_t boot_scratch_cap = 0;
+   sb::BootKeep boot_keep;                     // sbgpu_bootstrap_keep
+   char *boot_result = nullptr;                // sb::ctx_boot_result (sb::dev_take'n)
+   size_t boot_result_cap = 0;
 };
 
 namespace sb {
@@ -281,6 +284,7 @@ void dev_give(char *block, size_t capacity)
 const ResidentAnnotation *ctx_resident_annotation(const sbgpu_ctx_t *ctx) { return ctx->resident; }
 void ctx_set_resident_annotation(sbgpu_ctx_t *ctx, ResidentAnnotation *r)
 {
+   ctx->boot_keep.serial = 0; // (the bootstrap's record may point at the pinned annotation's isoform lengths)
    if (ctx->resident) {
       (void)hipStreamSynchronize(ctx->stream);
       dev_give(ctx->resident->arena, ctx->resident->capacity);
@@ -297,7 +301,7 @@ hipError_t ctx_scratch(sbgpu_ctx_t *ctx, int slot, size_t bytes, char **out)
    if (slot < 0 || slot >= 9) return hipErrorInvalidValue;
    // what a resident call kept for sbgpu_context_table_device lies in slots 0..7: whoever asks for one of them (any entry that
    // works in the context's scratch, not only sbgpu_quantify_*) may overwrite or free it, so the record ends here
-   if (slot != 8) ctx->context_keep.serial = 0;
+   if (slot != 8) ctx->context_keep.serial = 0, ctx->boot_keep.serial = 0;
    if (bytes < 256) bytes = 256;
    if (ctx->scratch_bytes[slot] < bytes) {
       if (ctx->scratch[slot]) (void)hipFree(ctx->scratch[slot]);
@@ -328,11 +332,33 @@ hipError_t ctx_boot_scratch(sbgpu_ctx_t *ctx, size_t bytes, char **out)
    *out = ctx->boot_scratch;
    return hipSuccess;
 }
+BootKeep *ctx_boot_keep(sbgpu_ctx_t *ctx) { return &ctx->boot_keep; }
+hipError_t ctx_boot_result(sbgpu_ctx_t *ctx, size_t bytes, char **out)
+{
+   *out = nullptr;
+   if (ctx->boot_result_cap < bytes) {
+      dev_give(ctx->boot_result, ctx->boot_result_cap);
+      ctx->boot_result = nullptr, ctx->boot_result_cap = 0;
+      hipError_t e = dev_take(bytes, &ctx->boot_result, &ctx->boot_result_cap);
+      if (e != hipSuccess) return e;
+   }
+   *out = ctx->boot_result;
+   return hipSuccess;
+}
 bool ctx_take_wide_error(sbgpu_ctx_t *ctx)
 {
    if (!ctx->wide_error || !*ctx->wide_error) return false;
    *ctx->wide_error = 0;
    return true;
+}
+void ctx_boot_release(sbgpu_ctx_t *ctx)
+{
+   BootKeep &k = ctx->boot_keep;
+   k.serial = 0;
+   if (k.plan) sbgpu_plan_destroy(k.plan);
+   k.plan = nullptr;
+   dev_give(ctx->boot_result, ctx->boot_result_cap);
+   ctx->boot_result = nullptr, ctx->boot_result_cap = 0;
 }
 } // namespace sb
 
@@ -654,6 +680,7 @@ int sbgpu_finalize(sbgpu_ctx_t *c)
    for (hipEvent_t ev : c->order_ev)
       if (ev) (void)hipEventDestroy(ev);
    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
+   sb::ctx_boot_release(c);
    sb::ctx_set_resident_annotation(c, nullptr);
    sb::dev_give(c->boot_scratch, c->boot_scratch_cap);
    delete c;

@@ -129,7 +129,9 @@ class FrontQuantifier(ChainQuantifier):
     def __init__(self, ctx, n_loci=60000, n_frags=2e8, seed=31, read_len=75, loci_subset=None, **resident_kw):
         """loci_subset = (rank, world): this rank's loci of ONE sample (locus l on rank l mod world, as the chain shards) --
         its records only; the clusters, like the reference's, are the shard's own gene models.  resident_kw: ChainQuantifier's
-        resident / empirical / comm / min_isoform_frac / keep_context (the last stage is then sbgpu_quantify_resident: records -> TPM)."""
+        resident / empirical / comm / min_isoform_frac / keep_context / keep_bootstrap (the last stage is then sbgpu_quantify_resident:
+        records -> TPM).  keep_bootstrap=True: after step() or stream_step(), abundance_bootstrap(n_rep, seed, ...) gives the FPKM / TPM
+        bootstrap of that pass (sbgpu_abundance_bootstrap_device on its handle)."""
         super().__init__(ctx, n_loci=n_loci, n_frags=n_frags, seed=seed, read_len=read_len, loci_subset=loci_subset, pin=True, **resident_kw)
         torch = self.torch
         t = time.perf_counter()

@@ -186,13 +186,46 @@ def quantify_host(annot, hits, insert, read_len, long_read=False, ctx=None, devi
                        "end_offset": used.end_offset, "total_reads": used.total_reads, "emp_hist": emp}}
 
 
+class BinsHandle:
+    """Owner of an sbgpu_bins_t a call handed out: `h` is the raw handle (what bootstrap.abundance_bootstrap_device and
+    context.context_table_device take; they accept this object too).  close() -- also on __exit__ and when the object is
+    collected -- destroys it, once."""
+
+    def __init__(self, L, h):
+        self.L, self.h = L, h
+
+    def close(self):
+        if self.h is not None and self.h.value:
+            self.L.sbgpu_bins_destroy(self.h)
+        self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # interpreter shutdown: the library may be gone already
+            pass
+
+
 def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=False, ctx=None, device=0, comm=None,
-                      min_isoform_frac=0.0, filter_by_expression=True, effective_len_norm=False, with_context=False):
+                      min_isoform_frac=0.0, filter_by_expression=True, effective_len_norm=False, with_context=False, bootstrap=None,
+                      keep_bootstrap=False, keep_handle=False):
     """sbgpu_quantify_resident on host hits brought to the device first (torch owns the copies): pass 1 (insert=None: the
     empirical insert-size law, built on the device), bins, weights, EM, FPKM / Frac / keep, the FPKM all-reduce over `comm`
     (dist.AbiComm / dist.HostComm; None: a world of one), TPM.  The hits must come grouped by locus.
     with_context: the call keeps what the `-f` table needs (sbgpu_context_table_keep) and the table is built on the device
     (context.context_table_device) -> "context"; "bins": the handle's LocusBins (the rows index its bins).
+    bootstrap = dict(n_rep=, seed=, level=0.95, locus_id=None, ...): the call keeps what the bootstrap needs (sbgpu_bootstrap_keep)
+    and bootstrap.abundance_bootstrap_device runs on its handle with these arguments (and `comm`) -> "bootstrap": its dict; "bins" as above.
+    keep_bootstrap: retention for the bootstrap on, without running it (for a caller that runs it several times).
+    keep_handle: the handle is not exported but returned as "handle", a BinsHandle that owns it -- it is destroyed by its close(),
+    as a context manager, or when the object is collected; the caller runs bootstrap.abundance_bootstrap_device /
+    context.context_table_device on it before the context's next quantify call.
     -> dict(theta, fpkm, frac, tpm, keep, status, iters, insert, total_fpkm, total_mapped_reads, n_frag_lens, info)"""
     import torch
     ctx = ctx or default_context(device)
@@ -224,6 +257,9 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     torch.cuda.synchronize(dev)
     if with_context:
         _lib.check(L.sbgpu_context_table_keep(ctx.h, 1), "sbgpu_context_table_keep")
+    keep_bootstrap = bool(keep_bootstrap) or bootstrap is not None
+    if keep_bootstrap:
+        _lib.check(L.sbgpu_bootstrap_keep(ctx.h, 1), "sbgpu_bootstrap_keep")
     try:
         _lib.check(L.sbgpu_quantify_resident(ctx.h, C.byref(a), C.byref(hs), d_mass.data_ptr(), off.ctypes.data,
                                              C.byref(ins) if ins is not None else None, int(read_len), int(long_read), int(mapped_reads),
@@ -232,23 +268,32 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     finally:
         if with_context:
             L.sbgpu_context_table_keep(ctx.h, 0)    # (what the call kept stays until the context's next quantify call)
+        if keep_bootstrap:
+            L.sbgpu_bootstrap_keep(ctx.h, 0)
     emp = None
     if used.use_emp:
         emp = np.ctypeslib.as_array(used.emp_hist, shape=(used.end_offset - used.start_offset + 1,)).copy()
+    owner = BinsHandle(L, handle) if keep_handle else None     # (from here on an exception frees the handle with the object)
     info = (C.c_int64 * 8)()
     _lib.check(L.sbgpu_bins_info(handle, info), "sbgpu_bins_info")
-    table = bins = None
-    if with_context:
+    table = bins = boot = None
+    if with_context or bootstrap is not None:
         from . import context
+        from .bootstrap import abundance_bootstrap_device
         from .exonbin import LocusBins
         try:
-            table = context.context_table_device(ctx, handle)
+            if bootstrap is not None:
+                boot = abundance_bootstrap_device(ctx, handle, comm=comm, **bootstrap)
+            if with_context:
+                table = context.context_table_device(ctx, handle)
         except Exception:
-            L.sbgpu_bins_destroy(handle)
+            if owner is None:
+                L.sbgpu_bins_destroy(handle)
             raise
-        bins = LocusBins.__new__(LocusBins)
-        bins._export(L, annot, handle, hits.n_hits, annot.compat_words, annot.key_words, with_hit_bin=False)   # destroys the handle
-    else:
+        if not keep_handle:
+            bins = LocusBins.__new__(LocusBins)
+            bins._export(L, annot, handle, hits.n_hits, annot.compat_words, annot.key_words, with_hit_bin=False)   # destroys the handle
+    elif not keep_handle:
         L.sbgpu_bins_destroy(handle)
     r = {k: (v[:n_iso] if k not in ("status", "iters") else v[:nl]) for k, v in res.items()}
     r.update({"insert": {"mean": used.mean, "sd": used.sd, "use_emp": bool(used.use_emp), "start_offset": used.start_offset,
@@ -257,4 +302,8 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
               "info": {"n_bins": int(info[2]), "n_elem": int(info[3]), "n_pairs": int(info[4])}})
     if with_context:
         r.update(context=table, bins=bins)
+    if bootstrap is not None:
+        r.update(bootstrap=boot, bins=bins)
+    if keep_handle:
+        r["handle"] = owner
     return r

@@ -12,6 +12,12 @@ Device events around windows that end in a synchronisation, after a warm-up wind
   counts_ms_per_replicate    sbgpu_bootstrap_counts_device with B = --count-reps: the resampling alone (prefix sums once per call)
   host_route_ms_per_replicate  numpy multinomial per locus, upload, sbgpu_em_run_device, download theta, numpy Welford: the route
                              without this entry (wall clock; --host-reps replicates)
+--resident: the bootstrap of the resident path on the chain sample (bench.py --workload c3-chain's generator):
+  resident_bootstrap_ms_per_replicate  sbgpu_abundance_bootstrap_device on the handle of one sbgpu_quantify_resident call, the whole
+                             call (its wait, the collective-free epilogues, the two statistics passes, the downloads) / B
+  em_bootstrap_ms_per_replicate  sbgpu_em_bootstrap_device on the same batch (the handle's bins, sbgpu_quantify_host's weights) in
+                             the same process: code the parent commit has too, the baseline
+  with --kernel-loop N only N calls of the resident bootstrap, for the kernel trace.
 --kernel-loop N: only N bootstrap calls of B replicates, for a `rocprofv3 --kernel-trace --stats` run of its own;
 --kernel-stats FILE merges that run's per-kernel averages (the *_kernel_stats.csv) into --out."""
 import argparse
@@ -98,13 +104,54 @@ def host_route(solver, batch, n_rep, seed):
     return summary(total), {k: summary(v) for k, v in parts.items()}
 
 
+def resident_leg(args):
+    """-> the --resident document (or, with --kernel-loop, just the calls)"""
+    from strawberry_amd import chain, em, synth
+    from strawberry_amd.quantify import quantify_host
+    ctx = em.default_context(0)
+    q = chain.ChainQuantifier(ctx, n_loci=args.loci, n_frags=2e8 * args.loci / 60000.0, resident=True, min_isoform_frac=0.01, keep_bootstrap=True)
+    torch = q.torch
+    q.step()
+    run = lambda: q.abundance_bootstrap(args.reps, args.seed, level=0.95, replicates=False)  # noqa: E731
+    if args.kernel_loop:
+        for _ in range(args.kernel_loop):
+            run()
+        print(json.dumps({"kernel_loop": args.kernel_loop, "reps": args.reps, "resident": True}))
+        q.close()
+        return None
+    doc = {"tool": "tools/bench_bootstrap.py --resident", "build_id": ctx.L.sbgpu_build_id().decode(), "n_loci": q.n_loci, "n_iso": q.n_iso,
+           "n_hits": q.n_hits, "n_frags": q.n_frags, "reps": args.reps, "measured": True}
+    first = run()
+    doc["kept_in_all_replicates"] = int((first["keep_count"] == args.reps).sum())
+    doc["kept_in_some_replicates"] = int(((first["keep_count"] > 0) & (first["keep_count"] < args.reps)).sum())
+    boot = lambda: event_window(torch, q.dev, run) / args.reps  # noqa: E731
+    doc["resident_bootstrap_ms_per_replicate"] = summary([boot() for _ in range(args.windows)])
+    print(json.dumps({"resident_bootstrap_ms_per_replicate": doc["resident_bootstrap_ms_per_replicate"]}), flush=True)
+    # the same batch by hand: the bins of the sample's hits and the host entry's weights
+    h = quantify_host(q.annot, q.hits.host_hits(q.n_loci), q.insert, q.read_len, ctx=ctx)
+    b = h["bins"]
+    mine = q.step(keep=True)     # one more resident step, its handle exported: both legs must solve the same batch
+    if not (np.array_equal(mine.row_off, b.row_off) and np.array_equal(np.asarray(mine.count), np.asarray(b.count))):
+        raise RuntimeError("the host entry's bins differ from the resident call's: the two legs would not solve the same batch")
+    doc["same_bins_in_both_legs"] = True
+    s = em.EmBatchSolver(synth.LocusBatch(b.row_off, b.iso_off, b.f_off, np.asarray(b.count, np.int32), h["F"], b.iso_len, "chain sample"), ctx)
+    doc["n_rows"] = int(b.row_off[-1])
+    base = lambda: event_window(torch, s.dev, lambda: s.run_bootstrap(args.reps, args.seed)) / args.reps  # noqa: E731
+    base()
+    doc["em_bootstrap_ms_per_replicate"] = summary([base() for _ in range(args.windows)])
+    doc["added_ms_per_replicate"] = doc["resident_bootstrap_ms_per_replicate"]["median"] - doc["em_bootstrap_ms_per_replicate"]["median"]
+    print(json.dumps({"em_bootstrap_ms_per_replicate": doc["em_bootstrap_ms_per_replicate"], "added_ms_per_replicate": doc["added_ms_per_replicate"]}), flush=True)
+    q.close()
+    return doc
+
+
 def kernel_stats(path):
     """rocprofv3's *_kernel_stats.csv -> {kernel: calls, average us} for the bootstrap's kernels and the EM's"""
     out = {}
     for row in csv.DictReader(open(path)):
         name = row.get("Name") or row.get("KernelName") or ""
         short = name.split("(")[0].split("::")[-1].split("<")[0]
-        if "boot_" in name or "fused" in name or "em_" in name or "wide" in name:
+        if "boot_" in name or "fused" in name or "em_" in name or "wide" in name or "abundance" in name:
             out[short] = {"calls": int(row["Calls"]), "avg_us": float(row["AverageNs"]) / 1e3, "total_ms": float(row["TotalDurationNs"]) / 1e6}
     return out
 
@@ -123,12 +170,19 @@ def main():
     ap.add_argument("--kernel-stats", default=None)
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5742)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--resident", action="store_true", help="the bootstrap of the resident path on the chain sample")
     args = ap.parse_args()
     if args.kernel_stats:
         doc = json.load(open(args.out))
         doc["kernels"] = kernel_stats(args.kernel_stats)
         json.dump(doc, open(args.out, "w"), indent=1)
         print(json.dumps(doc["kernels"]))
+        return
+    if args.resident:
+        doc = resident_leg(args)
+        if doc is not None and args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            json.dump(doc, open(args.out, "w"), indent=1)
         return
     if args.child_plain:
         sys.path.insert(0, os.path.abspath(args.child_plain))
