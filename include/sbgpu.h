@@ -1062,6 +1062,65 @@ int sbgpu_abundance_bootstrap_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins,
                                      int32_t rank_lo, int32_t rank_hi, int32_t keep_theta_rep, sbgpu_comm_t *comm, void *stream,
                                      sbgpu_abundance_bootstrap_t *out);
 
+/* ---- abundances per locus, and the bootstrap of Frac and of the loci's FPKM / TPM ------------------------------
+ * A locus is what Strawberry calls a gene (gene_id, gene_frag_count).  The rule (csrc/bootstrap_rules.h: boot_locus_sum,
+ * boot_locus_tpm; the host form and boot_locus_sum_kernel call the same functions, compiled with -ffp-contract=off).  For one
+ * abundance vector -- fpkm[n_iso], keep[n_iso], total_fpkm -- and locus l with the isoforms iso_off[l] .. iso_off[l+1]-1:
+ *    locus_fpkm[l]  starts at 0.0 and adds fpkm[j] over the isoforms with keep[j] != 0, in isoform order: the isoforms the
+ *                   epilogue's own kept-FPKM sum takes, so that over all loci locus_fpkm adds up to the total TPM divides by
+ *                   (not to its bits: the order differs);
+ *    locus_kept[l]  the number of those isoforms (int32);
+ *    locus_tpm[l]   = locus_kept[l] ? 1e6 * locus_fpkm[l] / total_fpkm : 0.0, the expression of sbgpu_tpm_device;
+ *    a locus without isoforms gives 0.0, 0, 0.0.
+ * Any output may be NULL.  SBGPU_EINVAL: n_loci < 0, NULL iso_off, offsets that decrease or start below 0, NULL fpkm / keep with
+ * isoforms present.  Host form: host arrays, no GPU needed.  Device form: device arrays -- the d_* arrays of
+ * sbgpu_quantify_resident's result as they stand, d_iso_off the caller's upload of the annotation's iso_off, d_total_fpkm one
+ * double on the device (needed for d_locus_tpm only) --, not checked beyond NULL; one launch, asynchronous on `stream`.        */
+int sbgpu_locus_abundance_host(int64_t n_loci, const int64_t *iso_off, const double *fpkm, const int32_t *keep, double total_fpkm,
+                               double *locus_fpkm, double *locus_tpm, int32_t *locus_kept);
+int sbgpu_locus_abundance_device(sbgpu_ctx_t *ctx, int64_t n_loci, const int64_t *d_iso_off, const double *d_fpkm, const int32_t *d_keep,
+                                 const double *d_total_fpkm, double *d_locus_fpkm, double *d_locus_tpm, int32_t *d_locus_kept, void *stream);
+/* sbgpu_abundance_bootstrap_device, and beside it the replicates' Frac and the loci's abundances.  Preconditions, argument
+ * checks, the n_rep <= 1024 cap, the replicates, the ONE all-reduce of the n_rep totals, schedule independence and "returns
+ * synchronised" are that call's; what it fills in `out` (may be NULL here) is bit for bit what that call fills for the same
+ * arguments.  A NULL `locus_out`: SBGPU_EINVAL.  It also keeps, per replicate k:
+ *    frac_rep[k][j]        the Frac abundance_kernel wrote for replicate k: the bits of sbgpu_abundance_device's d_frac on that
+ *                          replicate's theta and status under the retained parameters (an INIT_EMPTY locus: 0.0; an "NA"
+ *                          isoform: 0.0; a locus whose FPKM are all zero: what the kernel gives, NaN);
+ *    locus_fpkm_rep[k][l], locus_kept_rep[k][l]   the rule above on row k of fpkm_rep / keep_rep (one more small kernel behind the
+ *                          replicate's epilogue).
+ * After the totals' all-reduce the statistics of sbgpu_replicate_stats_device run at rank_lo / rank_hi over the columns of
+ *    frac_*        x_k = frac_rep[k][j], whatever keep says (a NaN sorts last);
+ *    locus_fpkm_*  x_k = locus_fpkm_rep[k][l];
+ *    locus_tpm_*   x_k = locus_kept_rep[k][l] ? 1e6 * locus_fpkm_rep[k][l] / total[k] : 0.0 (made while staging: no locus-TPM matrix
+ *                  is written), and locus_kept_count[l] = the number of k with locus_kept_rep[k][l] != 0.
+ * A locus lives on one rank: no collective beyond the totals'.  The struct: host arrays to fill (any may be NULL) and, on return,
+ * the device arrays of all of them, in the same pooled block as `out`'s (valid until the context's next bootstrap or
+ * sbgpu_quantify_* call).  On top of sbgpu_abundance_bootstrap_device's footprint the block takes n_rep * (8 n_iso + 12 n_loci)
+ * bytes for the three matrices (and 32 n_iso + 68 n_loci for the statistics); it is allocated before the first kernel:
+ * SBGPU_ENOMEM when it does not fit.                                                                                         */
+typedef struct {
+   double *frac_mean, *frac_var, *frac_lo, *frac_hi;                         /* in: host [n_iso], or NULL  */
+   double *locus_fpkm_mean, *locus_fpkm_var, *locus_fpkm_lo, *locus_fpkm_hi; /* in: host [n_loci], or NULL */
+   double *locus_tpm_mean, *locus_tpm_var, *locus_tpm_lo, *locus_tpm_hi;     /* in: host [n_loci], or NULL */
+   int32_t *locus_kept_count;                           /* in: host [n_loci], or NULL: replicates with a kept isoform      */
+   double *frac_rep;                                    /* in: host [n_rep][n_iso], or NULL: every replicate's Frac          */
+   double *locus_fpkm_rep;                              /* in: host [n_rep][n_loci], or NULL                               */
+   int32_t *locus_kept_rep;                             /* in: host [n_rep][n_loci], or NULL                               */
+   const double *d_frac_mean, *d_frac_var, *d_frac_lo, *d_frac_hi;                         /* out: device [n_iso]  */
+   const double *d_locus_fpkm_mean, *d_locus_fpkm_var, *d_locus_fpkm_lo, *d_locus_fpkm_hi; /* out: device [n_loci] */
+   const double *d_locus_tpm_mean, *d_locus_tpm_var, *d_locus_tpm_lo, *d_locus_tpm_hi;     /* out: device [n_loci] */
+   const int32_t *d_locus_kept_count;                   /* out: device [n_loci]                                            */
+   const double *d_frac_rep;                            /* out: device [n_rep][n_iso]                                      */
+   const double *d_locus_fpkm_rep;                      /* out: device [n_rep][n_loci]                                     */
+   const int32_t *d_locus_kept_rep;                     /* out: device [n_rep][n_loci]                                     */
+   int64_t n_iso, n_loci;                               /* out */
+   int32_t n_rep, reserved;                             /* out */
+} sbgpu_locus_bootstrap_t;
+int sbgpu_locus_bootstrap_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins, const sbgpu_bootstrap_params_t *params,
+                                 int32_t rank_lo, int32_t rank_hi, int32_t keep_theta_rep, sbgpu_comm_t *comm, void *stream,
+                                 sbgpu_abundance_bootstrap_t *out, sbgpu_locus_bootstrap_t *locus_out);
+
 /* ---- per-bin sequence statistics ---------------------------------------
  * What the reference's "bias" option (-b genome.fa) adds to the `-f` table and nothing else
  * (src/bias.cpp holds no code): for every exon bin, over the bases of its segments concatenated

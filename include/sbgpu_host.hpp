@@ -688,5 +688,88 @@ class AbundanceBootstrap {
    }
 };
 
+/* Abundances per locus (a locus is the reference's gene): sbgpu_locus_abundance_host on one abundance vector -- the sum of the
+ * kept isoforms' FPKM in isoform order, the number of kept isoforms, and 1e6 * sum / total_fpkm (0.0 where nothing is kept).  */
+struct LocusAbundance {
+   std::vector<double> fpkm, tpm; /* [n_loci] */
+   std::vector<int32_t> kept;     /* [n_loci] */
+};
+inline LocusAbundance locus_abundance(const std::vector<int64_t> &iso_off, const double *fpkm, const int32_t *keep, double total_fpkm)
+{
+   if (iso_off.empty()) throw std::invalid_argument("locus_abundance: iso_off holds n_loci + 1 offsets");
+   const size_t nl = iso_off.size() - 1;
+   LocusAbundance r;
+   r.fpkm.assign(nl + 1, 0.0), r.tpm.assign(nl + 1, 0.0), r.kept.assign(nl + 1, 0);
+   check(sbgpu_locus_abundance_host((int64_t)nl, iso_off.data(), fpkm, keep, total_fpkm, r.fpkm.data(), r.tpm.data(), r.kept.data()),
+         "sbgpu_locus_abundance_host");
+   r.fpkm.resize(nl), r.tpm.resize(nl), r.kept.resize(nl);
+   return r;
+}
+
+/* sbgpu_locus_bootstrap_device: AbundanceBootstrap's results (`iso`, bit for bit that call's) and beside them mean, variance and
+ * interval of Frac per isoform and of FPKM / TPM per locus, with the replicates in which each locus kept an isoform.           */
+class LocusBootstrap {
+ public:
+   AbundanceBootstrap iso;
+   std::vector<double> frac_mean, frac_var, frac_lo, frac_hi;                         /* [n_iso]  */
+   std::vector<double> locus_fpkm_mean, locus_fpkm_var, locus_fpkm_lo, locus_fpkm_hi; /* [n_loci] */
+   std::vector<double> locus_tpm_mean, locus_tpm_var, locus_tpm_lo, locus_tpm_hi;     /* [n_loci] */
+   std::vector<int32_t> locus_kept_count; /* [n_loci] */
+   std::vector<double> frac_rep;          /* [n_rep][n_iso], with keep_replicates  */
+   std::vector<double> locus_fpkm_rep;    /* [n_rep][n_loci], with keep_replicates */
+   std::vector<int32_t> locus_kept_rep;   /* [n_rep][n_loci], with keep_replicates */
+   sbgpu_locus_bootstrap_t raw{};         /* the device arrays: the context's, valid until its next bootstrap or quantify call */
+
+   static LocusBootstrap device(const Context &ctx, const sbgpu_bins_t *bins, int32_t n_rep, uint64_t seed, int32_t rank_lo, int32_t rank_hi,
+                                int32_t rep_first = 0, const int64_t *locus_id = nullptr, bool keep_theta_rep = false,
+                                sbgpu_comm_t *comm = nullptr, void *stream = nullptr, bool keep_replicates = false)
+   {
+      LocusBootstrap b;
+      int64_t info[8];
+      check(sbgpu_bins_info(bins, info), "sbgpu_bins_info");
+      const size_t ni = (size_t)info[1] + 1, nl = (size_t)info[0] + 1;
+      sbgpu_abundance_bootstrap_t &o = b.iso.raw;
+      std::vector<double> *stat[10] = {&b.iso.theta_mean, &b.iso.theta_var, &b.iso.fpkm_mean, &b.iso.fpkm_var, &b.iso.fpkm_lo, &b.iso.fpkm_hi,
+                                       &b.iso.tpm_mean, &b.iso.tpm_var, &b.iso.tpm_lo, &b.iso.tpm_hi};
+      double **slot[10] = {&o.theta_mean, &o.theta_var, &o.fpkm_mean, &o.fpkm_var, &o.fpkm_lo, &o.fpkm_hi, &o.tpm_mean, &o.tpm_var, &o.tpm_lo, &o.tpm_hi};
+      for (int i = 0; i < 10; ++i) {
+         stat[i]->assign(ni, 0.0);
+         *slot[i] = stat[i]->data();
+      }
+      b.iso.keep_count.assign(ni, 0), b.iso.status_count.assign(nl * 4, 0), b.iso.total_fpkm_rep.assign((size_t)(n_rep > 0 ? n_rep : 1), 0.0);
+      o.keep_count = b.iso.keep_count.data(), o.status_count = b.iso.status_count.data(), o.total_fpkm_rep = b.iso.total_fpkm_rep.data();
+      sbgpu_locus_bootstrap_t &l = b.raw;
+      std::vector<double> *lstat[12] = {&b.frac_mean, &b.frac_var, &b.frac_lo, &b.frac_hi, &b.locus_fpkm_mean, &b.locus_fpkm_var, &b.locus_fpkm_lo,
+                                        &b.locus_fpkm_hi, &b.locus_tpm_mean, &b.locus_tpm_var, &b.locus_tpm_lo, &b.locus_tpm_hi};
+      double **lslot[12] = {&l.frac_mean, &l.frac_var, &l.frac_lo, &l.frac_hi, &l.locus_fpkm_mean, &l.locus_fpkm_var, &l.locus_fpkm_lo,
+                            &l.locus_fpkm_hi, &l.locus_tpm_mean, &l.locus_tpm_var, &l.locus_tpm_lo, &l.locus_tpm_hi};
+      for (int i = 0; i < 12; ++i) {
+         lstat[i]->assign(i < 4 ? ni : nl, 0.0);
+         *lslot[i] = lstat[i]->data();
+      }
+      b.locus_kept_count.assign(nl, 0);
+      l.locus_kept_count = b.locus_kept_count.data();
+      if (keep_replicates && n_rep > 0) {
+         if (info[1] > 0) {
+            b.iso.fpkm_rep.assign((size_t)n_rep * (size_t)info[1], 0.0), b.iso.keep_rep.assign((size_t)n_rep * (size_t)info[1], 0);
+            b.frac_rep.assign((size_t)n_rep * (size_t)info[1], 0.0);
+            o.fpkm_rep = b.iso.fpkm_rep.data(), o.keep_rep = b.iso.keep_rep.data(), l.frac_rep = b.frac_rep.data();
+         }
+         if (info[0] > 0) {
+            b.locus_fpkm_rep.assign((size_t)n_rep * (size_t)info[0], 0.0), b.locus_kept_rep.assign((size_t)n_rep * (size_t)info[0], 0);
+            l.locus_fpkm_rep = b.locus_fpkm_rep.data(), l.locus_kept_rep = b.locus_kept_rep.data();
+         }
+      }
+      const sbgpu_bootstrap_params_t par = {n_rep, rep_first, seed, locus_id};
+      check(sbgpu_locus_bootstrap_device(ctx.get(), bins, &par, rank_lo, rank_hi, keep_theta_rep ? 1 : 0, comm, stream, &o, &l),
+            "sbgpu_locus_bootstrap_device");
+      for (int i = 0; i < 10; ++i) stat[i]->resize(ni - 1);
+      for (int i = 0; i < 12; ++i) lstat[i]->resize((i < 4 ? ni : nl) - 1);
+      b.iso.keep_count.resize(ni - 1), b.iso.status_count.resize((nl - 1) * 4), b.locus_kept_count.resize(nl - 1);
+      b.iso.rank_lo = rank_lo, b.iso.rank_hi = rank_hi;
+      return b;
+   }
+};
+
 } // namespace sbgpu
 #endif /* SBGPU_HOST_HPP_ */

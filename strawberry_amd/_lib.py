@@ -44,6 +44,7 @@ SYMBOLS = [
     "sbgpu_context_table_host", "sbgpu_context_table_keep", "sbgpu_context_table_device",
     "sbgpu_bootstrap_counts_host", "sbgpu_bootstrap_counts_device", "sbgpu_em_bootstrap_device",
     "sbgpu_replicate_stats_host", "sbgpu_replicate_stats_device", "sbgpu_bootstrap_keep", "sbgpu_abundance_bootstrap_device",
+    "sbgpu_locus_abundance_host", "sbgpu_locus_abundance_device", "sbgpu_locus_bootstrap_device",
 ]
 
 
@@ -159,6 +160,14 @@ class sbgpu_abundance_bootstrap_t(C.Structure):
                                            "d_theta_mean", "d_theta_var", "d_fpkm_mean", "d_fpkm_var", "d_fpkm_lo", "d_fpkm_hi", "d_tpm_mean",
                                            "d_tpm_var", "d_tpm_lo", "d_tpm_hi", "d_keep_count", "d_status_count", "d_total_fpkm_rep",
                                            "d_fpkm_rep", "d_keep_rep", "d_theta_rep")] +
+                [("n_iso", C.c_int64), ("n_loci", C.c_int64), ("n_rep", C.c_int32), ("reserved", C.c_int32)])
+
+
+class sbgpu_locus_bootstrap_t(C.Structure):
+    _NAMES = ("frac_mean", "frac_var", "frac_lo", "frac_hi", "locus_fpkm_mean", "locus_fpkm_var", "locus_fpkm_lo", "locus_fpkm_hi",
+              "locus_tpm_mean", "locus_tpm_var", "locus_tpm_lo", "locus_tpm_hi", "locus_kept_count", "frac_rep", "locus_fpkm_rep",
+              "locus_kept_rep")
+    _fields_ = ([(n, C.c_void_p) for n in _NAMES] + [("d_" + n, C.c_void_p) for n in _NAMES] +
                 [("n_iso", C.c_int64), ("n_loci", C.c_int64), ("n_rep", C.c_int32), ("reserved", C.c_int32)])
 
 
@@ -328,6 +337,10 @@ def load():
     L.sbgpu_bootstrap_keep.argtypes = [vp, C.c_int32]
     L.sbgpu_abundance_bootstrap_device.argtypes = [vp, vp, C.POINTER(sbgpu_bootstrap_params_t), C.c_int32, C.c_int32, C.c_int32, vp, vp,
                                                    C.POINTER(sbgpu_abundance_bootstrap_t)]
+    L.sbgpu_locus_abundance_host.argtypes = [C.c_int64, vp, vp, vp, C.c_double, vp, vp, vp]
+    L.sbgpu_locus_abundance_device.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.sbgpu_locus_bootstrap_device.argtypes = [vp, vp, C.POINTER(sbgpu_bootstrap_params_t), C.c_int32, C.c_int32, C.c_int32, vp, vp,
+                                               C.POINTER(sbgpu_abundance_bootstrap_t), C.POINTER(sbgpu_locus_bootstrap_t)]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("sbgpu_device_count", "sbgpu_plan_classes"):

@@ -333,12 +333,23 @@ class ChainQuantifier:
 
     def abundance_bootstrap(self, n_rep, seed, **kw):
         """The bootstrap of the last step (keep_bootstrap=True): bootstrap.abundance_bootstrap_device on its handle, over this
-        object's communicator -> its dict (FPKM / TPM mean, variance, interval; keep and status counts)."""
+        object's communicator -> its dict (FPKM / TPM mean, variance, interval; keep and status counts; locus=True: also Frac's
+        and the loci's, sbgpu_locus_bootstrap_device)."""
         from . import bootstrap
         if self.context_handle is None or not self.keep_bootstrap:
             raise _lib.SbgpuError("abundance_bootstrap: no step has run with keep_bootstrap=True")
         kw.setdefault("comm", self.comm)
         return bootstrap.abundance_bootstrap_device(self.ctx, self.context_handle, n_rep, seed, **kw)
+
+    def locus_abundance(self):
+        """Abundances per locus of the last resident step (bootstrap.locus_abundance_device on the device arrays the call left:
+        valid until the context's next quantify call) -> dict(fpkm, tpm [n_loci] float64, kept [n_loci] int32) of host arrays."""
+        from . import bootstrap
+        if not self.resident or not self._out.d_fpkm:
+            raise _lib.SbgpuError("locus_abundance: no resident step has run")
+        r = bootstrap.locus_abundance_device(self.ctx, self.annot.iso_off, int(self._out.d_fpkm), int(self._out.d_keep), self.total_fpkm)
+        self.torch.cuda.current_stream(self.dev).synchronize()
+        return {k: v.cpu().numpy() for k, v in r.items()}
 
     def set_law(self, insert):
         """Quantify under a GIVEN insert-size law from now on (an InsertSize: -i mean/sd, or an empirical law made elsewhere)."""

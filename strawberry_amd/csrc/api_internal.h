@@ -265,6 +265,7 @@ ContextKeep *ctx_context_keep(sbgpu_ctx_t *ctx);
 struct PlanShape {
    int64_t n_loci = 0, n_rows = 0, n_iso = 0;
    const int64_t *d_row_off = nullptr; // device, [n_loci + 1]
+   const int64_t *d_iso_off = nullptr; // device, [n_loci + 1]
 };
 PlanShape plan_shape(const sbgpu_plan_t *plan);
 // The bootstrap's working set: one block from the pool (sb::dev_take) that stays with the context -- the call is asynchronous, and

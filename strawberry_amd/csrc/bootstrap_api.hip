@@ -1,6 +1,7 @@
 // strawberry_amd/csrc/bootstrap_api.hip -- sbgpu_bootstrap_counts_device / sbgpu_em_bootstrap_device, and the bootstrap of the
-// resident path: sbgpu_bootstrap_keep / sbgpu_abundance_bootstrap_device / sbgpu_replicate_stats_device (include/sbgpu.h):
-// the EM bootstrap on the device (bootstrap_device.h).  Replicates' counts by the rule of bootstrap_rules.h, the
+// resident path: sbgpu_bootstrap_keep / sbgpu_abundance_bootstrap_device / sbgpu_replicate_stats_device, and per locus
+// sbgpu_locus_abundance_device / sbgpu_locus_bootstrap_device (include/sbgpu.h): the EM bootstrap on the device
+// (bootstrap_device.h).  Replicates' counts by the rule of bootstrap_rules.h, the
 // existing EM entry replicate after replicate, Welford's recurrence over the replicates' theta.
 #include <hip/hip_runtime.h>
 
@@ -228,6 +229,183 @@ int check_ranks(const char *who, int32_t n_rep, int32_t rank_lo, int32_t rank_hi
    return SBGPU_OK;
 }
 
+// sbgpu_abundance_bootstrap_device (`loc` null) and sbgpu_locus_bootstrap_device (`loc` set): one body, so that what `out` gets
+// cannot differ between the two.  With `loc` the result block grows behind its old end -- every old array keeps its place --, the
+// epilogue writes Frac into row k of frac_rep instead of the one-row scratch, boot_locus_sum_kernel follows it on the join
+// stream, and three more statistics passes run behind the old two.
+int abundance_bootstrap(const char *who, sbgpu_ctx_t *c, const sbgpu_bins_t *bins, const sbgpu_bootstrap_params_t *params, int32_t rank_lo, int32_t rank_hi,
+                        int32_t keep_theta_rep, sbgpu_comm_t *comm, void *stream, sbgpu_abundance_bootstrap_t *out, sbgpu_locus_bootstrap_t *loc)
+{
+   if (const int rc = check_params(who, params); rc != SBGPU_OK) return rc;
+   if (!c || !bins || !out) return api_fail(SBGPU_EINVAL, std::string(who) + ": null argument");
+   if (const int rc = check_ranks(who, params->n_rep, rank_lo, rank_hi); rc != SBGPU_OK) return rc;
+   const sb::BootKeep *rec = sb::ctx_boot_keep(c);
+   const sb::BinsContextView v = sb::bins_context_view(bins);
+   if (!v.boot_serial)
+      return api_fail(SBGPU_EINVAL, std::string(who) + ": this handle was made without retention (sbgpu_bootstrap_keep was off for its call, or it is not "
+                                                       "from sbgpu_quantify_resident / sbgpu_front_stream_end)");
+   if (v.boot_serial != rec->serial || !rec->plan)
+      return api_fail(SBGPU_EINVAL, std::string(who) + ": a stale handle: a later call on this context (sbgpu_quantify_*, or another entry that works in the "
+                                                       "context's scratch) has reused what its call kept");
+   const sb::PlanShape ps = sb::plan_shape(rec->plan);
+   const int64_t nl = ps.n_loci, n_iso = ps.n_iso;
+   if (nl != v.n_loci || n_iso != v.n_iso || nl != rec->n_loci || n_iso != rec->n_iso) return api_fail(SBGPU_EINVAL, std::string(who) + ": the handle and the context's record disagree");
+   const int32_t B = params->n_rep;
+   hipStream_t s = stream ? (hipStream_t)stream : sb::ctx_stream(c);
+   if (hipError_t e = hipSetDevice(sb::ctx_device(c)); e != hipSuccess) return api_fail_hip(e, "hipSetDevice");
+   // ---- the results' block, before any kernel: [ten statistics | frac of one replicate | totals | keep and status counts | the replicates' matrices]
+   const size_t ni = (size_t)std::max<int64_t>(n_iso, 1), col = up256(ni * 8);
+   size_t off = 0;
+   auto take = [&off](size_t bytes) {
+      const size_t at = off;
+      off += up256(bytes);
+      return at;
+   };
+   size_t o_stat[10];
+   for (size_t &o : o_stat) o = take(col);
+   const size_t o_frac = take(col), o_total = take((size_t)B * 8), o_keep_count = take(ni * 4), o_status_count = take((size_t)nl * 16);
+   const size_t o_fpkm_rep = take((size_t)B * ni * 8), o_keep_rep = take((size_t)B * ni * 4);
+   const size_t o_theta_rep = keep_theta_rep ? take((size_t)B * ni * 8) : 0;
+   // (the locus call's additions: four Frac statistics, eight locus statistics, the kept replicates' count, the three matrices)
+   const size_t nlc = (size_t)std::max<int64_t>(nl, 1), lcol = up256(nlc * 8);
+   size_t o_fstat[4] = {0, 0, 0, 0}, o_lstat[8] = {0, 0, 0, 0, 0, 0, 0, 0}, o_lkept_count = 0, o_frac_rep = 0, o_lfpkm_rep = 0, o_lkept_rep = 0;
+   if (loc) {
+      for (size_t &o : o_fstat) o = take(col);
+      for (size_t &o : o_lstat) o = take(lcol);
+      o_lkept_count = take(nlc * 4);
+      o_frac_rep = take((size_t)B * ni * 8), o_lfpkm_rep = take((size_t)B * nlc * 8), o_lkept_rep = take((size_t)B * nlc * 4);
+   }
+   char *d = nullptr;
+   if (hipError_t e = sb::ctx_boot_result(c, off, &d); e != hipSuccess) return api_fail_hip(e, "hipMalloc(the replicates' FPKM and keep matrices)");
+   double *stat[10];
+   for (int i = 0; i < 10; ++i) stat[i] = (double *)(d + o_stat[i]);
+   double *d_theta_mean = stat[0], *d_theta_var = stat[1], *d_fpkm_mean = stat[2], *d_fpkm_var = stat[3], *d_fpkm_lo = stat[4], *d_fpkm_hi = stat[5];
+   double *d_tpm_mean = stat[6], *d_tpm_var = stat[7], *d_tpm_lo = stat[8], *d_tpm_hi = stat[9];
+   double *d_frac = (double *)(d + o_frac), *d_total = (double *)(d + o_total), *d_fpkm_rep = (double *)(d + o_fpkm_rep);
+   int32_t *d_keep_count = (int32_t *)(d + o_keep_count), *d_status_count = (int32_t *)(d + o_status_count), *d_keep_rep = (int32_t *)(d + o_keep_rep);
+   double *d_theta_rep = keep_theta_rep ? (double *)(d + o_theta_rep) : nullptr;
+   double *fstat[4] = {nullptr, nullptr, nullptr, nullptr}, *lstat[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+   double *d_frac_rep = nullptr, *d_lfpkm_rep = nullptr;
+   int32_t *d_lkept_count = nullptr, *d_lkept_rep = nullptr;
+   if (loc) {
+      for (int i = 0; i < 4; ++i) fstat[i] = (double *)(d + o_fstat[i]);
+      for (int i = 0; i < 8; ++i) lstat[i] = (double *)(d + o_lstat[i]);
+      d_lkept_count = (int32_t *)(d + o_lkept_count), d_lkept_rep = (int32_t *)(d + o_lkept_rep);
+      d_frac_rep = (double *)(d + o_frac_rep), d_lfpkm_rep = (double *)(d + o_lfpkm_rep);
+   }
+#define SB_TRY(expr)                                    \
+   do {                                                 \
+      hipError_t e_ = (expr);                           \
+      if (e_ != hipSuccess) {                           \
+         (void)hipStreamSynchronize(s);                 \
+         return api_fail_hip(e_, #expr);                \
+      }                                                 \
+   } while (0)
+   // ---- the replicates: behind each one's statistics step, the reference's epilogue on its theta and status -- FPKM and keep into
+   // row k of the matrices, this rank's kept-FPKM sum into d_total[k].  The mapped-read total and the insert law are the sample's.
+   const sbgpu_abundance_params_t par = rec->params;
+   const sbgpu_plan_t *plan = rec->plan;
+   const int32_t *d_len = rec->d_iso_len;
+   const AfterStats epilogue = [&](int32_t k, const double *d_theta, const int32_t *d_status, hipStream_t js) {
+      double *row_fpkm = d_fpkm_rep + (size_t)k * (size_t)n_iso;
+      int32_t *row_keep = d_keep_rep + (size_t)k * (size_t)n_iso;
+      if (const int rc = sbgpu_abundance_device(c, plan, d_theta, d_status, d_len, &par, row_fpkm, loc ? d_frac_rep + (size_t)k * (size_t)n_iso : d_frac,
+                                                row_keep, d_total + k, js);
+          rc != SBGPU_OK || !loc)
+         return rc;
+      // the loci's sums of this replicate's row, behind its epilogue
+      sb::BootLocusSumArgs la{};
+      la.n_loci = nl, la.n_iso = n_iso, la.n_rows = 1, la.iso_off = ps.d_iso_off, la.fpkm = row_fpkm, la.keep = row_keep;
+      la.locus_fpkm = d_lfpkm_rep + (size_t)k * (size_t)nl, la.locus_kept = d_lkept_rep + (size_t)k * (size_t)nl;
+      hipLaunchKernelGGL(sb::boot_locus_sum_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, js, la);
+      if (hipError_t e = hipGetLastError(); e != hipSuccess) return api_fail_hip(e, "boot_locus_sum_kernel");
+      return (int)SBGPU_OK;
+   };
+   if (const int rc = run_replicates(c, who, plan, rec->d_count, rec->d_F, params, d_theta_mean, d_theta_var, d_status_count, d_theta_rep, nullptr, nullptr, s,
+                                     epilogue);
+       rc != SBGPU_OK)
+      return rc;
+   // ---- the total TPM divides by: ONE collective per call, over all replicates
+   if (comm) {
+      if (const int rc = sbgpu_allreduce_sum_f64(comm, d_total, B, s); rc != SBGPU_OK) {
+         (void)hipStreamSynchronize(s);
+         return rc;
+      }
+   }
+   // ---- the replicates' statistics, twice over the columns: the raw FPKM; the TPM (made while staging) with the kept replicates' count
+   SB_TRY(hipMemsetAsync(d_keep_count, 0, ni * 4, s));
+   sb::BootIntervalArgs a{};
+   a.n = n_iso, a.n_rep = B, a.rank_lo = rank_lo, a.rank_hi = rank_hi, a.x = d_fpkm_rep;
+   a.mean = d_fpkm_mean, a.var = d_fpkm_var, a.lo = d_fpkm_lo, a.hi = d_fpkm_hi;
+   if (const int rc = launch_interval(a, s); rc != SBGPU_OK) {
+      (void)hipStreamSynchronize(s);
+      return rc;
+   }
+   a.keep = d_keep_rep, a.total = d_total, a.keep_count = d_keep_count;
+   a.mean = d_tpm_mean, a.var = d_tpm_var, a.lo = d_tpm_lo, a.hi = d_tpm_hi;
+   if (const int rc = launch_interval(a, s); rc != SBGPU_OK) {
+      (void)hipStreamSynchronize(s);
+      return rc;
+   }
+   // ---- the locus call's three passes: Frac as it stands; the loci's FPKM; the loci's TPM (made while staging, the loci's kept
+   // counts as the flag) with the count of the replicates that kept an isoform of the locus
+   if (loc) {
+      SB_TRY(hipMemsetAsync(d_lkept_count, 0, nlc * 4, s));
+      sb::BootIntervalArgs f{};
+      f.n = n_iso, f.n_rep = B, f.rank_lo = rank_lo, f.rank_hi = rank_hi, f.x = d_frac_rep;
+      f.mean = fstat[0], f.var = fstat[1], f.lo = fstat[2], f.hi = fstat[3];
+      int rc = launch_interval(f, s);
+      f.n = nl, f.x = d_lfpkm_rep;
+      f.mean = lstat[0], f.var = lstat[1], f.lo = lstat[2], f.hi = lstat[3];
+      if (rc == SBGPU_OK) rc = launch_interval(f, s);
+      f.keep = d_lkept_rep, f.total = d_total, f.keep_count = d_lkept_count;
+      f.mean = lstat[4], f.var = lstat[5], f.lo = lstat[6], f.hi = lstat[7];
+      if (rc == SBGPU_OK) rc = launch_interval(f, s);
+      if (rc != SBGPU_OK) {
+         (void)hipStreamSynchronize(s);
+         return rc;
+      }
+   }
+   // ---- what was asked for comes down; the call returns synchronised
+   auto get = [&](void *dst, const void *src, size_t bytes) { return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess; };
+   double *const host_stat[10] = {out->theta_mean, out->theta_var, out->fpkm_mean, out->fpkm_var, out->fpkm_lo, out->fpkm_hi, out->tpm_mean, out->tpm_var, out->tpm_lo, out->tpm_hi};
+   for (int i = 0; i < 10; ++i) SB_TRY(get(host_stat[i], stat[i], (size_t)n_iso * 8));
+   SB_TRY(get(out->keep_count, d_keep_count, (size_t)n_iso * 4));
+   SB_TRY(get(out->status_count, d_status_count, (size_t)nl * 16));
+   SB_TRY(get(out->total_fpkm_rep, d_total, (size_t)B * 8));
+   SB_TRY(get(out->fpkm_rep, d_fpkm_rep, (size_t)B * (size_t)n_iso * 8));
+   SB_TRY(get(out->keep_rep, d_keep_rep, (size_t)B * (size_t)n_iso * 4));
+   if (d_theta_rep) SB_TRY(get(out->theta_rep, d_theta_rep, (size_t)B * (size_t)n_iso * 8));
+   if (loc) {
+      double *const host_f[4] = {loc->frac_mean, loc->frac_var, loc->frac_lo, loc->frac_hi};
+      double *const host_l[8] = {loc->locus_fpkm_mean, loc->locus_fpkm_var, loc->locus_fpkm_lo, loc->locus_fpkm_hi,
+                                 loc->locus_tpm_mean, loc->locus_tpm_var, loc->locus_tpm_lo, loc->locus_tpm_hi};
+      for (int i = 0; i < 4; ++i) SB_TRY(get(host_f[i], fstat[i], (size_t)n_iso * 8));
+      for (int i = 0; i < 8; ++i) SB_TRY(get(host_l[i], lstat[i], (size_t)nl * 8));
+      SB_TRY(get(loc->locus_kept_count, d_lkept_count, (size_t)nl * 4));
+      SB_TRY(get(loc->frac_rep, d_frac_rep, (size_t)B * (size_t)n_iso * 8));
+      SB_TRY(get(loc->locus_fpkm_rep, d_lfpkm_rep, (size_t)B * (size_t)nl * 8));
+      SB_TRY(get(loc->locus_kept_rep, d_lkept_rep, (size_t)B * (size_t)nl * 4));
+   }
+   SB_TRY(hipStreamSynchronize(s));
+#undef SB_TRY
+   if (sb::ctx_take_wide_error(c)) return api_fail(SBGPU_EHIP, std::string(who) + ": a barrier of the wide-locus EM kernel timed out: the loci it served have no result");
+   out->n_rep = B, out->n_iso = n_iso, out->n_loci = nl;
+   out->d_theta_mean = d_theta_mean, out->d_theta_var = d_theta_var;
+   out->d_fpkm_mean = d_fpkm_mean, out->d_fpkm_var = d_fpkm_var, out->d_fpkm_lo = d_fpkm_lo, out->d_fpkm_hi = d_fpkm_hi;
+   out->d_tpm_mean = d_tpm_mean, out->d_tpm_var = d_tpm_var, out->d_tpm_lo = d_tpm_lo, out->d_tpm_hi = d_tpm_hi;
+   out->d_keep_count = d_keep_count, out->d_status_count = d_status_count, out->d_total_fpkm_rep = d_total;
+   out->d_fpkm_rep = d_fpkm_rep, out->d_keep_rep = d_keep_rep, out->d_theta_rep = d_theta_rep;
+   if (loc) {
+      loc->n_rep = B, loc->n_iso = n_iso, loc->n_loci = nl, loc->reserved = 0;
+      loc->d_frac_mean = fstat[0], loc->d_frac_var = fstat[1], loc->d_frac_lo = fstat[2], loc->d_frac_hi = fstat[3];
+      loc->d_locus_fpkm_mean = lstat[0], loc->d_locus_fpkm_var = lstat[1], loc->d_locus_fpkm_lo = lstat[2], loc->d_locus_fpkm_hi = lstat[3];
+      loc->d_locus_tpm_mean = lstat[4], loc->d_locus_tpm_var = lstat[5], loc->d_locus_tpm_lo = lstat[6], loc->d_locus_tpm_hi = lstat[7];
+      loc->d_locus_kept_count = d_lkept_count, loc->d_frac_rep = d_frac_rep, loc->d_locus_fpkm_rep = d_lfpkm_rep, loc->d_locus_kept_rep = d_lkept_rep;
+   }
+   return SBGPU_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -302,108 +480,33 @@ int sbgpu_bootstrap_keep(sbgpu_ctx_t *c, int32_t on)
 int sbgpu_abundance_bootstrap_device(sbgpu_ctx_t *c, const sbgpu_bins_t *bins, const sbgpu_bootstrap_params_t *params, int32_t rank_lo, int32_t rank_hi,
                                      int32_t keep_theta_rep, sbgpu_comm_t *comm, void *stream, sbgpu_abundance_bootstrap_t *out)
 {
-   const char *who = "sbgpu_abundance_bootstrap_device";
-   if (const int rc = check_params(who, params); rc != SBGPU_OK) return rc;
-   if (!c || !bins || !out) return api_fail(SBGPU_EINVAL, std::string(who) + ": null argument");
-   if (const int rc = check_ranks(who, params->n_rep, rank_lo, rank_hi); rc != SBGPU_OK) return rc;
-   const sb::BootKeep *rec = sb::ctx_boot_keep(c);
-   const sb::BinsContextView v = sb::bins_context_view(bins);
-   if (!v.boot_serial)
-      return api_fail(SBGPU_EINVAL, std::string(who) + ": this handle was made without retention (sbgpu_bootstrap_keep was off for its call, or it is not "
-                                                       "from sbgpu_quantify_resident / sbgpu_front_stream_end)");
-   if (v.boot_serial != rec->serial || !rec->plan)
-      return api_fail(SBGPU_EINVAL, std::string(who) + ": a stale handle: a later call on this context (sbgpu_quantify_*, or another entry that works in the "
-                                                       "context's scratch) has reused what its call kept");
-   const sb::PlanShape ps = sb::plan_shape(rec->plan);
-   const int64_t nl = ps.n_loci, n_iso = ps.n_iso;
-   if (nl != v.n_loci || n_iso != v.n_iso || nl != rec->n_loci || n_iso != rec->n_iso) return api_fail(SBGPU_EINVAL, std::string(who) + ": the handle and the context's record disagree");
-   const int32_t B = params->n_rep;
-   hipStream_t s = stream ? (hipStream_t)stream : sb::ctx_stream(c);
+   return abundance_bootstrap("sbgpu_abundance_bootstrap_device", c, bins, params, rank_lo, rank_hi, keep_theta_rep, comm, stream, out, nullptr);
+}
+
+int sbgpu_locus_bootstrap_device(sbgpu_ctx_t *c, const sbgpu_bins_t *bins, const sbgpu_bootstrap_params_t *params, int32_t rank_lo, int32_t rank_hi,
+                                 int32_t keep_theta_rep, sbgpu_comm_t *comm, void *stream, sbgpu_abundance_bootstrap_t *out, sbgpu_locus_bootstrap_t *locus_out)
+{
+   const char *who = "sbgpu_locus_bootstrap_device";
+   if (!locus_out) return api_fail(SBGPU_EINVAL, std::string(who) + ": null locus_out");
+   sbgpu_abundance_bootstrap_t none{}; // (`out` may be NULL: nothing of it comes down then)
+   return abundance_bootstrap(who, c, bins, params, rank_lo, rank_hi, keep_theta_rep, comm, stream, out ? out : &none, locus_out);
+}
+
+int sbgpu_locus_abundance_device(sbgpu_ctx_t *c, int64_t n_loci, const int64_t *d_iso_off, const double *d_fpkm, const int32_t *d_keep,
+                                 const double *d_total_fpkm, double *d_locus_fpkm, double *d_locus_tpm, int32_t *d_locus_kept, void *stream)
+{
+   const char *who = "sbgpu_locus_abundance_device";
+   if (!c || n_loci < 0 || !d_iso_off) return api_fail(SBGPU_EINVAL, std::string(who) + ": null context or iso_off, or a negative locus count");
+   if (n_loci == 0) return SBGPU_OK;
+   if (n_loci > INT32_MAX) return api_fail(SBGPU_ESHAPE, std::string(who) + ": more than 2^31 - 1 loci");
+   if (!d_fpkm || !d_keep) return api_fail(SBGPU_EINVAL, std::string(who) + ": null fpkm or keep array");
+   if (d_locus_tpm && !d_total_fpkm) return api_fail(SBGPU_EINVAL, std::string(who) + ": the loci's TPM need the total FPKM");
    if (hipError_t e = hipSetDevice(sb::ctx_device(c)); e != hipSuccess) return api_fail_hip(e, "hipSetDevice");
-   // ---- the results' block, before any kernel: [ten statistics | frac of one replicate | totals | keep and status counts | the replicates' matrices]
-   const size_t ni = (size_t)std::max<int64_t>(n_iso, 1), col = up256(ni * 8);
-   size_t off = 0;
-   auto take = [&off](size_t bytes) {
-      const size_t at = off;
-      off += up256(bytes);
-      return at;
-   };
-   size_t o_stat[10];
-   for (size_t &o : o_stat) o = take(col);
-   const size_t o_frac = take(col), o_total = take((size_t)B * 8), o_keep_count = take(ni * 4), o_status_count = take((size_t)nl * 16);
-   const size_t o_fpkm_rep = take((size_t)B * ni * 8), o_keep_rep = take((size_t)B * ni * 4);
-   const size_t o_theta_rep = keep_theta_rep ? take((size_t)B * ni * 8) : 0;
-   char *d = nullptr;
-   if (hipError_t e = sb::ctx_boot_result(c, off, &d); e != hipSuccess) return api_fail_hip(e, "hipMalloc(the replicates' FPKM and keep matrices)");
-   double *stat[10];
-   for (int i = 0; i < 10; ++i) stat[i] = (double *)(d + o_stat[i]);
-   double *d_theta_mean = stat[0], *d_theta_var = stat[1], *d_fpkm_mean = stat[2], *d_fpkm_var = stat[3], *d_fpkm_lo = stat[4], *d_fpkm_hi = stat[5];
-   double *d_tpm_mean = stat[6], *d_tpm_var = stat[7], *d_tpm_lo = stat[8], *d_tpm_hi = stat[9];
-   double *d_frac = (double *)(d + o_frac), *d_total = (double *)(d + o_total), *d_fpkm_rep = (double *)(d + o_fpkm_rep);
-   int32_t *d_keep_count = (int32_t *)(d + o_keep_count), *d_status_count = (int32_t *)(d + o_status_count), *d_keep_rep = (int32_t *)(d + o_keep_rep);
-   double *d_theta_rep = keep_theta_rep ? (double *)(d + o_theta_rep) : nullptr;
-#define SB_TRY(expr)                                    \
-   do {                                                 \
-      hipError_t e_ = (expr);                           \
-      if (e_ != hipSuccess) {                           \
-         (void)hipStreamSynchronize(s);                 \
-         return api_fail_hip(e_, #expr);                \
-      }                                                 \
-   } while (0)
-   // ---- the replicates: behind each one's statistics step, the reference's epilogue on its theta and status -- FPKM and keep into
-   // row k of the matrices, this rank's kept-FPKM sum into d_total[k].  The mapped-read total and the insert law are the sample's.
-   const sbgpu_abundance_params_t par = rec->params;
-   const sbgpu_plan_t *plan = rec->plan;
-   const int32_t *d_len = rec->d_iso_len;
-   const AfterStats epilogue = [&](int32_t k, const double *d_theta, const int32_t *d_status, hipStream_t js) {
-      return sbgpu_abundance_device(c, plan, d_theta, d_status, d_len, &par, d_fpkm_rep + (size_t)k * (size_t)n_iso, d_frac,
-                                    d_keep_rep + (size_t)k * (size_t)n_iso, d_total + k, js);
-   };
-   if (const int rc = run_replicates(c, who, plan, rec->d_count, rec->d_F, params, d_theta_mean, d_theta_var, d_status_count, d_theta_rep, nullptr, nullptr, s,
-                                     epilogue);
-       rc != SBGPU_OK)
-      return rc;
-   // ---- the total TPM divides by: ONE collective per call, over all replicates
-   if (comm) {
-      if (const int rc = sbgpu_allreduce_sum_f64(comm, d_total, B, s); rc != SBGPU_OK) {
-         (void)hipStreamSynchronize(s);
-         return rc;
-      }
-   }
-   // ---- the replicates' statistics, twice over the columns: the raw FPKM; the TPM (made while staging) with the kept replicates' count
-   SB_TRY(hipMemsetAsync(d_keep_count, 0, ni * 4, s));
-   sb::BootIntervalArgs a{};
-   a.n = n_iso, a.n_rep = B, a.rank_lo = rank_lo, a.rank_hi = rank_hi, a.x = d_fpkm_rep;
-   a.mean = d_fpkm_mean, a.var = d_fpkm_var, a.lo = d_fpkm_lo, a.hi = d_fpkm_hi;
-   if (const int rc = launch_interval(a, s); rc != SBGPU_OK) {
-      (void)hipStreamSynchronize(s);
-      return rc;
-   }
-   a.keep = d_keep_rep, a.total = d_total, a.keep_count = d_keep_count;
-   a.mean = d_tpm_mean, a.var = d_tpm_var, a.lo = d_tpm_lo, a.hi = d_tpm_hi;
-   if (const int rc = launch_interval(a, s); rc != SBGPU_OK) {
-      (void)hipStreamSynchronize(s);
-      return rc;
-   }
-   // ---- what was asked for comes down; the call returns synchronised
-   auto get = [&](void *dst, const void *src, size_t bytes) { return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess; };
-   double *const host_stat[10] = {out->theta_mean, out->theta_var, out->fpkm_mean, out->fpkm_var, out->fpkm_lo, out->fpkm_hi, out->tpm_mean, out->tpm_var, out->tpm_lo, out->tpm_hi};
-   for (int i = 0; i < 10; ++i) SB_TRY(get(host_stat[i], stat[i], (size_t)n_iso * 8));
-   SB_TRY(get(out->keep_count, d_keep_count, (size_t)n_iso * 4));
-   SB_TRY(get(out->status_count, d_status_count, (size_t)nl * 16));
-   SB_TRY(get(out->total_fpkm_rep, d_total, (size_t)B * 8));
-   SB_TRY(get(out->fpkm_rep, d_fpkm_rep, (size_t)B * (size_t)n_iso * 8));
-   SB_TRY(get(out->keep_rep, d_keep_rep, (size_t)B * (size_t)n_iso * 4));
-   if (d_theta_rep) SB_TRY(get(out->theta_rep, d_theta_rep, (size_t)B * (size_t)n_iso * 8));
-   SB_TRY(hipStreamSynchronize(s));
-#undef SB_TRY
-   if (sb::ctx_take_wide_error(c)) return api_fail(SBGPU_EHIP, std::string(who) + ": a barrier of the wide-locus EM kernel timed out: the loci it served have no result");
-   out->n_rep = B, out->n_iso = n_iso, out->n_loci = nl;
-   out->d_theta_mean = d_theta_mean, out->d_theta_var = d_theta_var;
-   out->d_fpkm_mean = d_fpkm_mean, out->d_fpkm_var = d_fpkm_var, out->d_fpkm_lo = d_fpkm_lo, out->d_fpkm_hi = d_fpkm_hi;
-   out->d_tpm_mean = d_tpm_mean, out->d_tpm_var = d_tpm_var, out->d_tpm_lo = d_tpm_lo, out->d_tpm_hi = d_tpm_hi;
-   out->d_keep_count = d_keep_count, out->d_status_count = d_status_count, out->d_total_fpkm_rep = d_total;
-   out->d_fpkm_rep = d_fpkm_rep, out->d_keep_rep = d_keep_rep, out->d_theta_rep = d_theta_rep;
+   sb::BootLocusSumArgs a{};
+   a.n_loci = n_loci, a.n_iso = 0, a.n_rows = 1, a.iso_off = d_iso_off, a.fpkm = d_fpkm, a.keep = d_keep, a.total = d_total_fpkm;
+   a.locus_fpkm = d_locus_fpkm, a.locus_tpm = d_locus_tpm, a.locus_kept = d_locus_kept;
+   hipLaunchKernelGGL(sb::boot_locus_sum_kernel, dim3((unsigned)((n_loci + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+   if (hipError_t e = hipGetLastError(); e != hipSuccess) return api_fail_hip(e, "boot_locus_sum_kernel");
    return SBGPU_OK;
 }
 

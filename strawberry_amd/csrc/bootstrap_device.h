@@ -8,7 +8,10 @@
 //   boot_stats_kernel      per replicate: one thread per isoform (mean, M2 -> variance) and per locus (status counts)
 //   boot_interval_kernel   once per statistic: mean, variance and two order statistics of every column of a replicate-major
 //                          matrix [n_rep][n] (sbgpu_replicate_stats_device; the FPKM and TPM intervals of
-//                          sbgpu_abundance_bootstrap_device)
+//                          sbgpu_abundance_bootstrap_device; Frac, locus FPKM and locus TPM of
+//                          sbgpu_locus_bootstrap_device)
+//   boot_locus_sum_kernel  per replicate, or once (sbgpu_locus_abundance_device): one thread per (row, locus): the locus' kept
+//                          FPKM sum and the number of kept isoforms by boot_locus_sum
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -229,7 +232,8 @@ struct BootIntervalArgs {
    int64_t n;                    // columns
    int32_t n_rep, rank_lo, rank_hi;
    const double *x;              // [n_rep][n]
-   const int32_t *keep;          // [n_rep][n], or null: x is taken as it stands
+   const int32_t *keep;          // [n_rep][n], or null: x is taken as it stands.  Any value other than 0 is "kept": the isoforms'
+                                 // keep (0 / 1 / 2), or -- the locus columns -- the loci's numbers of kept isoforms
    const double *total;          // [n_rep] (with keep)
    double *mean, *var, *lo, *hi; // [n], each may be null
    int32_t *keep_count;          // [n], zero on entry, or null (with keep)
@@ -337,6 +341,35 @@ __global__ __launch_bounds__(kBootIntervalThreads) void boot_interval_kernel(con
          if (a.hi) a.hi[j] = boot_key_value(k_hi);
       }
    }
+}
+
+// ---- abundances per locus (rule: boot_locus_sum, bootstrap_rules.h)
+//
+// One thread per (row, locus) of fpkm / keep [n_rows][n_iso]: neighbouring lanes own neighbouring loci and so neighbouring
+// isoform ranges -- a wave's loads fall in one contiguous stretch of the row.  The additions run in isoform order (the rule);
+// the loads come four at a time.  No atomics, no LDS.  With `total` ([n_rows]) the locus' TPM is written too.
+struct BootLocusSumArgs {
+   int64_t n_loci, n_iso; // n_iso: the rows' stride in fpkm / keep
+   int32_t n_rows;
+   const int64_t *iso_off; // [n_loci + 1]
+   const double *fpkm;     // [n_rows][n_iso]
+   const int32_t *keep;    // [n_rows][n_iso]
+   const double *total;    // [n_rows], or null (then locus_tpm is null)
+   double *locus_fpkm, *locus_tpm; // [n_rows][n_loci], each may be null
+   int32_t *locus_kept;            // [n_rows][n_loci], or null
+};
+
+__global__ __launch_bounds__(256) void boot_locus_sum_kernel(const BootLocusSumArgs a)
+{
+   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+   if (i >= a.n_loci * a.n_rows) return;
+   const int64_t r = i / a.n_loci, l = i - r * a.n_loci;
+   double sum;
+   int32_t kept;
+   boot_locus_sum(a.fpkm + r * a.n_iso, a.keep + r * a.n_iso, a.iso_off[l], a.iso_off[l + 1], sum, kept);
+   if (a.locus_fpkm) a.locus_fpkm[i] = sum;
+   if (a.locus_kept) a.locus_kept[i] = kept;
+   if (a.locus_tpm) a.locus_tpm[i] = boot_locus_tpm(sum, kept, a.total[r]);
 }
 
 } // namespace sb

@@ -1,5 +1,5 @@
 // strawberry_amd/csrc/bootstrap_host.cpp -- sbgpu_bootstrap_counts_host (include/sbgpu.h): one bootstrap replicate's bin
-// counts on the host, and sbgpu_replicate_stats_host: the replicates' statistics.  The one CPU statement of what csrc/bootstrap_device.h computes: every draw is a function of
+// counts on the host, sbgpu_replicate_stats_host: the replicates' statistics, and sbgpu_locus_abundance_host: abundances per locus.  The one CPU statement of what csrc/bootstrap_device.h computes: every draw is a function of
 // bootstrap_rules.h, which the kernels call too.  No kernels here.
 #include <algorithm>
 #include <cstdint>
@@ -74,6 +74,27 @@ extern "C" int sbgpu_replicate_stats_host(int32_t n_rep, int64_t n, const double
       if (lo || hi) std::sort(key.begin(), key.end());
       if (lo) lo[j] = sb::boot_key_value(key[(size_t)rank_lo]);
       if (hi) hi[j] = sb::boot_key_value(key[(size_t)rank_hi]);
+   }
+   return SBGPU_OK;
+}
+
+// sbgpu_locus_abundance_host: the loci's kept-FPKM sums, their numbers of kept isoforms and their TPM, by boot_locus_sum /
+// boot_locus_tpm of bootstrap_rules.h (boot_locus_sum_kernel calls the same functions).
+extern "C" int sbgpu_locus_abundance_host(int64_t n_loci, const int64_t *iso_off, const double *fpkm, const int32_t *keep, double total_fpkm,
+                                          double *locus_fpkm, double *locus_tpm, int32_t *locus_kept)
+{
+   if (n_loci < 0 || !iso_off) return api_fail(SBGPU_EINVAL, "sbgpu_locus_abundance_host: null iso_off or a negative locus count");
+   if (iso_off[0] < 0) return api_fail(SBGPU_EINVAL, "sbgpu_locus_abundance_host: iso_off must start at 0 or above");
+   for (int64_t l = 0; l < n_loci; ++l)
+      if (iso_off[l + 1] < iso_off[l]) return api_fail(SBGPU_EINVAL, "sbgpu_locus_abundance_host: iso_off must not decrease (locus " + std::to_string(l) + ")");
+   if (iso_off[n_loci] > iso_off[0] && (!fpkm || !keep)) return api_fail(SBGPU_EINVAL, "sbgpu_locus_abundance_host: null fpkm or keep array");
+   for (int64_t l = 0; l < n_loci; ++l) {
+      double sum;
+      int32_t kept;
+      sb::boot_locus_sum(fpkm, keep, iso_off[l], iso_off[l + 1], sum, kept);
+      if (locus_fpkm) locus_fpkm[l] = sum;
+      if (locus_kept) locus_kept[l] = kept;
+      if (locus_tpm) locus_tpm[l] = sb::boot_locus_tpm(sum, kept, total_fpkm);
    }
    return SBGPU_OK;
 }

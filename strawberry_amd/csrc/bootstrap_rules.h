@@ -108,4 +108,35 @@ __host__ __device__ inline double boot_key_value(uint64_t k)
 // The TPM of one replicate's isoform: the expression tpm_kernel (sbgpu_api.hip) evaluates
 __host__ __device__ inline double boot_tpm_value(double fpkm, int32_t keep, double total) { return keep ? 1e6 * fpkm / total : 0.0; }
 
+// ---- abundances per locus (sbgpu_locus_abundance_*, the locus columns of sbgpu_locus_bootstrap_device)
+//
+// Locus l owns isoforms j0 = iso_off[l] .. j1 - 1 = iso_off[l + 1] - 1.  Its FPKM starts at 0.0 and adds fpkm[j] over the
+// isoforms with keep[j] != 0 in isoform order -- the isoforms abundance_kernel's own kept-FPKM sum takes --, `kept` counts
+// them; a locus without isoforms gives 0.0 and 0.  The order of the additions is the rule; only the loads are grouped, four
+// at a time as abundance_kernel's are.  The locus' TPM is boot_tpm_value with `kept` as the flag.
+__host__ __device__ inline void boot_locus_sum(const double *fpkm, const int32_t *keep, int64_t j0, int64_t j1, double &sum, int32_t &kept)
+{
+   double acc = 0.0;
+   int32_t n = 0;
+   for (int64_t jb = j0; jb < j1; jb += 4) {
+      double f[4];
+      int32_t kk[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+         const bool in = jb + u < j1;
+         f[u] = in ? fpkm[jb + u] : 0.0;
+         kk[u] = in ? keep[jb + u] : 0;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+         if (kk[u]) { // (a slot past the locus' end holds keep 0)
+            acc += f[u];
+            ++n;
+         }
+      }
+   }
+   sum = acc, kept = n;
+}
+__host__ __device__ inline double boot_locus_tpm(double locus_fpkm, int32_t kept, double total) { return boot_tpm_value(locus_fpkm, kept, total); }
+
 } // namespace sb

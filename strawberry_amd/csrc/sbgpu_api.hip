@@ -416,7 +416,7 @@ PlanShape plan_shape(const sbgpu_plan_t *plan)
 {
    PlanShape s;
    s.n_loci = plan->host.n_loci, s.n_rows = plan->host.n_rows, s.n_iso = plan->host.n_iso;
-   s.d_row_off = plan->d_row_off;
+   s.d_row_off = plan->d_row_off, s.d_iso_off = plan->d_iso_off;
    return s;
 }
 } // namespace sb

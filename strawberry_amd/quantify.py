@@ -222,6 +222,7 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     (context.context_table_device) -> "context"; "bins": the handle's LocusBins (the rows index its bins).
     bootstrap = dict(n_rep=, seed=, level=0.95, locus_id=None, ...): the call keeps what the bootstrap needs (sbgpu_bootstrap_keep)
     and bootstrap.abundance_bootstrap_device runs on its handle with these arguments (and `comm`) -> "bootstrap": its dict; "bins" as above.
+    With locus=True among them the bootstrap is sbgpu_locus_bootstrap_device: "bootstrap" also holds "frac" and "locus" (DESIGN 3.19).
     keep_bootstrap: retention for the bootstrap on, without running it (for a caller that runs it several times).
     keep_handle: the handle is not exported but returned as "handle", a BinsHandle that owns it -- it is destroyed by its close(),
     as a context manager, or when the object is collected; the caller runs bootstrap.abundance_bootstrap_device /

@@ -18,6 +18,10 @@ Device events around windows that end in a synchronisation, after a warm-up wind
   em_bootstrap_ms_per_replicate  sbgpu_em_bootstrap_device on the same batch (the handle's bins, sbgpu_quantify_host's weights) in
                              the same process: code the parent commit has too, the baseline
   with --kernel-loop N only N calls of the resident bootstrap, for the kernel trace.
+--resident --locus: the locus bootstrap beside it, in one process on one resident call's handle:
+  locus_bootstrap_ms_per_replicate     sbgpu_locus_bootstrap_device, the whole call / B
+  resident_bootstrap_ms_per_replicate  sbgpu_abundance_bootstrap_device, the whole call / B: code the parent commit has too, the baseline
+  with --kernel-loop N only N calls of the locus bootstrap, for the kernel trace (boot_locus_sum_kernel, boot_interval_kernel).
 --kernel-loop N: only N bootstrap calls of B replicates, for a `rocprofv3 --kernel-trace --stats` run of its own;
 --kernel-stats FILE merges that run's per-kernel averages (the *_kernel_stats.csv) into --out."""
 import argparse
@@ -112,13 +116,32 @@ def resident_leg(args):
     q = chain.ChainQuantifier(ctx, n_loci=args.loci, n_frags=2e8 * args.loci / 60000.0, resident=True, min_isoform_frac=0.01, keep_bootstrap=True)
     torch = q.torch
     q.step()
-    run = lambda: q.abundance_bootstrap(args.reps, args.seed, level=0.95, replicates=False)  # noqa: E731
+    run = lambda: q.abundance_bootstrap(args.reps, args.seed, level=0.95, replicates=False, locus=args.locus)  # noqa: E731
     if args.kernel_loop:
         for _ in range(args.kernel_loop):
             run()
-        print(json.dumps({"kernel_loop": args.kernel_loop, "reps": args.reps, "resident": True}))
+        print(json.dumps({"kernel_loop": args.kernel_loop, "reps": args.reps, "resident": True, "locus": args.locus}))
         q.close()
         return None
+    if args.locus:
+        doc = {"tool": "tools/bench_bootstrap.py --resident --locus", "build_id": ctx.L.sbgpu_build_id().decode(), "n_loci": q.n_loci,
+               "n_iso": q.n_iso, "n_hits": q.n_hits, "n_frags": q.n_frags, "reps": args.reps, "measured": True}
+        old = lambda: q.abundance_bootstrap(args.reps, args.seed, level=0.95, replicates=False)  # noqa: E731
+        first, before = run(), old()
+        if any(first[k].tobytes() != before[k].tobytes() for k in ("fpkm_mean", "fpkm_var", "tpm_lo", "tpm_hi", "keep_count", "total_fpkm_rep")):
+            raise RuntimeError("the locus call's isoform results differ from the old call's")
+        doc["same_isoform_results_in_both_legs"] = True
+        doc["loci_kept_in_all_replicates"] = int((first["locus"]["kept_count"] == args.reps).sum())
+        doc["loci_kept_in_some_replicates"] = int(((first["locus"]["kept_count"] > 0) & (first["locus"]["kept_count"] < args.reps)).sum())
+        a, b = [], []
+        for _ in range(args.windows):       # the legs alternate: a drift of the clocks hits both
+            a.append(event_window(torch, q.dev, run) / args.reps)
+            b.append(event_window(torch, q.dev, old) / args.reps)
+        doc["locus_bootstrap_ms_per_replicate"], doc["resident_bootstrap_ms_per_replicate"] = summary(a), summary(b)
+        doc["added_ms_per_replicate"] = doc["locus_bootstrap_ms_per_replicate"]["median"] - doc["resident_bootstrap_ms_per_replicate"]["median"]
+        print(json.dumps({k: doc[k] for k in ("locus_bootstrap_ms_per_replicate", "resident_bootstrap_ms_per_replicate", "added_ms_per_replicate")}), flush=True)
+        q.close()
+        return doc
     doc = {"tool": "tools/bench_bootstrap.py --resident", "build_id": ctx.L.sbgpu_build_id().decode(), "n_loci": q.n_loci, "n_iso": q.n_iso,
            "n_hits": q.n_hits, "n_frags": q.n_frags, "reps": args.reps, "measured": True}
     first = run()
@@ -171,6 +194,7 @@ def main():
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5742)
     ap.add_argument("--out", default=None)
     ap.add_argument("--resident", action="store_true", help="the bootstrap of the resident path on the chain sample")
+    ap.add_argument("--locus", action="store_true", help="with --resident: sbgpu_locus_bootstrap_device beside sbgpu_abundance_bootstrap_device")
     args = ap.parse_args()
     if args.kernel_stats:
         doc = json.load(open(args.out))
