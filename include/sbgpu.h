@@ -951,6 +951,63 @@ int sbgpu_context_table_keep(sbgpu_ctx_t *ctx, int32_t on);
  * (NULL: the context's own).  Loci of more than 4096 isoforms: SBGPU_ESHAPE.                                        */
 int sbgpu_context_table_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins, void *stream, sbgpu_context_table_t *out);
 
+/* ---- fragment assignment: which isoform a fragment came from, and how sure that is -------------------
+ * The posterior U(i,j) that EmSolver::run computes per bin and discards (src/estimate.cpp:449-458), per HIT: hits of one bin
+ * differ in their compat words, so they differ in their candidates.  The rule (csrc/assign_rules.h, shared by both forms,
+ * compiled under -ffp-contract=off), for locus l with bins b, isoforms j, raw weights F[b][j], the caller's theta, keep, status:
+ *   - kept(j): keep[j] != 0, and nothing is kept in a locus whose status is SBGPU_EM_INIT_EMPTY (as for the -f table);
+ *   - a bin is LIVE if some F[b][j] > SBGPU_EM_ROW_EPS (the row drop of EmSolver::init, estimate.cpp:377-384);
+ *   - the column scale c_j is the sum of F[b][j] over the locus' live bins in ascending bin order -- the normalisation the EM
+ *     runs on from its second iteration (estimate.cpp:466-475); the model weight is W[b][j] = F[b][j] / c_j, 0 where c_j == 0;
+ *   - the gain g_j = theta[j] / c_j, exactly 0.0 where j is not kept or c_j == 0;
+ *   - the CANDIDATES of hit h are compat(h) & kept(l); n_cand[h] is their number -- a fact of the words alone, defined for
+ *     every hit;
+ *   - numerator num_j = theta[j] * W[b][j], evaluated as g_j * F[b][j], for each candidate; the denominator den is the sum of
+ *     the numerators over the candidates in ascending j; the posterior p(j|h) = num_j / den;
+ *   - h is UNASSIGNED -- map_iso = -1, map_prob = 0.0 -- when it has no bin (hit -> bin < 0), its bin is not live, it has no
+ *     candidate, or den is not > 0;
+ *   - otherwise map_iso[h] is the candidate of the largest numerator, the lowest j on a tie (strict > in ascending order), as
+ *     the index inside the locus, and map_prob[h] is its p;
+ *   - per isoform, over the ASSIGNED hits of its locus, m_h the hit's mass (1.0 where no masses are given):
+ *       unique_mass[j] = sum of m_h over the hits with n_cand == 1 and candidate j,
+ *       map_mass[j]    = sum of m_h over the hits with map_iso == j,
+ *       post_mass[j]   = sum of m_h * p(j|h);
+ *   - per locus, unassigned[l] is the number of its unassigned hits.
+ * The struct: host arrays to fill (any may be NULL) with, where one of the three per-hit arrays is given, n_hits saying how
+ * many hits they hold (another count than the call's own: SBGPU_EINVAL, nothing is written) and, on return, the hit count
+ * and -- device form only -- the device arrays of all seven (the context's memory: valid until its next sbgpu_quantify_* or sbgpu_fragment_assign_device call). */
+typedef struct {
+   int32_t *map_iso;          /* in: [n_hits]  the MAP isoform's index inside the hit's locus, -1: unassigned */
+   double  *map_prob;         /* in: [n_hits]  its posterior, 0.0: unassigned                                  */
+   int32_t *n_cand;           /* in: [n_hits]                                                                  */
+   double  *unique_mass, *map_mass, *post_mass; /* in: [n_iso]                                                 */
+   int64_t *unassigned;       /* in: [n_loci]                                                                  */
+   int64_t n_hits;            /* in: the per-hit arrays' length (read where one is given); out: the hits */
+   const int32_t *d_map_iso; const double *d_map_prob; const int32_t *d_n_cand; /* out: device form only       */
+   const double *d_unique_mass, *d_map_mass, *d_post_mass; const int64_t *d_unassigned;
+} sbgpu_fragment_assign_t;
+/* Host form, the plain statement of the arithmetic; every sum runs in hit order.  `bins` holds hit -> bin (sbgpu_bins_create,
+ * sbgpu_quantify_host; a handle that holds none: SBGPU_EINVAL), compat[n_hits * compat_words] the hits' compat words, F[n_elem]
+ * the bin weights (NULL: the handle's own), theta[n_iso] the abundances the posterior is taken under (NULL: SBGPU_EINVAL),
+ * keep[n_iso] / status[n_loci] as for sbgpu_context_table_host (NULL: everything kept / every locus started), hit_mass[n_hits]
+ * the hits' masses (NULL: 1.0 each).  A hit without a bin belongs to the locus the hits' grouping says; a handle whose hits
+ * did not come grouped by locus and that holds such a hit: SBGPU_EINVAL.                                              */
+int sbgpu_fragment_assign_host(const sbgpu_bins_t *bins, const uint32_t *compat, int32_t compat_words, const double *F,
+                               const double *theta, const int32_t *keep, const int32_t *status, const float *hit_mass,
+                               sbgpu_fragment_assign_t *out);
+/* Device form (csrc/assign_device.h): under the conditions of sbgpu_context_table_device -- right after a resident call or an
+ * sbgpu_front_stream_end made with sbgpu_context_table_keep on, on that call's handle; SBGPU_EINVAL for a handle made without
+ * retention or a stale one -- from what the call kept (hit -> bin, compat words, F, keep, status: nothing more is retained).
+ * d_theta: any device [n_iso] array -- normally the call's d_theta; a bootstrap mean serves as well; d_hit_mass: the array the
+ * resident call was given, or NULL for unit masses.  One pass over F (live bins, gains), one over the hits.  The per-hit
+ * results are the host form's bits; the per-isoform sums are added in another order (integers in doubles for unit masses:
+ * exact; post_mass: within the rounding of a sum of its non-negative terms).  The results live in a scratch slot of their
+ * own: the table and the assignment may be asked for in either order, repeatedly.  Only what the caller asked for crosses
+ * PCIe.  Synchronises on `stream` (NULL: the context's own).  Loci of more than 4096 isoforms or more than 5632 bins:
+ * SBGPU_ESHAPE.                                                                                                       */
+int sbgpu_fragment_assign_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins, const double *d_theta, const float *d_hit_mass,
+                                 void *stream, sbgpu_fragment_assign_t *out);
+
 /* ---- the EM bootstrap: how far theta can be trusted -------------------------
  * The reference prints theta with no statement of its spread.  The bootstrap resamples every locus' fragments over its
  * bins, solves again, and reports mean and variance of theta over the replicates.

@@ -635,6 +635,54 @@ class ContextTable {
    }
 };
 
+/* Fragment assignment (sbgpu_fragment_assign_*, include/sbgpu.h states the rule): every hit's MAP isoform (the index inside its
+ * locus, -1: unassigned), its posterior and its number of candidates; per isoform the mass of the hits only it explains, of the
+ * hits whose MAP it is, and the posterior mass; per locus the unassigned hits.  host(): on a handle that holds hit -> bin
+ * (n_hits: the hits the handle was made from).  device(): under ContextTable::device's conditions (ContextTable::keep before the
+ * resident call), n_hits and d_hit_mass (nullptr: unit masses) as that call was given them, d_theta normally its d_theta.       */
+class FragmentAssignment {
+ public:
+   std::vector<int32_t> map_iso, n_cand;             /* [n_hits] */
+   std::vector<double> map_prob;                     /* [n_hits] */
+   std::vector<double> unique_mass, map_mass, post_mass; /* [n_iso] */
+   std::vector<int64_t> unassigned;                  /* [n_loci] */
+   sbgpu_fragment_assign_t raw{};  /* device(): the device arrays -- the context's, valid until its next quantify or assignment call */
+
+   static FragmentAssignment host(const sbgpu_bins_t *bins, int64_t n_hits, const uint32_t *compat, int32_t compat_words, const double *F,
+                                  const double *theta, const int32_t *keep, const int32_t *status, const float *hit_mass)
+   {
+      FragmentAssignment t;
+      t.prepare(bins, n_hits);
+      check(sbgpu_fragment_assign_host(bins, compat, compat_words, F, theta, keep, status, hit_mass, &t.raw), "sbgpu_fragment_assign_host");
+      return t;
+   }
+   static FragmentAssignment device(const Context &ctx, const sbgpu_bins_t *bins, int64_t n_hits, const double *d_theta,
+                                    const float *d_hit_mass = nullptr, void *stream = nullptr)
+   {
+      FragmentAssignment t;
+      t.prepare(bins, n_hits);
+      check(sbgpu_fragment_assign_device(ctx.get(), bins, d_theta, d_hit_mass, stream, &t.raw), "sbgpu_fragment_assign_device");
+      return t;
+   }
+
+ private:
+   void prepare(const sbgpu_bins_t *bins, int64_t n_hits)
+   {
+      int64_t info[8];
+      check(sbgpu_bins_info(bins, info), "sbgpu_bins_info");
+      if (n_hits < 0) throw std::invalid_argument("FragmentAssignment: negative hit count");
+      map_iso.assign((size_t)n_hits, -1), n_cand.assign((size_t)n_hits, 0), map_prob.assign((size_t)n_hits, 0.0);
+      unique_mass.assign((size_t)info[1], 0.0), map_mass.assign((size_t)info[1], 0.0), post_mass.assign((size_t)info[1], 0.0);
+      unassigned.assign((size_t)info[0], 0);
+      raw = sbgpu_fragment_assign_t{};
+      /* (the vectors' own buffers: moving the object moves them, and raw's host pointers with them) */
+      raw.map_iso = map_iso.data(), raw.n_cand = n_cand.data(), raw.map_prob = map_prob.data();
+      raw.unique_mass = unique_mass.data(), raw.map_mass = map_mass.data(), raw.post_mass = post_mass.data();
+      raw.unassigned = unassigned.data();
+      raw.n_hits = n_hits;
+   }
+};
+
 /* The bootstrap of the resident path (sbgpu_bootstrap_keep / sbgpu_abundance_bootstrap_device, include/sbgpu.h): FPKM and TPM
  * mean, variance and percentile interval over resampled bin counts, with the replicates in which the expression filter kept
  * each isoform.  keep(): before the resident call; device(): right after it, on that call's handle.  interval_ranks(): the two

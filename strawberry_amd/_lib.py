@@ -45,6 +45,7 @@ SYMBOLS = [
     "sbgpu_bootstrap_counts_host", "sbgpu_bootstrap_counts_device", "sbgpu_em_bootstrap_device",
     "sbgpu_replicate_stats_host", "sbgpu_replicate_stats_device", "sbgpu_bootstrap_keep", "sbgpu_abundance_bootstrap_device",
     "sbgpu_locus_abundance_host", "sbgpu_locus_abundance_device", "sbgpu_locus_bootstrap_device",
+    "sbgpu_fragment_assign_host", "sbgpu_fragment_assign_device",
 ]
 
 
@@ -148,6 +149,12 @@ class sbgpu_hits_t(C.Structure):
 class sbgpu_context_table_t(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("locus_row_off", "locus_hits", "row_bin", "row_hits", "row_prob")] + [("n_rows", C.c_int64)] +
                 [(n, C.c_void_p) for n in ("d_locus_row_off", "d_locus_hits", "d_row_bin", "d_row_hits", "d_row_prob")])
+
+
+class sbgpu_fragment_assign_t(C.Structure):
+    _NAMES = ("map_iso", "map_prob", "n_cand", "unique_mass", "map_mass", "post_mass", "unassigned")
+    _fields_ = ([(n, C.c_void_p) for n in _NAMES] + [("n_hits", C.c_int64)] +
+                [("d_" + n, C.c_void_p) for n in ("map_iso", "map_prob", "n_cand", "unique_mass", "map_mass", "post_mass", "unassigned")])
 
 
 class sbgpu_bootstrap_params_t(C.Structure):
@@ -329,6 +336,8 @@ def load():
     L.sbgpu_context_table_host.argtypes = [vp, vp, C.c_int32, vp, vp, vp, C.POINTER(sbgpu_context_table_t)]
     L.sbgpu_context_table_keep.argtypes = [vp, C.c_int32]
     L.sbgpu_context_table_device.argtypes = [vp, vp, vp, C.POINTER(sbgpu_context_table_t)]
+    L.sbgpu_fragment_assign_host.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(sbgpu_fragment_assign_t)]
+    L.sbgpu_fragment_assign_device.argtypes = [vp, vp, vp, vp, vp, C.POINTER(sbgpu_fragment_assign_t)]
     L.sbgpu_bootstrap_counts_host.argtypes = [C.c_int64, vp, vp, vp, C.c_uint64, C.c_int32, vp]
     L.sbgpu_bootstrap_counts_device.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp]
     L.sbgpu_em_bootstrap_device.argtypes = [vp, vp, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp, vp, vp, vp, vp, vp]

@@ -229,7 +229,8 @@ class ChainQuantifier:
         theta, FPKM, Frac, keep and TPM land in the object's host arrays, `law` holds the insert-size law that was used.
         keep_context=True (resident only): every step asks the context to keep what the `-f` table needs (sbgpu_context_table_keep,
         switched on for the step's own call only: the context may be shared) and the last step's handle lives on in
-        `context_handle`; context_table() builds the table from it on the device.
+        `context_handle`; context_table() builds the table from it on the device, fragment_assignment() every hit's isoform
+        posterior (both from the same retention, in either order, repeatedly).
         keep_bootstrap=True (resident only): likewise for the bootstrap (sbgpu_bootstrap_keep); abundance_bootstrap() runs it on the
         last step's handle."""
         import torch
@@ -330,6 +331,21 @@ class ChainQuantifier:
         if self.context_handle is None:
             raise _lib.SbgpuError("context_table: no step has run with keep_context=True")
         return context.context_table_device(self.ctx, self.context_handle)
+
+    def _assignment_hits(self):
+        """(device address of the masses the last resident call was given, its hit count)"""
+        return self.hits.mass.data_ptr(), self.n_hits
+
+    def fragment_assignment(self, d_theta=None, want=None):
+        """Every hit's isoform posterior for the last step (assign.FragmentAssignment), built on the device under the step's own
+        theta -- or d_theta, a float64 tensor / device address [n_iso], e.g. a bootstrap mean -- and the hits' masses.
+        want: the arrays to bring to the host (None: all)."""
+        from . import assign
+        if self.context_handle is None or not self.keep_context:
+            raise _lib.SbgpuError("fragment_assignment: no step has run with keep_context=True")
+        d_mass, n_hits = self._assignment_hits()
+        return assign.fragment_assign_device(self.ctx, self.context_handle, int(self._out.d_theta) if d_theta is None else d_theta, n_hits,
+                                             d_hit_mass=d_mass, want=want)
 
     def abundance_bootstrap(self, n_rep, seed, **kw):
         """The bootstrap of the last step (keep_bootstrap=True): bootstrap.abundance_bootstrap_device on its handle, over this

@@ -178,7 +178,7 @@ hipStream_t ctx_stream(const sbgpu_ctx_t *ctx); // the context's own stream
 hipStream_t ctx_aux_stream(const sbgpu_ctx_t *ctx, int i); // one of the context's side streams (0..7; the EM's kinds use 0, 1, 2, 6)
 int ctx_cu_count(const sbgpu_ctx_t *ctx);
 int ctx_device(const sbgpu_ctx_t *ctx);        // the HIP device the context was made on
-// device scratch that lives with the context (slot 0..8; 8 is the context table's, grows on demand, never shrinks): valid until the next
+// device scratch that lives with the context (slot 0..9; 8 is the context table's, 9 the fragment assignment's; grows on demand, never shrinks): valid until the next
 // request for the same slot; one host thread per context
 hipError_t ctx_scratch(sbgpu_ctx_t *ctx, int slot, size_t bytes, char **out);
 // Device allocations that change hands (a handle's arenas, a plan's arena): a hipMalloc / hipFree pair per call costs a
@@ -243,9 +243,12 @@ struct BinsContextView {
    const uint32_t *d_key = nullptr; // device, [n_bins * key_words]: the bin keys of a device grouping, else null
    uint64_t context_serial = 0;     // the resident call that kept the table's inputs for this handle (0: none did)
    uint64_t boot_serial = 0;        // the resident call that kept the bootstrap's inputs for this handle (0: none did)
+   const int64_t *locus_hit_off = nullptr; // host, [n_loci + 1]: the hits by locus where they came grouped (hit -> bin on the host), else null
 };
 BinsContextView bins_context_view(const sbgpu_bins_t *bins);
 void bins_set_context_serial(sbgpu_bins_t *bins, uint64_t serial);
+// where each locus' hits begin, for a handle whose hits came grouped by locus (what says which locus a hit WITHOUT a bin belongs to)
+void bins_set_locus_hit_off(sbgpu_bins_t *bins, const std::vector<int64_t> &locus_hit_off);
 void bins_set_boot_serial(sbgpu_bins_t *bins, uint64_t serial);
 // What a resident call leaves for sbgpu_context_table_device when the context was asked to (sbgpu_context_table_keep): device
 // pointers into the context's scratch, valid until the context's next sbgpu_quantify_* call (which clears the record).

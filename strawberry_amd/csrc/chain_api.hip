@@ -849,6 +849,7 @@ int QuantifyCall::finish_handle(const WorkArena &w)
       sb::bins_set_device_hit_bin(bins, hit_bin_arena, hit_bin_cap, nh);
       hit_bin_arena = nullptr, hit_bin_cap = 0;
    }
+   if (grouped && nh && !on_dev) sb::bins_set_locus_hit_off(bins, locus_hit_off); // (the host grouping notes it itself)
    if (a.insert_used) *a.insert_used = law.ins;
    if (a.insert_used && !a.insert && law.ins.use_emp) {
       // the histogram lives on with the handle: behind the weights

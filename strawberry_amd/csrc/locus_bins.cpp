@@ -57,6 +57,7 @@ struct sbgpu_bins {
    std::string host_grouping_reason;
    uint64_t context_serial = 0; // the resident call that kept the context table's inputs for this handle (sbgpu_context_table_keep)
    uint64_t boot_serial = 0;    // the resident call that kept the bootstrap's inputs for this handle (sbgpu_bootstrap_keep)
+   std::vector<int64_t> locus_hit_off; // [n_loci + 1] where the hits came grouped by locus, else empty (sbgpu_fragment_assign_host)
    ~sbgpu_bins()
    {
       sb::dev_give(dev.arena, dev.capacity);
@@ -318,7 +319,13 @@ int bins_create_impl(const sbgpu_annotation_t *an, const sbgpu_hits_t *hits, con
       for (int64_t l = 0; l < nl; ++l) loc_start[(size_t)l + 1] += loc_start[(size_t)l];
       {
          std::vector<int64_t> fill(loc_start.begin(), loc_start.end() - 1);
-         for (int64_t h = 0; h < nh; ++h) order[(size_t)fill[(size_t)hits->hit_locus[h]]++] = h;
+         bool grouped = true; // the hits come locus by locus: hit h is the h-th in locus order
+         for (int64_t h = 0; h < nh; ++h) {
+            const int64_t at = fill[(size_t)hits->hit_locus[h]]++;
+            order[(size_t)at] = h;
+            grouped &= at == h;
+         }
+         if (grouped && !pre) B->locus_hit_off = loc_start;
       }
       B->hit_bin.assign((size_t)nh, -1);
       stage("setup");
@@ -610,6 +617,7 @@ void bins_set_device_hit_bin(sbgpu_bins_t *b, char *arena, size_t capacity, int6
 const double *bins_weights_tail(const sbgpu_bins_t *b, size_t at) { return b->F.data() + at; }
 void bins_set_context_serial(sbgpu_bins_t *b, uint64_t serial) { b->context_serial = serial; }
 void bins_set_boot_serial(sbgpu_bins_t *b, uint64_t serial) { b->boot_serial = serial; }
+void bins_set_locus_hit_off(sbgpu_bins_t *b, const std::vector<int64_t> &off) { b->locus_hit_off = off; }
 BinsContextView bins_context_view(const sbgpu_bins_t *b)
 {
    BinsContextView v;
@@ -621,6 +629,7 @@ BinsContextView bins_context_view(const sbgpu_bins_t *b)
    if (b->dev_bins.arena) v.d_key = (const uint32_t *)(b->dev_bins.arena + b->dev_bins.o_key);
    v.context_serial = b->context_serial;
    v.boot_serial = b->boot_serial;
+   if ((int64_t)b->locus_hit_off.size() == b->n_loci + 1) v.locus_hit_off = b->locus_hit_off.data();
    return v;
 }
 const DevicePairs *bins_device_pairs(const sbgpu_bins_t *b) { return b && b->pairs_on_device ? &b->dev : nullptr; }

@@ -155,9 +155,27 @@ class FrontQuantifier(ChainQuantifier):
         self._read_off = np.zeros(self.n_loci + 1, np.int64)
         self.stage_wall_ms = {}
         self.counts = {}
+        self._front_hits = None     # keep_context: (destroy, handle, masses' device address, hits) of the last pass' unique hits
+
+    def _release_front_hits(self):
+        """keep_context: the last pass' unique hits lived on for fragment_assignment() (their masses); the next pass, or close(), lets them go."""
+        if getattr(self, "_front_hits", None) is not None:
+            destroy, handle = self._front_hits[:2]
+            self._front_hits = None
+            destroy(handle)
+
+    def _assignment_hits(self):
+        if self._front_hits is None:
+            raise _lib.SbgpuError("fragment_assignment: no pass has run with keep_context=True")
+        return self._front_hits[2], self._front_hits[3]
+
+    def close(self):
+        self._release_front_hits()
+        super().close()
 
     def step(self, keep=False):
         torch, L, ctx = self.torch, self.ctx.L, self.ctx
+        self._release_front_hits()
         sync = lambda: torch.cuda.synchronize(self.dev)  # noqa: E731
         ms = {}
         sync()
@@ -217,8 +235,11 @@ class FrontQuantifier(ChainQuantifier):
             info = (C.c_int64 * 8)()
             _lib.check(L.sbgpu_bins_info(h, info), "sbgpu_bins_info")
             self.info = {"n_bins": int(info[2]), "n_elem": int(info[3]), "n_pairs": int(info[4]), "hits_in_bins": int(info[6])}
-        self._retire(h)         # (the table reads the hits' compat words, not the hits: the unique hits' handle may go)
-        L.sbgpu_uniq_dev_destroy(hu)
+        self._retire(h)         # (the table reads the hits' compat words, not the hits: the unique hits' handle may go ...
+        if self.keep_context:   # ... the assignment reads their masses: it lives until the next pass)
+            self._front_hits = (L.sbgpu_uniq_dev_destroy, hu, d_mass.value, int(dh.n_hits))
+        else:
+            L.sbgpu_uniq_dev_destroy(hu)
         self.stage_wall_ms = ms
 
     # ---- the same pass for a caller that holds the records in HOST memory: sbgpu_front_stream_* (chunks, bounded footprint)
@@ -277,7 +298,9 @@ class FrontQuantifier(ChainQuantifier):
         as a BGZF file, pushed compressed (sbgpu_front_stream_push_bgzf) instead of the inflated chunks.  -> the stream's info
         (sbgpu_front_stream_info) as a dict."""
         L, ctx = self.ctx.L, self.ctx
+        self._release_front_hits()
         fs = C.c_void_p()
+        kept = False
         _lib.check(L.sbgpu_front_stream_begin(ctx.h, C.byref(self._clusters), C.byref(self._opts), self.chunk_bytes, C.byref(fs)), "sbgpu_front_stream_begin")
         try:
             if bgzf is not None:
@@ -307,8 +330,14 @@ class FrontQuantifier(ChainQuantifier):
             info = (C.c_int64 * 16)()
             _lib.check(L.sbgpu_front_stream_info(fs, info), "sbgpu_front_stream_info")
             self._retire(h)
+            if self.keep_context:   # (the store's masses are what fragment_assignment() reads: the stream lives until the next pass)
+                dh, d_mass = _lib.sbgpu_hits_t(), C.c_void_p()
+                _lib.check(L.sbgpu_front_stream_hits(fs, C.byref(dh), C.byref(d_mass), None), "sbgpu_front_stream_hits")
+                self._front_hits = (L.sbgpu_front_stream_destroy, fs, d_mass.value, int(dh.n_hits))
+                kept = True
         finally:
-            L.sbgpu_front_stream_destroy(fs)
+            if not kept:
+                L.sbgpu_front_stream_destroy(fs)
         keys = ("records", "accepted_records", "pairs", "unique_hits", "features", "pairs_dropped_by_the_span_filter", "mapped_reads", "chunks",
                 "clusters_finished", "most_bytes_carried", "records_decoded_twice", "least_free_device_bytes", "chunk_bytes", "ended",
                 "free_device_bytes_at_begin", "compressed_bytes_pushed")

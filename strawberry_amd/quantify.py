@@ -138,11 +138,15 @@ class LocusQuantifier:
         return self.solve(total_mapped_reads, **abundance_kw)
 
 
-def quantify_host(annot, hits, insert, read_len, long_read=False, ctx=None, device=0, context_keep=None, context_status=None):
+def quantify_host(annot, hits, insert, read_len, long_read=False, ctx=None, device=0, context_keep=None, context_status=None,
+                  assignment_theta=None, assignment_keep=None, assignment_status=None):
     """sbgpu_quantify_host: the whole chain as one C-ABI call on host arrays (what a C / C++ driver uses).
     insert=None: build the empirical insert-size distribution from the hits.
     context_keep (per isoform, from the caller's epilogue; context_status: the EM's per locus, default this call's): also the
     `-f` table's arrays from the handle, through the host form (context.context_table_host) -> "context".
+    assignment_theta (per isoform; True: this call's theta), with assignment_keep / assignment_status (default: all kept / this
+    call's status): also every hit's isoform posterior through the host form (assign.fragment_assign_host, under the hits' own
+    masses) -> "assignment".
     -> dict(theta, status, iters, compat, bins (LocusBins incl. hit_bin), F, insert (mean, sd, use_emp, ...))"""
     from .exonbin import LocusBins
     ctx = ctx or default_context(device)
@@ -178,10 +182,20 @@ def quantify_host(annot, hits, insert, read_len, long_read=False, ctx=None, devi
         except Exception:
             L.sbgpu_bins_destroy(handle)
             raise
+    assignment = None
+    if assignment_theta is not None:
+        from . import assign
+        try:
+            assignment = assign.fragment_assign_host(
+                handle, compat[:hits.n_hits], theta[:n_iso] if assignment_theta is True else assignment_theta, keep=assignment_keep,
+                status=status[:annot.n_loci] if assignment_status is None else assignment_status, hit_mass=hits.mass)
+        except Exception:
+            L.sbgpu_bins_destroy(handle)
+            raise
     bins = LocusBins.__new__(LocusBins)
     bins._export(L, annot, handle, hits.n_hits, cw, kw, with_hit_bin=True)   # destroys the handle
     return {"theta": theta[:n_iso], "status": status[:annot.n_loci], "iters": iters[:annot.n_loci],
-            "compat": compat[:hits.n_hits], "bins": bins, "F": F[:int(info[3])], "context": table,
+            "compat": compat[:hits.n_hits], "bins": bins, "F": F[:int(info[3])], "context": table, "assignment": assignment,
             "insert": {"mean": used.mean, "sd": used.sd, "use_emp": bool(used.use_emp), "start_offset": used.start_offset,
                        "end_offset": used.end_offset, "total_reads": used.total_reads, "emp_hist": emp}}
 
@@ -214,12 +228,14 @@ class BinsHandle:
 
 def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=False, ctx=None, device=0, comm=None,
                       min_isoform_frac=0.0, filter_by_expression=True, effective_len_norm=False, with_context=False, bootstrap=None,
-                      keep_bootstrap=False, keep_handle=False):
+                      keep_bootstrap=False, keep_handle=False, with_assignment=False):
     """sbgpu_quantify_resident on host hits brought to the device first (torch owns the copies): pass 1 (insert=None: the
     empirical insert-size law, built on the device), bins, weights, EM, FPKM / Frac / keep, the FPKM all-reduce over `comm`
     (dist.AbiComm / dist.HostComm; None: a world of one), TPM.  The hits must come grouped by locus.
     with_context: the call keeps what the `-f` table needs (sbgpu_context_table_keep) and the table is built on the device
     (context.context_table_device) -> "context"; "bins": the handle's LocusBins (the rows index its bins).
+    with_assignment: the same retention, and every hit's isoform posterior under the call's theta and the hits' masses, built on
+    the device (assign.fragment_assign_device) -> "assignment"; "bins" as with_context.
     bootstrap = dict(n_rep=, seed=, level=0.95, locus_id=None, ...): the call keeps what the bootstrap needs (sbgpu_bootstrap_keep)
     and bootstrap.abundance_bootstrap_device runs on its handle with these arguments (and `comm`) -> "bootstrap": its dict; "bins" as above.
     With locus=True among them the bootstrap is sbgpu_locus_bootstrap_device: "bootstrap" also holds "frac" and "locus" (DESIGN 3.19).
@@ -256,7 +272,8 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     ins = insert._struct(read_len, long_read) if insert is not None else None
     handle = C.c_void_p()
     torch.cuda.synchronize(dev)
-    if with_context:
+    retain = bool(with_context) or bool(with_assignment)
+    if retain:
         _lib.check(L.sbgpu_context_table_keep(ctx.h, 1), "sbgpu_context_table_keep")
     keep_bootstrap = bool(keep_bootstrap) or bootstrap is not None
     if keep_bootstrap:
@@ -267,7 +284,7 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
                                              C.byref(par), comm.h if comm is not None else None, C.byref(used), C.byref(out),
                                              C.byref(handle)), "sbgpu_quantify_resident")
     finally:
-        if with_context:
+        if retain:
             L.sbgpu_context_table_keep(ctx.h, 0)    # (what the call kept stays until the context's next quantify call)
         if keep_bootstrap:
             L.sbgpu_bootstrap_keep(ctx.h, 0)
@@ -277,9 +294,9 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     owner = BinsHandle(L, handle) if keep_handle else None     # (from here on an exception frees the handle with the object)
     info = (C.c_int64 * 8)()
     _lib.check(L.sbgpu_bins_info(handle, info), "sbgpu_bins_info")
-    table = bins = boot = None
-    if with_context or bootstrap is not None:
-        from . import context
+    table = bins = boot = assignment = None
+    if retain or bootstrap is not None:
+        from . import assign, context
         from .bootstrap import abundance_bootstrap_device
         from .exonbin import LocusBins
         try:
@@ -287,6 +304,8 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
                 boot = abundance_bootstrap_device(ctx, handle, comm=comm, **bootstrap)
             if with_context:
                 table = context.context_table_device(ctx, handle)
+            if with_assignment:
+                assignment = assign.fragment_assign_device(ctx, handle, int(out.d_theta), hits.n_hits, d_hit_mass=d_mass)
         except Exception:
             if owner is None:
                 L.sbgpu_bins_destroy(handle)
@@ -303,6 +322,8 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
               "info": {"n_bins": int(info[2]), "n_elem": int(info[3]), "n_pairs": int(info[4])}})
     if with_context:
         r.update(context=table, bins=bins)
+    if with_assignment:
+        r.update(assignment=assignment, bins=bins)
     if bootstrap is not None:
         r.update(bootstrap=boot, bins=bins)
     if keep_handle:
