@@ -1008,6 +1008,59 @@ int sbgpu_fragment_assign_host(const sbgpu_bins_t *bins, const uint32_t *compat,
 int sbgpu_fragment_assign_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins, const double *d_theta, const float *d_hit_mass,
                                  void *stream, sbgpu_fragment_assign_t *out);
 
+/* ---- isoform-resolved coverage: per-exon depth and junction support ----------------------------------
+ * Where along an isoform its fragments lie: what is built from the fragment assignment above and the hits' features.  The rule
+ * (csrc/coverage_rules.h, shared by both forms, compiled under -ffp-contract=off).  Who is assigned, its candidates J(h) and
+ * the posterior p(j|h) ARE the fragment assignment's, under the same theta, keep, status and weights.  For locus l, an assigned
+ * hit h of mass m_h (a float; 1.0 where no masses are given) and a candidate j:
+ *   - WEIGHT  w(h,j) = (double)m_h * p(j|h), multiplied in that order;
+ *   - OVERLAP for an exon e = [L_e, R_e] of isoform j (exon_off, closed coordinates): ov(h,e) is the sum over the hit's S_MATCH
+ *     features f of max(0, min(R_e, f.right) - max(L_e, f.left) + 1), an integer; S_GAP and S_INTRON features add nothing:
+ *     only sequenced bases count;
+ *   - exon_bases[e] = sum over the assigned hits h of l with j in J(h) of w(h,j) * (double)ov(h,e); indexed as exon_left is;
+ *   - junction_mass[e], for an exon that is not its isoform's last: the sum of w(h,j) over the assigned hits with j in J(h)
+ *     that own an S_INTRON feature with left == R_e + 1 and right == L_{e+1} - 1 -- a pair whose unsequenced gap spans the
+ *     intron does not support it; exactly 0.0 for an isoform's last exon;
+ *   - iso_bases[j] = the finished exon_bases[e] of the isoform's exons, added in ascending e: a function of exon_bases' bits;
+ *   - unexplained_bases[l] = sum over the UNASSIGNED hits of l of (double)m_h * (double)matchlen(h), matchlen(h) the total
+ *     length of the hit's S_MATCH features.
+ * An isoform that is not kept, and a locus whose status is SBGPU_EM_INIT_EMPTY, get zeros; all hits of such a locus are
+ * unassigned, so they count as unexplained.  Depth is the caller's division: exon_bases[e] / (R_e - L_e + 1) per exon,
+ * iso_bases[j] / the isoform's length per isoform.
+ * The struct: host arrays to fill (any may be NULL) and, on return -- device form only -- the device arrays of all four (the
+ * context's memory: valid until its next sbgpu_quantify_* or sbgpu_isoform_coverage_device call). */
+typedef struct {
+   double *exon_bases;        /* in: [exon_off[n_iso]]                                          */
+   double *junction_mass;     /* in: [exon_off[n_iso]]                                          */
+   double *iso_bases;         /* in: [n_iso]                                                    */
+   double *unexplained_bases; /* in: [n_loci]                                                   */
+   const double *d_exon_bases, *d_junction_mass, *d_iso_bases, *d_unexplained_bases; /* out: device form only */
+} sbgpu_isoform_coverage_t;
+/* Host form, the plain statement of the rule: hits in index order, inside a hit the candidates in ascending j, inside a candidate
+ * the exons in ascending order.  `bins`, compat, F, theta, keep, status, hit_mass: as for sbgpu_fragment_assign_host, with its
+ * refusals (theta NULL, a handle that holds no hit -> bin, a bin-less hit among hits that did not come grouped by locus:
+ * SBGPU_EINVAL).  annot, hits: the host arrays the handle was made from; hits->n_hits or the annotation's loci / isoforms other
+ * than the handle's: SBGPU_EINVAL, sbgpu_last_error says which.                                                        */
+int sbgpu_isoform_coverage_host(const sbgpu_bins_t *bins, const sbgpu_annotation_t *annot, const sbgpu_hits_t *hits,
+                                const uint32_t *compat, int32_t compat_words, const double *F, const double *theta,
+                                const int32_t *keep, const int32_t *status, const float *hit_mass, sbgpu_isoform_coverage_t *out);
+/* Device form (csrc/coverage_device.h): valid exactly where sbgpu_fragment_assign_device is -- same handles, same refusals --
+ * and nothing more is retained by a resident call.  annot: HOST pointers (the context's pinned copy is used where it matches,
+ * otherwise the exon arrays are uploaded); d_hits: the DEVICE arrays the resident call was given, or sbgpu_front_stream_hits'
+ * (another n_hits than the retained call's: SBGPU_EINVAL); d_theta, d_hit_mass: as for sbgpu_fragment_assign_device.  The
+ * assignment's column pass, one pass over the hits, one over the isoforms.  The sums are added in another order than the host
+ * form's: equal within the rounding of a sum of non-negative terms, exactly where every term is an integer; iso_bases is the
+ * ascending sum of the device's own exon_bases.  The results live in a scratch slot of their own: table, assignment and
+ * coverage may be asked for in any order, repeatedly.  Only the arrays the caller gave pointers for cross PCIe.  Synchronises
+ * on `stream` (NULL: the context's own).  Loci of more than 4096 isoforms or more than 5632 bins: SBGPU_ESHAPE.       */
+int sbgpu_isoform_coverage_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins, const sbgpu_annotation_t *annot, const sbgpu_hits_t *d_hits,
+                                  const double *d_theta, const float *d_hit_mass, void *stream, sbgpu_isoform_coverage_t *out);
+/* The device form's thresholds (csrc/coverage_device.h), for callers and tests that want a locus on either side of each:
+ * out[0] hits of one work item, [1] annotated exons of a locus up to which its exon table and sums live in LDS, [2] the same
+ * number again (the isoforms that LDS has room for: no threshold of its own, an isoform owns an exon), [3] isoforms and [4] exons
+ * up to which the sums are kept in copies, [5] the copies, [6] the most bins and [7] the most isoforms of one locus.          */
+int sbgpu_isoform_coverage_limits(int64_t out[8]);
+
 /* ---- the EM bootstrap: how far theta can be trusted -------------------------
  * The reference prints theta with no statement of its spread.  The bootstrap resamples every locus' fragments over its
  * bins, solves again, and reports mean and variance of theta over the replicates.

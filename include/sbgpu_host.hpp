@@ -683,6 +683,73 @@ class FragmentAssignment {
    }
 };
 
+/* Isoform-resolved coverage (sbgpu_isoform_coverage_*, include/sbgpu.h states the rule): per annotated exon the posterior-weighted
+ * sequenced bases and -- for an exon that is not its isoform's last -- the mass of the spliced hits that support the junction
+ * behind it; per isoform the bases of its exons; per locus the bases of the hits no kept isoform explains.  host(): on a handle
+ * that holds hit -> bin, with the annotation and the hits it was made from.  device(): under FragmentAssignment::device's
+ * conditions, annot with HOST pointers, d_hits and d_hit_mass (nullptr: unit masses) the device arrays the resident call was
+ * given, d_theta normally its d_theta.  exon_depth() / iso_depth(): bases over length.                                        */
+class IsoformCoverage {
+ public:
+   std::vector<double> exon_bases, junction_mass; /* [exon_off[n_iso]] */
+   std::vector<double> iso_bases;                 /* [n_iso] */
+   std::vector<double> unexplained_bases;         /* [n_loci] */
+   sbgpu_isoform_coverage_t raw{};  /* device(): the device arrays -- the context's, valid until its next quantify or coverage call;
+                                       its host pointers are null after the call: the vectors above are the results, in a copy too */
+
+   static IsoformCoverage host(const sbgpu_bins_t *bins, const sbgpu_annotation_t &annot, const sbgpu_hits_t &hits, const uint32_t *compat,
+                               int32_t compat_words, const double *F, const double *theta, const int32_t *keep, const int32_t *status,
+                               const float *hit_mass)
+   {
+      IsoformCoverage t;
+      t.prepare(bins, annot);
+      check(sbgpu_isoform_coverage_host(bins, &annot, &hits, compat, compat_words, F, theta, keep, status, hit_mass, &t.raw), "sbgpu_isoform_coverage_host");
+      t.done();
+      return t;
+   }
+   static IsoformCoverage device(const Context &ctx, const sbgpu_bins_t *bins, const sbgpu_annotation_t &annot, const sbgpu_hits_t &d_hits,
+                                 const double *d_theta, const float *d_hit_mass = nullptr, void *stream = nullptr)
+   {
+      IsoformCoverage t;
+      t.prepare(bins, annot);
+      check(sbgpu_isoform_coverage_device(ctx.get(), bins, &annot, &d_hits, d_theta, d_hit_mass, stream, &t.raw), "sbgpu_isoform_coverage_device");
+      t.done();
+      return t;
+   }
+   std::vector<double> exon_depth(const sbgpu_annotation_t &annot) const
+   {
+      std::vector<double> d(exon_bases.size());
+      for (size_t e = 0; e < d.size(); ++e) d[e] = exon_bases[e] / ((double)annot.exon_right[e] - (double)annot.exon_left[e] + 1.0);
+      return d;
+   }
+   std::vector<double> iso_depth(const sbgpu_annotation_t &annot) const
+   {
+      std::vector<double> d(iso_bases.size(), 0.0);
+      for (size_t i = 0; i < d.size(); ++i) {
+         int64_t len = 0;
+         for (int64_t e = annot.exon_off[i]; e < annot.exon_off[i + 1]; ++e) len += (int64_t)annot.exon_right[e] - (int64_t)annot.exon_left[e] + 1;
+         if (len > 0) d[i] = iso_bases[i] / (double)len;
+      }
+      return d;
+   }
+
+ private:
+   void prepare(const sbgpu_bins_t *bins, const sbgpu_annotation_t &annot)
+   {
+      int64_t info[8];
+      check(sbgpu_bins_info(bins, info), "sbgpu_bins_info");
+      if (!annot.iso_off || !annot.exon_off || annot.n_loci != info[0] || annot.iso_off[annot.n_loci] != info[1])
+         throw std::invalid_argument("IsoformCoverage: the annotation is not the handle's");
+      const size_t n_exon = (size_t)annot.exon_off[info[1]];
+      exon_bases.assign(n_exon, 0.0), junction_mass.assign(n_exon, 0.0);
+      iso_bases.assign((size_t)info[1], 0.0), unexplained_bases.assign((size_t)info[0], 0.0);
+      raw = sbgpu_isoform_coverage_t{};
+      raw.exon_bases = exon_bases.data(), raw.junction_mass = junction_mass.data();
+      raw.iso_bases = iso_bases.data(), raw.unexplained_bases = unexplained_bases.data();
+   }
+   void done() { raw.exon_bases = raw.junction_mass = raw.iso_bases = raw.unexplained_bases = nullptr; }
+};
+
 /* The bootstrap of the resident path (sbgpu_bootstrap_keep / sbgpu_abundance_bootstrap_device, include/sbgpu.h): FPKM and TPM
  * mean, variance and percentile interval over resampled bin counts, with the replicates in which the expression filter kept
  * each isoform.  keep(): before the resident call; device(): right after it, on that call's handle.  interval_ranks(): the two

@@ -46,6 +46,7 @@ SYMBOLS = [
     "sbgpu_replicate_stats_host", "sbgpu_replicate_stats_device", "sbgpu_bootstrap_keep", "sbgpu_abundance_bootstrap_device",
     "sbgpu_locus_abundance_host", "sbgpu_locus_abundance_device", "sbgpu_locus_bootstrap_device",
     "sbgpu_fragment_assign_host", "sbgpu_fragment_assign_device",
+    "sbgpu_isoform_coverage_host", "sbgpu_isoform_coverage_device", "sbgpu_isoform_coverage_limits",
 ]
 
 
@@ -155,6 +156,11 @@ class sbgpu_fragment_assign_t(C.Structure):
     _NAMES = ("map_iso", "map_prob", "n_cand", "unique_mass", "map_mass", "post_mass", "unassigned")
     _fields_ = ([(n, C.c_void_p) for n in _NAMES] + [("n_hits", C.c_int64)] +
                 [("d_" + n, C.c_void_p) for n in ("map_iso", "map_prob", "n_cand", "unique_mass", "map_mass", "post_mass", "unassigned")])
+
+
+class sbgpu_isoform_coverage_t(C.Structure):
+    _NAMES = ("exon_bases", "junction_mass", "iso_bases", "unexplained_bases")
+    _fields_ = [(n, C.c_void_p) for n in _NAMES] + [("d_" + n, C.c_void_p) for n in _NAMES]
 
 
 class sbgpu_bootstrap_params_t(C.Structure):
@@ -338,6 +344,11 @@ def load():
     L.sbgpu_context_table_device.argtypes = [vp, vp, vp, C.POINTER(sbgpu_context_table_t)]
     L.sbgpu_fragment_assign_host.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(sbgpu_fragment_assign_t)]
     L.sbgpu_fragment_assign_device.argtypes = [vp, vp, vp, vp, vp, C.POINTER(sbgpu_fragment_assign_t)]
+    L.sbgpu_isoform_coverage_host.argtypes = [vp, C.POINTER(sbgpu_annotation_t), C.POINTER(sbgpu_hits_t), vp, C.c_int32, vp, vp, vp, vp, vp,
+                                              C.POINTER(sbgpu_isoform_coverage_t)]
+    L.sbgpu_isoform_coverage_device.argtypes = [vp, vp, C.POINTER(sbgpu_annotation_t), C.POINTER(sbgpu_hits_t), vp, vp, vp,
+                                                C.POINTER(sbgpu_isoform_coverage_t)]
+    L.sbgpu_isoform_coverage_limits.argtypes = [C.POINTER(C.c_int64)]
     L.sbgpu_bootstrap_counts_host.argtypes = [C.c_int64, vp, vp, vp, C.c_uint64, C.c_int32, vp]
     L.sbgpu_bootstrap_counts_device.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp]
     L.sbgpu_em_bootstrap_device.argtypes = [vp, vp, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp, vp, vp, vp, vp, vp]

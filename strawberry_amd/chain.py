@@ -230,7 +230,8 @@ class ChainQuantifier:
         keep_context=True (resident only): every step asks the context to keep what the `-f` table needs (sbgpu_context_table_keep,
         switched on for the step's own call only: the context may be shared) and the last step's handle lives on in
         `context_handle`; context_table() builds the table from it on the device, fragment_assignment() every hit's isoform
-        posterior (both from the same retention, in either order, repeatedly).
+        posterior, isoform_coverage() the per-exon bases and junction support (all from the same retention, in any order,
+        repeatedly).
         keep_bootstrap=True (resident only): likewise for the bootstrap (sbgpu_bootstrap_keep); abundance_bootstrap() runs it on the
         last step's handle."""
         import torch
@@ -346,6 +347,21 @@ class ChainQuantifier:
         d_mass, n_hits = self._assignment_hits()
         return assign.fragment_assign_device(self.ctx, self.context_handle, int(self._out.d_theta) if d_theta is None else d_theta, n_hits,
                                              d_hit_mass=d_mass, want=want)
+
+    def _coverage_hits(self):
+        """(the _lib.sbgpu_hits_t of device arrays the last resident call was given, the device address of their masses)"""
+        return self._ht, self.hits.mass.data_ptr()
+
+    def isoform_coverage(self, d_theta=None, want=None):
+        """Per-exon bases, per-junction mass, per-isoform bases and every locus' unexplained bases for the last step
+        (coverage.IsoformCoverage), built on the device under the step's own theta -- or d_theta, as for fragment_assignment()
+        -- and the hits' masses.  want: the arrays to bring to the host (None: all)."""
+        from . import coverage
+        if self.context_handle is None or not self.keep_context:
+            raise _lib.SbgpuError("isoform_coverage: no step has run with keep_context=True")
+        d_hits, d_mass = self._coverage_hits()
+        return coverage.isoform_coverage_device(self.ctx, self.context_handle, self.annot, d_hits, int(self._out.d_theta) if d_theta is None else d_theta,
+                                                d_hit_mass=d_mass, want=want)
 
     def abundance_bootstrap(self, n_rep, seed, **kw):
         """The bootstrap of the last step (keep_bootstrap=True): bootstrap.abundance_bootstrap_device on its handle, over this

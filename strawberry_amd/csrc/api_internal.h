@@ -178,7 +178,7 @@ hipStream_t ctx_stream(const sbgpu_ctx_t *ctx); // the context's own stream
 hipStream_t ctx_aux_stream(const sbgpu_ctx_t *ctx, int i); // one of the context's side streams (0..7; the EM's kinds use 0, 1, 2, 6)
 int ctx_cu_count(const sbgpu_ctx_t *ctx);
 int ctx_device(const sbgpu_ctx_t *ctx);        // the HIP device the context was made on
-// device scratch that lives with the context (slot 0..9; 8 is the context table's, 9 the fragment assignment's; grows on demand, never shrinks): valid until the next
+// device scratch that lives with the context (slot 0..10; 8 is the context table's, 9 the fragment assignment's, 10 the isoform coverage's; grows on demand, never shrinks): valid until the next
 // request for the same slot; one host thread per context
 hipError_t ctx_scratch(sbgpu_ctx_t *ctx, int slot, size_t bytes, char **out);
 // Device allocations that change hands (a handle's arenas, a plan's arena): a hipMalloc / hipFree pair per call costs a
@@ -264,6 +264,18 @@ struct ContextKeep {
    std::vector<int64_t> locus_hit_off;      // host copy, [n_loci + 1]
 };
 ContextKeep *ctx_context_keep(sbgpu_ctx_t *ctx);
+// assign_api.hip: the fragment assignment's column pass alone (asg_column_kernel, unchanged: the live flag of every bin, the
+// gain of every column), for a stage that builds on the assignment's posterior in a translation unit of its own
+// (coverage_api.hip).  Every pointer is device memory; row_off, iso_off, f_off: [n_loci + 1].
+struct AsgColumnPass {
+   int64_t n_loci = 0;
+   const int64_t *row_off = nullptr, *iso_off = nullptr, *f_off = nullptr;
+   const int32_t *keep = nullptr, *status = nullptr;
+   const double *F = nullptr, *theta = nullptr;
+   uint8_t *live = nullptr; // out, [n_bins]
+   double *gain = nullptr;  // out, [n_iso]
+};
+hipError_t asg_launch_column_pass(const AsgColumnPass &p, unsigned grid, hipStream_t s);
 // What the EM bootstrap (bootstrap_api.hip) reads of a plan: the totals, and the rows' offsets in device memory
 struct PlanShape {
    int64_t n_loci = 0, n_rows = 0, n_iso = 0;

@@ -13,6 +13,20 @@
 
 using sb::api_fail;
 
+namespace sb {
+hipError_t asg_launch_column_pass(const AsgColumnPass &p, unsigned grid, hipStream_t s)
+{
+   AsgArgs a{};
+   a.n_loci = p.n_loci;
+   a.row_off = p.row_off, a.iso_off = p.iso_off, a.f_off = p.f_off;
+   a.keep = p.keep, a.status = p.status;
+   a.F = p.F, a.theta = p.theta;
+   a.live = p.live, a.gain = p.gain;
+   hipLaunchKernelGGL(asg_column_kernel, dim3(grid), dim3(kAsgThreads), 0, s, a);
+   return hipGetLastError();
+}
+} // namespace sb
+
 extern "C" int sbgpu_fragment_assign_device(sbgpu_ctx_t *c, const sbgpu_bins_t *bins, const double *d_theta, const float *d_hit_mass,
                                             void *stream, sbgpu_fragment_assign_t *out)
 {

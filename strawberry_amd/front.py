@@ -155,7 +155,7 @@ class FrontQuantifier(ChainQuantifier):
         self._read_off = np.zeros(self.n_loci + 1, np.int64)
         self.stage_wall_ms = {}
         self.counts = {}
-        self._front_hits = None     # keep_context: (destroy, handle, masses' device address, hits) of the last pass' unique hits
+        self._front_hits = None     # keep_context: (destroy, handle, masses' device address, hits, their sbgpu_hits_t) of the last pass' unique hits
 
     def _release_front_hits(self):
         """keep_context: the last pass' unique hits lived on for fragment_assignment() (their masses); the next pass, or close(), lets them go."""
@@ -168,6 +168,11 @@ class FrontQuantifier(ChainQuantifier):
         if self._front_hits is None:
             raise _lib.SbgpuError("fragment_assignment: no pass has run with keep_context=True")
         return self._front_hits[2], self._front_hits[3]
+
+    def _coverage_hits(self):
+        if self._front_hits is None:
+            raise _lib.SbgpuError("isoform_coverage: no pass has run with keep_context=True")
+        return self._front_hits[4], self._front_hits[2]
 
     def close(self):
         self._release_front_hits()
@@ -237,7 +242,7 @@ class FrontQuantifier(ChainQuantifier):
             self.info = {"n_bins": int(info[2]), "n_elem": int(info[3]), "n_pairs": int(info[4]), "hits_in_bins": int(info[6])}
         self._retire(h)         # (the table reads the hits' compat words, not the hits: the unique hits' handle may go ...
         if self.keep_context:   # ... the assignment reads their masses: it lives until the next pass)
-            self._front_hits = (L.sbgpu_uniq_dev_destroy, hu, d_mass.value, int(dh.n_hits))
+            self._front_hits = (L.sbgpu_uniq_dev_destroy, hu, d_mass.value, int(dh.n_hits), dh)
         else:
             L.sbgpu_uniq_dev_destroy(hu)
         self.stage_wall_ms = ms
@@ -333,7 +338,7 @@ class FrontQuantifier(ChainQuantifier):
             if self.keep_context:   # (the store's masses are what fragment_assignment() reads: the stream lives until the next pass)
                 dh, d_mass = _lib.sbgpu_hits_t(), C.c_void_p()
                 _lib.check(L.sbgpu_front_stream_hits(fs, C.byref(dh), C.byref(d_mass), None), "sbgpu_front_stream_hits")
-                self._front_hits = (L.sbgpu_front_stream_destroy, fs, d_mass.value, int(dh.n_hits))
+                self._front_hits = (L.sbgpu_front_stream_destroy, fs, d_mass.value, int(dh.n_hits), dh)
                 kept = True
         finally:
             if not kept:

@@ -228,7 +228,7 @@ class BinsHandle:
 
 def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=False, ctx=None, device=0, comm=None,
                       min_isoform_frac=0.0, filter_by_expression=True, effective_len_norm=False, with_context=False, bootstrap=None,
-                      keep_bootstrap=False, keep_handle=False, with_assignment=False):
+                      keep_bootstrap=False, keep_handle=False, with_assignment=False, with_coverage=False):
     """sbgpu_quantify_resident on host hits brought to the device first (torch owns the copies): pass 1 (insert=None: the
     empirical insert-size law, built on the device), bins, weights, EM, FPKM / Frac / keep, the FPKM all-reduce over `comm`
     (dist.AbiComm / dist.HostComm; None: a world of one), TPM.  The hits must come grouped by locus.
@@ -236,6 +236,8 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     (context.context_table_device) -> "context"; "bins": the handle's LocusBins (the rows index its bins).
     with_assignment: the same retention, and every hit's isoform posterior under the call's theta and the hits' masses, built on
     the device (assign.fragment_assign_device) -> "assignment"; "bins" as with_context.
+    with_coverage: the same retention, and the isoform-resolved coverage under the call's theta and the hits' masses, built on the
+    device from the hits the call was given (coverage.isoform_coverage_device) -> "coverage"; "bins" as with_context.
     bootstrap = dict(n_rep=, seed=, level=0.95, locus_id=None, ...): the call keeps what the bootstrap needs (sbgpu_bootstrap_keep)
     and bootstrap.abundance_bootstrap_device runs on its handle with these arguments (and `comm`) -> "bootstrap": its dict; "bins" as above.
     With locus=True among them the bootstrap is sbgpu_locus_bootstrap_device: "bootstrap" also holds "frac" and "locus" (DESIGN 3.19).
@@ -272,7 +274,7 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     ins = insert._struct(read_len, long_read) if insert is not None else None
     handle = C.c_void_p()
     torch.cuda.synchronize(dev)
-    retain = bool(with_context) or bool(with_assignment)
+    retain = bool(with_context) or bool(with_assignment) or bool(with_coverage)
     if retain:
         _lib.check(L.sbgpu_context_table_keep(ctx.h, 1), "sbgpu_context_table_keep")
     keep_bootstrap = bool(keep_bootstrap) or bootstrap is not None
@@ -294,9 +296,9 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     owner = BinsHandle(L, handle) if keep_handle else None     # (from here on an exception frees the handle with the object)
     info = (C.c_int64 * 8)()
     _lib.check(L.sbgpu_bins_info(handle, info), "sbgpu_bins_info")
-    table = bins = boot = assignment = None
+    table = bins = boot = assignment = cov = None
     if retain or bootstrap is not None:
-        from . import assign, context
+        from . import assign, context, coverage
         from .bootstrap import abundance_bootstrap_device
         from .exonbin import LocusBins
         try:
@@ -306,6 +308,8 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
                 table = context.context_table_device(ctx, handle)
             if with_assignment:
                 assignment = assign.fragment_assign_device(ctx, handle, int(out.d_theta), hits.n_hits, d_hit_mass=d_mass)
+            if with_coverage:
+                cov = coverage.isoform_coverage_device(ctx, handle, annot, hs, int(out.d_theta), d_hit_mass=d_mass)
         except Exception:
             if owner is None:
                 L.sbgpu_bins_destroy(handle)
@@ -324,6 +328,8 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
         r.update(context=table, bins=bins)
     if with_assignment:
         r.update(assignment=assignment, bins=bins)
+    if with_coverage:
+        r.update(coverage=cov, bins=bins)
     if bootstrap is not None:
         r.update(bootstrap=boot, bins=bins)
     if keep_handle:
