@@ -1061,6 +1061,78 @@ int sbgpu_isoform_coverage_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins, co
  * up to which the sums are kept in copies, [5] the copies, [6] the most bins and [7] the most isoforms of one locus.          */
 int sbgpu_isoform_coverage_limits(int64_t out[8]);
 
+/* ---- model fit: likelihood, bin residuals, isoform scores ---------------------------------------------
+ * How well theta explains a locus' bin counts, and how converged theta is: made from the mixture mass of every exon bin, which
+ * EmSolver::run (estimate.cpp:449-476) computes each iteration and discards.  The rule (csrc/fit_rules.h, shared by both forms,
+ * compiled under -ffp-contract=off).  One locus: bins b with counts n_b (int32 >= 0), isoforms j, raw weights F[b][j], the
+ * caller's theta, keep, status.
+ *    1. kept(j), the live bins, the column scale c_j (the column's sum over the live bins in ascending order) and the gain
+ *       g_j = theta_j / c_j ARE the fragment assignment's above (ctx_kept_word, asg_row_live, asg_gain).
+ *    2. d_b = the sum over the kept j, ascending, of g_j * F[b][j] for a live bin, 0.0 otherwise: the bin's mixture mass in count
+ *       units, the `den` of a hit compatible with every kept isoform.
+ *    3. A live bin is POSSIBLE when d_b > 0.
+ *    4. n_live[l] = sum of n_b over the live bins; n_dropped[l] = the same over the bins that are not live (the rows
+ *       EmSolver::init drops); n_impossible[l] = the same over the live bins that are not possible (fragments to which the kept
+ *       isoforms give probability zero: after the expression filter erased an isoform, or under SBGPU_EM_DENOM_ZERO);
+ *       M = n_live - n_impossible; D = sum of d_b over the possible bins.
+ *    5. expected[b] = (double)M * (d_b / D) for a possible bin, 0.0 otherwise.
+ *    6. resid[b] = ((double)n_b - expected[b]) / sqrt(expected[b]) where expected[b] > 0, 0.0 otherwise.
+ *    7. loglik[l] = sum of (double)n_b * log(d_b / D) over the possible bins with n_b > 0: the multinomial log-likelihood
+ *       without its constant.
+ *    8. deviance[l] = 2 * sum of (double)n_b * log((double)n_b / expected[b]) over the same bins.
+ *    9. pearson[l] = sum of resid[b]^2 over the possible bins: a function of resid's bits.
+ *   10. dof[l] = max(0, P - 1 - max(0, A - 1)), P the number of possible bins, A the number of isoforms with g_j > 0.
+ *   11. worst_bin[l] = the locus-local index of the possible bin of largest |resid| under strict > in ascending order (the
+ *       lowest index wins a tie; a NaN never wins); -1 when there is none.
+ *   12. score[j] = (sum over the possible b, ascending, of ((double)n_b / d_b) * F[b][j]) / c_j for a kept isoform with
+ *       c_j != 0, 0.0 otherwise; the ratio first, then the product, the division by c_j last.  theta[j] * score[j] is the
+ *       M-step's next theta[j] on the column-normalised F, so score[j] = 1 for every theta[j] > 0 at the optimum, and
+ *       || theta o score - theta ||_2 per locus is the distance the reference's stopping rule (SBGPU_EM_THETA_CHANGE_LIMIT)
+ *       looks at.
+ * A locus whose status is SBGPU_EM_INIT_EMPTY, or with nothing kept: all zeros, dof 0, worst_bin -1, and n_dropped counts ALL
+ * its fragments, live row or not: none of them entered a fit.  p-values are the caller's: dof and the two statistics are what
+ * they need.
+ * The struct: host arrays to fill (any may be NULL) and, on return -- device forms only -- the device arrays of all of them:
+ * the context's memory, in a scratch slot of their own, valid until the context's next sbgpu_quantify_* or fit call.        */
+typedef struct {
+   double *expected, *resid;                       /* in: [n_bins]  */
+   double *score;                                  /* in: [n_iso]   */
+   double *loglik, *deviance, *pearson;            /* in: [n_loci]  */
+   int64_t *n_live, *n_dropped, *n_impossible;     /* in: [n_loci]  */
+   int32_t *dof, *worst_bin;                       /* in: [n_loci]  */
+   const double *d_expected, *d_resid, *d_score, *d_loglik, *d_deviance, *d_pearson; /* out: device forms only */
+   const int64_t *d_n_live, *d_n_dropped, *d_n_impossible;
+   const int32_t *d_dof, *d_worst_bin;
+} sbgpu_em_fit_t;
+/* Host form (csrc/fit_host.cpp; no GPU needed), the plain statement of the rule: every sum in ascending order.  theta [n_iso];
+ * keep [n_iso] or NULL: everything kept; status [n_loci] or NULL: every locus started.  SBGPU_EINVAL, with the reason in
+ * sbgpu_last_error: a NULL theta, a negative count, malformed offsets (not beginning at 0, not ascending, f_off not rows x
+ * isoforms), NULL count / F where there are bins / weights.                                                             */
+int sbgpu_em_fit_host(const sbgpu_batch_t *batch, const double *theta, const int32_t *keep, const int32_t *status, sbgpu_em_fit_t *out);
+/* Device form (csrc/fit_device.h) for any batch sbgpu_em_run_device solves: the plan, d_count and d_F as given to it; d_theta:
+ * any device [n_iso] array (the EM's, or a bootstrap mean); d_keep / d_status: device arrays or NULL, as above.  The
+ * assignment's column pass (unchanged), then one pass that reads F twice: a wave per locus of at most out[0] weights of
+ * sbgpu_em_fit_limits, a workgroup per larger locus.  d_b and the score's inner sum run in the rule's order: the integer arrays,
+ * the zeros and which bins are possible are the host form's exactly; D, loglik, deviance and pearson are added along a fixed
+ * tree (csrc/fit_device.h states it): equal to the host form within the rounding of another order, the same bits from call to
+ * call; pearson is that tree over the device's own resid, worst_bin the argmax of the device's own resid.  Only the arrays
+ * the caller gave pointers for cross PCIe.  Synchronises on `stream` (NULL: the context's own).  Loci of more than 4096
+ * isoforms or more than 5632 bins: SBGPU_ESHAPE.  A NULL d_theta: SBGPU_EINVAL.                                          */
+int sbgpu_em_fit_device(sbgpu_ctx_t *ctx, const sbgpu_plan_t *plan, const int32_t *d_count, const double *d_F, const double *d_theta,
+                        const int32_t *d_keep, const int32_t *d_status, void *stream, sbgpu_em_fit_t *out);
+/* The same right after a resident call or an sbgpu_front_stream_end made with sbgpu_bootstrap_keep on, from that record (the
+ * call's plan, counts and weights): nothing more is retained, and the call's seven results are the same bits with and without a
+ * fit call behind it.  A handle made without retention, or a stale one: SBGPU_EINVAL, as for
+ * sbgpu_abundance_bootstrap_device.  Fit, table, assignment and coverage may be asked for in any order.                  */
+int sbgpu_model_fit_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins, const double *d_theta, const int32_t *d_keep, const int32_t *d_status,
+                           void *stream, sbgpu_em_fit_t *out);
+/* The device form's thresholds (csrc/fit_device.h), for callers and tests that want a locus on either side of each: out[0]
+ * weights (and bins, and isoforms) of a locus up to which a wave serves it, a workgroup beyond; [1] weights up to which the
+ * workgroup form stages F in LDS, global memory beyond; [2] loci per workgroup in the wave form; [3] workgroups per CU a launch's
+ * grid is capped at; [4] threads of a workgroup; [5] of a wave (the reduction tree's two levels); [6] the most bins and [7] the
+ * most isoforms of one locus.                                                                                              */
+int sbgpu_em_fit_limits(int64_t out[8]);
+
 /* ---- the EM bootstrap: how far theta can be trusted -------------------------
  * The reference prints theta with no statement of its spread.  The bootstrap resamples every locus' fragments over its
  * bins, solves again, and reports mean and variance of theta over the replicates.

@@ -750,6 +750,83 @@ class IsoformCoverage {
    void done() { raw.exon_bases = raw.junction_mass = raw.iso_bases = raw.unexplained_bases = nullptr; }
 };
 
+/* The model fit (sbgpu_em_fit_* / sbgpu_model_fit_device, include/sbgpu.h states the rule): expected counts and Pearson residuals
+ * per bin, the EM's score per isoform, likelihood, deviance, Pearson statistic, fragment counts, degrees of freedom and the worst
+ * bin per locus.  host(): any batch with theta (keep / status: nullptr = everything kept / every locus started); no GPU.
+ * device(plan, ...): for a batch sbgpu_em_run_device solves, on its device arrays; device(bins, ...): right after a resident call
+ * made with AbundanceBootstrap::keep on, on that call's handle.  reduced_chi2(): pearson / dof, NaN where dof is 0.           */
+class ModelFit {
+ public:
+   std::vector<double> expected, resid;                  /* [n_bins] */
+   std::vector<double> score;                            /* [n_iso] */
+   std::vector<double> loglik, deviance, pearson;        /* [n_loci] */
+   std::vector<int64_t> n_live, n_dropped, n_impossible; /* [n_loci] */
+   std::vector<int32_t> dof, worst_bin;                  /* [n_loci] */
+   sbgpu_em_fit_t raw{};  /* device(): the device arrays -- the context's, valid until its next quantify or fit call; its host
+                             pointers are null after the call: the vectors above are the results, in a copy too */
+
+   static ModelFit host(const sbgpu_batch_t &batch, const double *theta, const int32_t *keep = nullptr, const int32_t *status = nullptr)
+   {
+      if (batch.n_loci < 0 || !batch.row_off || !batch.iso_off) throw std::invalid_argument("ModelFit::host: bad n_loci or null offset array");
+      ModelFit t;
+      t.prepare(batch.n_loci, batch.row_off[batch.n_loci], batch.iso_off[batch.n_loci]);
+      check(sbgpu_em_fit_host(&batch, theta, keep, status, &t.raw), "sbgpu_em_fit_host");
+      t.done();
+      return t;
+   }
+   static ModelFit device(const Context &ctx, const sbgpu_plan_t *plan, const int32_t *d_count, const double *d_F, const double *d_theta,
+                          const int32_t *d_keep = nullptr, const int32_t *d_status = nullptr, void *stream = nullptr)
+   {
+      int64_t info[8];
+      check(sbgpu_plan_info(plan, info), "sbgpu_plan_info");
+      ModelFit t;
+      t.prepare(info[0], info[1], info[2]);
+      check(sbgpu_em_fit_device(ctx.get(), plan, d_count, d_F, d_theta, d_keep, d_status, stream, &t.raw), "sbgpu_em_fit_device");
+      t.done();
+      return t;
+   }
+   static ModelFit device(const Context &ctx, const sbgpu_bins_t *bins, const double *d_theta, const int32_t *d_keep = nullptr,
+                          const int32_t *d_status = nullptr, void *stream = nullptr)
+   {
+      int64_t info[8];
+      check(sbgpu_bins_info(bins, info), "sbgpu_bins_info");
+      ModelFit t;
+      t.prepare(info[0], info[2], info[1]);
+      check(sbgpu_model_fit_device(ctx.get(), bins, d_theta, d_keep, d_status, stream, &t.raw), "sbgpu_model_fit_device");
+      t.done();
+      return t;
+   }
+   std::vector<double> reduced_chi2() const
+   {
+      std::vector<double> x(pearson.size());
+      for (size_t l = 0; l < x.size(); ++l) x[l] = dof[l] > 0 ? pearson[l] / (double)dof[l] : std::nan("");
+      return x;
+   }
+
+ private:
+   void prepare(int64_t n_loci, int64_t n_bins, int64_t n_iso)
+   {
+      const size_t nl = (size_t)n_loci + 1, nb = (size_t)n_bins + 1, ni = (size_t)n_iso + 1; /* (one spare entry: data() of an empty vector may be null) */
+      expected.assign(nb, 0.0), resid.assign(nb, 0.0), score.assign(ni, 0.0);
+      loglik.assign(nl, 0.0), deviance.assign(nl, 0.0), pearson.assign(nl, 0.0);
+      n_live.assign(nl, 0), n_dropped.assign(nl, 0), n_impossible.assign(nl, 0);
+      dof.assign(nl, 0), worst_bin.assign(nl, -1);
+      raw = sbgpu_em_fit_t{};
+      raw.expected = expected.data(), raw.resid = resid.data(), raw.score = score.data();
+      raw.loglik = loglik.data(), raw.deviance = deviance.data(), raw.pearson = pearson.data();
+      raw.n_live = n_live.data(), raw.n_dropped = n_dropped.data(), raw.n_impossible = n_impossible.data();
+      raw.dof = dof.data(), raw.worst_bin = worst_bin.data();
+   }
+   void done()
+   {
+      raw.expected = raw.resid = raw.score = raw.loglik = raw.deviance = raw.pearson = nullptr;
+      raw.n_live = raw.n_dropped = raw.n_impossible = nullptr;
+      raw.dof = raw.worst_bin = nullptr;
+      expected.pop_back(), resid.pop_back(), score.pop_back(), loglik.pop_back(), deviance.pop_back(), pearson.pop_back();
+      n_live.pop_back(), n_dropped.pop_back(), n_impossible.pop_back(), dof.pop_back(), worst_bin.pop_back();
+   }
+};
+
 /* The bootstrap of the resident path (sbgpu_bootstrap_keep / sbgpu_abundance_bootstrap_device, include/sbgpu.h): FPKM and TPM
  * mean, variance and percentile interval over resampled bin counts, with the replicates in which the expression filter kept
  * each isoform.  keep(): before the resident call; device(): right after it, on that call's handle.  interval_ranks(): the two

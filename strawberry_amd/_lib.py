@@ -47,6 +47,7 @@ SYMBOLS = [
     "sbgpu_locus_abundance_host", "sbgpu_locus_abundance_device", "sbgpu_locus_bootstrap_device",
     "sbgpu_fragment_assign_host", "sbgpu_fragment_assign_device",
     "sbgpu_isoform_coverage_host", "sbgpu_isoform_coverage_device", "sbgpu_isoform_coverage_limits",
+    "sbgpu_em_fit_host", "sbgpu_em_fit_device", "sbgpu_model_fit_device", "sbgpu_em_fit_limits",
 ]
 
 
@@ -160,6 +161,11 @@ class sbgpu_fragment_assign_t(C.Structure):
 
 class sbgpu_isoform_coverage_t(C.Structure):
     _NAMES = ("exon_bases", "junction_mass", "iso_bases", "unexplained_bases")
+    _fields_ = [(n, C.c_void_p) for n in _NAMES] + [("d_" + n, C.c_void_p) for n in _NAMES]
+
+
+class sbgpu_em_fit_t(C.Structure):
+    _NAMES = ("expected", "resid", "score", "loglik", "deviance", "pearson", "n_live", "n_dropped", "n_impossible", "dof", "worst_bin")
     _fields_ = [(n, C.c_void_p) for n in _NAMES] + [("d_" + n, C.c_void_p) for n in _NAMES]
 
 
@@ -349,6 +355,10 @@ def load():
     L.sbgpu_isoform_coverage_device.argtypes = [vp, vp, C.POINTER(sbgpu_annotation_t), C.POINTER(sbgpu_hits_t), vp, vp, vp,
                                                 C.POINTER(sbgpu_isoform_coverage_t)]
     L.sbgpu_isoform_coverage_limits.argtypes = [C.POINTER(C.c_int64)]
+    L.sbgpu_em_fit_host.argtypes = [C.POINTER(sbgpu_batch_t), vp, vp, vp, C.POINTER(sbgpu_em_fit_t)]
+    L.sbgpu_em_fit_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(sbgpu_em_fit_t)]
+    L.sbgpu_model_fit_device.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(sbgpu_em_fit_t)]
+    L.sbgpu_em_fit_limits.argtypes = [C.POINTER(C.c_int64)]
     L.sbgpu_bootstrap_counts_host.argtypes = [C.c_int64, vp, vp, vp, C.c_uint64, C.c_int32, vp]
     L.sbgpu_bootstrap_counts_device.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp]
     L.sbgpu_em_bootstrap_device.argtypes = [vp, vp, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp, vp, vp, vp, vp, vp]

@@ -178,7 +178,7 @@ hipStream_t ctx_stream(const sbgpu_ctx_t *ctx); // the context's own stream
 hipStream_t ctx_aux_stream(const sbgpu_ctx_t *ctx, int i); // one of the context's side streams (0..7; the EM's kinds use 0, 1, 2, 6)
 int ctx_cu_count(const sbgpu_ctx_t *ctx);
 int ctx_device(const sbgpu_ctx_t *ctx);        // the HIP device the context was made on
-// device scratch that lives with the context (slot 0..10; 8 is the context table's, 9 the fragment assignment's, 10 the isoform coverage's; grows on demand, never shrinks): valid until the next
+// device scratch that lives with the context (slot 0..11; 8 is the context table's, 9 the fragment assignment's, 10 the isoform coverage's, 11 the model fit's; grows on demand, never shrinks): valid until the next
 // request for the same slot; one host thread per context
 hipError_t ctx_scratch(sbgpu_ctx_t *ctx, int slot, size_t bytes, char **out);
 // Device allocations that change hands (a handle's arenas, a plan's arena): a hipMalloc / hipFree pair per call costs a
@@ -276,11 +276,13 @@ struct AsgColumnPass {
    double *gain = nullptr;  // out, [n_iso]
 };
 hipError_t asg_launch_column_pass(const AsgColumnPass &p, unsigned grid, hipStream_t s);
-// What the EM bootstrap (bootstrap_api.hip) reads of a plan: the totals, and the rows' offsets in device memory
+// What the EM bootstrap (bootstrap_api.hip) and the model fit (fit_api.hip) read of a plan: the totals and the offsets
 struct PlanShape {
    int64_t n_loci = 0, n_rows = 0, n_iso = 0;
    const int64_t *d_row_off = nullptr; // device, [n_loci + 1]
    const int64_t *d_iso_off = nullptr; // device, [n_loci + 1]
+   const int64_t *d_f_off = nullptr;   // device, [n_loci + 1]
+   const int64_t *row_off = nullptr, *iso_off = nullptr; // host, [n_loci + 1]: the plan's own copies
 };
 PlanShape plan_shape(const sbgpu_plan_t *plan);
 // The bootstrap's working set: one block from the pool (sb::dev_take) that stays with the context -- the call is asynchronous, and

@@ -68,8 +68,8 @@ struct sbgpu_ctx {
    int n_phase_timed = 0;
    // grow-only device scratch of the multi-stage entry points (a hipMalloc / hipFree pair of a few GB per call costs
    // tens to hundreds of milliseconds): sb::ctx_scratch
-   char *scratch[11] = {};
-   size_t scratch_bytes[11] = {};
+   char *scratch[12] = {};
+   size_t scratch_bytes[12] = {};
    int32_t *d_pdf_support = nullptr; // [5] device: support of the insert-size table of the bin-weight launch in flight (pdf_support_kernel)
    int32_t *wide_error = nullptr; // pinned host word the wide-locus kernel raises when a barrier times out
    // kernel stages of the chain entry points, bracketed by events while `timing` is on (sb::ctx_stage_begin / _end)
@@ -298,10 +298,11 @@ void ctx_set_pairs_hint(sbgpu_ctx_t *ctx, size_t bytes) { ctx->pairs_hint = byte
 hipError_t ctx_scratch(sbgpu_ctx_t *ctx, int slot, size_t bytes, char **out)
 {
    *out = nullptr;
-   if (slot < 0 || slot >= 11) return hipErrorInvalidValue;
+   if (slot < 0 || slot >= 12) return hipErrorInvalidValue;
    // what a resident call kept for sbgpu_context_table_device lies in slots 0..7: whoever asks for one of them (any entry that
    // works in the context's scratch, not only sbgpu_quantify_*) may overwrite or free it, so the record ends here
-   // (8, 9 and 10 hold what is made FROM the record: the context table, the fragment assignment, the isoform coverage)
+   // (8, 9, 10 and 11 hold what is made FROM the record: the context table, the fragment assignment, the isoform coverage,
+   // the model fit)
    if (slot < 8) ctx->context_keep.serial = 0, ctx->boot_keep.serial = 0;
    if (bytes < 256) bytes = 256;
    if (ctx->scratch_bytes[slot] < bytes) {
@@ -377,6 +378,7 @@ struct sbgpu_plan {
    char *d_arena = nullptr;            // one allocation (sb::dev_take), one upload: the arrays below point into it
    size_t arena_cap = 0;
    int64_t *d_row_off = nullptr, *d_iso_off = nullptr, *d_f_off = nullptr;
+   std::vector<int64_t> h_row_off, h_iso_off; // host copies, [n_loci + 1]: what the model fit sorts the loci by (sb::plan_shape)
    int32_t *d_loci_all = nullptr;      // all class lists, concatenated (input of phase 0)
    int32_t *d_class_n = nullptr;       // loci per class (input count of phase 0)
    char *d_zero = nullptr;             // the later phases' survivor counts and batch totals: zeroed before every run
@@ -417,7 +419,8 @@ PlanShape plan_shape(const sbgpu_plan_t *plan)
 {
    PlanShape s;
    s.n_loci = plan->host.n_loci, s.n_rows = plan->host.n_rows, s.n_iso = plan->host.n_iso;
-   s.d_row_off = plan->d_row_off, s.d_iso_off = plan->d_iso_off;
+   s.d_row_off = plan->d_row_off, s.d_iso_off = plan->d_iso_off, s.d_f_off = plan->d_f_off;
+   s.row_off = plan->h_row_off.data(), s.iso_off = plan->h_iso_off.data();
    return s;
 }
 } // namespace sb
@@ -674,7 +677,7 @@ int sbgpu_finalize(sbgpu_ctx_t *c)
       for (hipEvent_t e : ev)
          if (e) (void)hipEventDestroy(e);
    if (c->d_pdf_support) (void)hipFree(c->d_pdf_support);
-   for (int i = 0; i < 11; ++i)
+   for (int i = 0; i < 12; ++i)
       if (c->scratch[i]) (void)hipFree(c->scratch[i]);
    for (int i = 0; i < 4; ++i)
       if (c->pinned[i]) (void)hipHostFree(c->pinned[i]);
@@ -775,6 +778,8 @@ int sbgpu_plan_create(sbgpu_ctx_t *c, int64_t n_loci, const int64_t *row_off, co
       delete p;
       return fail(rc, err);
    }
+   if (n_loci > 0) p->h_row_off.assign(row_off, row_off + n_loci + 1), p->h_iso_off.assign(iso_off, iso_off + n_loci + 1);
+   else p->h_row_off.assign(1, 0), p->h_iso_off.assign(1, 0);
    auto bail = [&](hipError_t e, const char *what) {
       sbgpu_plan_destroy(p);
       return fail(e == hipErrorOutOfMemory ? SBGPU_ENOMEM : SBGPU_EHIP, std::string(what) + ": " + hipGetErrorString(e));

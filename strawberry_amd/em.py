@@ -258,6 +258,15 @@ class EmBatchSolver:
             out["theta"], out["status"], out["iters"] = out["theta"][:, :k], out["status"][:, :n], out["iters"][:, :n]
         return out
 
+    def run_fit(self, d_theta=None, d_keep=None, d_status=None, want=None):
+        """The model fit of the batch (sbgpu_em_fit_device; fit.py): expected counts and residuals per bin, the EM's score per
+        isoform, likelihood, deviance, Pearson statistic and degrees of freedom per locus, under the last run_em's theta and
+        status -- or d_theta / d_status, device tensors of another estimate -- and d_keep (None: every isoform kept; the
+        epilogue's is self.d_keep).  Synchronises on torch's current stream -> a fit.ModelFit of host arrays (want: which)."""
+        from . import fit
+        return fit.em_fit_device(self.ctx, self.plan, self.d_count, self.d_F, self.d_theta if d_theta is None else d_theta, d_keep,
+                                 self.d_status if d_status is None else d_status, stream=self._stream(), want=want)
+
     def bootstrap_counts(self, n_rep, seed, rep_first=0, locus_id=None):
         """The replicates' counts alone (sbgpu_bootstrap_counts_device) -> int32 device tensor [n_rep, total rows]"""
         n = self.batch.n_loci
