@@ -12,52 +12,33 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._results import Results, addr, as_array, bins_info, check_lengths, check_tensors, ptr
 
 PER_HIT = (("map_iso", np.int32), ("map_prob", np.float64), ("n_cand", np.int32))
 PER_ISO = (("unique_mass", np.float64), ("map_mass", np.float64), ("post_mass", np.float64))
 
 
-class FragmentAssignment:
+class FragmentAssignment(Results):
     """map_iso / map_prob / n_cand [n_hits]; unique_mass / map_mass / post_mass [n_iso]; unassigned [n_loci] (int64).
-    want: the names to bring to the host (None: all) -- the device form copies nothing else over PCIe; the others are None."""
+    want: the names to bring to the host (None: all) -- the device form copies nothing else over PCIe; the others are None.
+    .device: name -> device address of the context's copy (device form; valid until its next quantify / assignment call)."""
+    STRUCT = _lib.sbgpu_fragment_assign_t
 
     def __init__(self, n_hits, n_iso, n_loci, want=None):
         sizes = {k: (n_hits, dt) for k, dt in PER_HIT}
         sizes.update({k: (n_iso, dt) for k, dt in PER_ISO})
         sizes["unassigned"] = (n_loci, np.int64)
-        unknown = set(want or ()) - set(sizes)
-        if unknown:
-            raise ValueError("FragmentAssignment: unknown arrays %s" % sorted(unknown))
-        self._sizes = sizes
-        for k, (n, dt) in sizes.items():
-            setattr(self, k, np.zeros(max(n, 1), dt) if want is None or k in want else None)
+        self._arrays(sizes, want)
         self.n_hits = 0
-        self.device = {}     # device form: name -> device address of the context's copy (valid until its next quantify / assignment call)
 
     def _struct(self):
-        s = _lib.sbgpu_fragment_assign_t()
-        for k in self._sizes:
-            a = getattr(self, k)
-            setattr(s, k, None if a is None else a.ctypes.data)
+        s = super()._struct()
         s.n_hits = self._sizes["map_iso"][0]     # (the library refuses another count before it writes)
         return s
 
     def _finish(self, s):
         self.n_hits = int(s.n_hits)
-        for k, (n, _) in self._sizes.items():
-            a = getattr(self, k)
-            if a is not None:
-                setattr(self, k, a[:n])
-            p = getattr(s, "d_" + k)
-            if p:
-                self.device[k] = int(p)
-        return self
-
-
-def _sizes(L, handle):
-    info = (C.c_int64 * 8)()
-    _lib.check(L.sbgpu_bins_info(handle, info), "sbgpu_bins_info")
-    return int(info[0]), int(info[1])
+        return super()._finish(s)
 
 
 def fragment_assign_host(handle, compat, theta, F=None, keep=None, status=None, hit_mass=None, want=None):
@@ -66,18 +47,15 @@ def fragment_assign_host(handle, compat, theta, F=None, keep=None, status=None, 
     keep [n_iso] / status [n_loci] (None: all kept / all started); hit_mass [n_hits] float32 (None: 1.0 each)."""
     L = _lib.load()
     handle = getattr(handle, "h", handle)
-    n_loci, n_iso = _sizes(L, handle)
+    n_loci, n_iso = bins_info(L, handle)[:2]
     compat = np.ascontiguousarray(compat, np.uint32)
     cw = compat.shape[1] if compat.ndim == 2 else 1
     n_hits = compat.shape[0] if compat.ndim == 2 else compat.size
-    as_ = lambda a, dt: None if a is None else np.ascontiguousarray(a, dt)  # noqa: E731
-    theta, F, keep, status, hit_mass = as_(theta, np.float64), as_(F, np.float64), as_(keep, np.int32), as_(status, np.int32), as_(hit_mass, np.float32)
-    for name, a, n in (("theta", theta, n_iso), ("keep", keep, n_iso), ("status", status, n_loci), ("hit_mass", hit_mass, n_hits)):
-        if a is not None and a.size < n:
-            raise ValueError("fragment_assign_host: %s holds %d entries, %d are needed" % (name, a.size, n))
+    theta, F, keep, status = as_array(theta, np.float64), as_array(F, np.float64), as_array(keep, np.int32), as_array(status, np.int32)
+    hit_mass = as_array(hit_mass, np.float32)
+    check_lengths("fragment_assign_host", ("theta", theta, n_iso), ("keep", keep, n_iso), ("status", status, n_loci), ("hit_mass", hit_mass, n_hits))
     t = FragmentAssignment(n_hits, n_iso, n_loci, want)
     s = t._struct()
-    ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data  # noqa: E731
     _lib.check(L.sbgpu_fragment_assign_host(handle, ptr(compat), cw, ptr(F), ptr(theta), ptr(keep), ptr(status), ptr(hit_mass), C.byref(s)),
                "sbgpu_fragment_assign_host")
     return t._finish(s)
@@ -90,11 +68,8 @@ def fragment_assign_device(ctx, handle, d_theta, n_hits, d_hit_mass=None, stream
     call was given, or None for unit masses."""
     L = ctx.L
     handle = getattr(handle, "h", handle)
-    n_loci, n_iso = _sizes(L, handle)
-    addr = lambda x: None if x is None else (int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x))  # noqa: E731
-    for name, x, dt in (("d_theta", d_theta, "torch.float64"), ("d_hit_mass", d_hit_mass, "torch.float32")):
-        if hasattr(x, "data_ptr") and (str(x.dtype) != dt or not x.is_cuda or not x.is_contiguous()):
-            raise ValueError("fragment_assign_device: %s must be a contiguous %s tensor on the context's device" % (name, dt))
+    n_loci, n_iso = bins_info(L, handle)[:2]
+    check_tensors("fragment_assign_device", d_theta=(d_theta, "torch.float64"), d_hit_mass=(d_hit_mass, "torch.float32"))
     t = FragmentAssignment(int(n_hits), n_iso, n_loci, want)
     s = t._struct()
     _lib.check(L.sbgpu_fragment_assign_device(ctx.h, handle, addr(d_theta), addr(d_hit_mass), stream, C.byref(s)), "sbgpu_fragment_assign_device")

@@ -18,6 +18,7 @@ from fractions import Fraction
 import numpy as np
 
 from . import _lib
+from ._results import bins_info
 
 MAX_DEVICE_REP = 1024     # sbgpu_replicate_stats_device / sbgpu_abundance_bootstrap_device: above it SBGPU_ESHAPE
 
@@ -93,9 +94,7 @@ def abundance_bootstrap_device(ctx, handle, n_rep, seed, level=0.95, rep_first=0
     replicates in which the locus kept an isoform; with replicates fpkm_rep / kept_rep [n_rep, n_loci])."""
     L = ctx.L
     handle = getattr(handle, "h", handle)      # (a quantify.BinsHandle, or the raw handle)
-    info = (C.c_int64 * 8)()
-    _lib.check(L.sbgpu_bins_info(handle, info), "sbgpu_bins_info")
-    nl, n_iso, B = int(info[0]), int(info[1]), int(n_rep)
+    (nl, n_iso), B = bins_info(L, handle)[:2], int(n_rep)
     lo, hi = interval_ranks(B, level) if ranks is None else (int(ranks[0]), int(ranks[1]))
     ids = None if locus_id is None else np.ascontiguousarray(locus_id, np.int64)
     if ids is not None and ids.shape != (nl,):

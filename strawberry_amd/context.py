@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._results import as_array, bins_info, ptr
 from .output import CONTEXT_HEADER, context_row
 
 
@@ -48,9 +49,8 @@ class ContextTable:
 
 
 def _sizes(L, handle):
-    info = (C.c_int64 * 8)()
-    _lib.check(L.sbgpu_bins_info(handle, info), "sbgpu_bins_info")
-    return int(info[0]), int(info[2]), int(info[3])
+    n_loci, _, n_bins, n_elem = bins_info(L, handle)[:4]
+    return n_loci, n_bins, n_elem
 
 
 def context_table_host(handle, compat, F=None, keep=None, status=None):
@@ -60,12 +60,9 @@ def context_table_host(handle, compat, F=None, keep=None, status=None):
     n_loci, n_bins, n_elem = _sizes(L, handle)
     compat = np.ascontiguousarray(compat, np.uint32)
     cw = compat.shape[1] if compat.ndim == 2 else 1
-    F = None if F is None else np.ascontiguousarray(F, np.float64)
-    keep = None if keep is None else np.ascontiguousarray(keep, np.int32)
-    status = None if status is None else np.ascontiguousarray(status, np.int32)
+    F, keep, status = as_array(F, np.float64), as_array(keep, np.int32), as_array(status, np.int32)
     t = ContextTable(n_loci, n_bins, n_elem)
     s = t._struct()
-    ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data  # noqa: E731
     _lib.check(L.sbgpu_context_table_host(handle, ptr(compat), cw, ptr(F), ptr(keep), ptr(status), C.byref(s)),
                "sbgpu_context_table_host")
     return t._finish(s, n_elem)

@@ -13,6 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._results import Results, addr, as_array, bins_info, check_lengths, check_tensors, ptr
 
 NAMES = ("exon_bases", "junction_mass", "iso_bases", "unexplained_bases")
 LIMIT_NAMES = ("item_hits", "lds_exons", "lds_iso", "narrow_iso", "copy_exons", "copies", "max_bins", "max_iso")
@@ -25,36 +26,14 @@ def limits():
     return dict(zip(LIMIT_NAMES, (int(x) for x in out)))
 
 
-class IsoformCoverage:
+class IsoformCoverage(Results):
     """exon_bases / junction_mass [n_exon]; iso_bases [n_iso]; unexplained_bases [n_loci] (float64).
-    want: the names to bring to the host (None: all) -- the device form copies nothing else over PCIe; the others are None."""
+    want: the names to bring to the host (None: all) -- the device form copies nothing else over PCIe; the others are None.
+    .device: name -> device address of the context's copy (device form; valid until its next quantify / coverage call)."""
+    STRUCT = _lib.sbgpu_isoform_coverage_t
 
     def __init__(self, n_exon, n_iso, n_loci, want=None):
-        sizes = {"exon_bases": n_exon, "junction_mass": n_exon, "iso_bases": n_iso, "unexplained_bases": n_loci}
-        unknown = set(want or ()) - set(sizes)
-        if unknown:
-            raise ValueError("IsoformCoverage: unknown arrays %s" % sorted(unknown))
-        self._sizes = sizes
-        for k, n in sizes.items():
-            setattr(self, k, np.zeros(max(n, 1), np.float64) if want is None or k in want else None)
-        self.device = {}     # device form: name -> device address of the context's copy (valid until its next quantify / coverage call)
-
-    def _struct(self):
-        s = _lib.sbgpu_isoform_coverage_t()
-        for k in self._sizes:
-            a = getattr(self, k)
-            setattr(s, k, None if a is None else a.ctypes.data)
-        return s
-
-    def _finish(self, s):
-        for k, n in self._sizes.items():
-            a = getattr(self, k)
-            if a is not None:
-                setattr(self, k, a[:n])
-            p = getattr(s, "d_" + k)
-            if p:
-                self.device[k] = int(p)
-        return self
+        self._arrays({k: (n, np.float64) for k, n in zip(NAMES, (n_exon, n_exon, n_iso, n_loci))}, want)
 
     def exon_depth(self, annot):
         """exon_bases[e] / (R_e - L_e + 1)"""
@@ -82,9 +61,8 @@ class IsoformCoverage:
 
 
 def _sizes(L, handle, annot):
-    info = (C.c_int64 * 8)()
-    _lib.check(L.sbgpu_bins_info(handle, info), "sbgpu_bins_info")
-    return int(np.asarray(annot.exon_off)[-1]), int(info[1]), int(info[0])
+    n_loci, n_iso = bins_info(L, handle)[:2]
+    return int(np.asarray(annot.exon_off)[-1]), n_iso, n_loci
 
 
 def isoform_coverage_host(handle, annot, hits, compat, theta, F=None, keep=None, status=None, hit_mass=None, want=None):
@@ -96,14 +74,11 @@ def isoform_coverage_host(handle, annot, hits, compat, theta, F=None, keep=None,
     compat = np.ascontiguousarray(compat, np.uint32)
     cw = compat.shape[1] if compat.ndim == 2 else 1
     n_hits = compat.shape[0] if compat.ndim == 2 else compat.size
-    as_ = lambda a, dt: None if a is None else np.ascontiguousarray(a, dt)  # noqa: E731
-    theta, F, keep, status, hit_mass = as_(theta, np.float64), as_(F, np.float64), as_(keep, np.int32), as_(status, np.int32), as_(hit_mass, np.float32)
-    for name, a, n in (("theta", theta, n_iso), ("keep", keep, n_iso), ("status", status, n_loci), ("hit_mass", hit_mass, n_hits)):
-        if a is not None and a.size < n:
-            raise ValueError("isoform_coverage_host: %s holds %d entries, %d are needed" % (name, a.size, n))
+    theta, F, keep, status = as_array(theta, np.float64), as_array(F, np.float64), as_array(keep, np.int32), as_array(status, np.int32)
+    hit_mass = as_array(hit_mass, np.float32)
+    check_lengths("isoform_coverage_host", ("theta", theta, n_iso), ("keep", keep, n_iso), ("status", status, n_loci), ("hit_mass", hit_mass, n_hits))
     t = IsoformCoverage(n_exon, n_iso, n_loci, want)
     s, a, h = t._struct(), annot._struct(), hits._struct()
-    ptr = lambda x: None if x is None or x.size == 0 else x.ctypes.data  # noqa: E731
     _lib.check(L.sbgpu_isoform_coverage_host(handle, C.byref(a), C.byref(h), ptr(compat), cw, ptr(F), ptr(theta), ptr(keep), ptr(status),
                                              ptr(hit_mass), C.byref(s)), "sbgpu_isoform_coverage_host")
     return t._finish(s)
@@ -118,10 +93,7 @@ def isoform_coverage_device(ctx, handle, annot, d_hits, d_theta, d_hit_mass=None
     L = ctx.L
     handle = getattr(handle, "h", handle)
     n_exon, n_iso, n_loci = _sizes(L, handle, annot)
-    addr = lambda x: None if x is None else (int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x))  # noqa: E731
-    for name, x, dt in (("d_theta", d_theta, "torch.float64"), ("d_hit_mass", d_hit_mass, "torch.float32")):
-        if hasattr(x, "data_ptr") and (str(x.dtype) != dt or not x.is_cuda or not x.is_contiguous()):
-            raise ValueError("isoform_coverage_device: %s must be a contiguous %s tensor on the context's device" % (name, dt))
+    check_tensors("isoform_coverage_device", d_theta=(d_theta, "torch.float64"), d_hit_mass=(d_hit_mass, "torch.float32"))
     t = IsoformCoverage(n_exon, n_iso, n_loci, want)
     s = t._struct()
     a = annot if isinstance(annot, _lib.sbgpu_annotation_t) else annot._struct()

@@ -24,29 +24,21 @@
 #include <stdint.h>
 
 #include "assign_rules.h"
+#include "stage_host.h"
 
 namespace sb {
 
-// (the limits and the work items of context_device.h, restated: that header defines kernels and belongs to one translation unit)
-constexpr int kAsgMaxBins = 5632;  // bins of one locus whose live flags fit LDS (= kCtxMaxBins; the device grouping stops at 5600)
-constexpr int kAsgMaxWords = 128;  // compat words of one locus in LDS (= kCtxMaxWords: 4096 isoforms)
-constexpr int kAsgItemHits = 16384; // hits of one work item: a deeper locus is split (= kCtxItemHits)
+constexpr int kAsgMaxBins = kStageMaxBins, kAsgMaxWords = kStageMaxWords, kAsgItemHits = kStageItemHits; // (stage_host.h)
 constexpr int kAsgThreads = 256;
 constexpr int kAsgStage = 4096;    // weights of one locus staged in LDS by the column pass (32 KB)
 constexpr int kAsgLdsIso = 1024;   // isoforms up to which the hit pass keeps gains and sums in LDS (4 x 8 KB)
 constexpr int kAsgNarrow = 8;      // isoforms up to which the sums are kept in copies
 constexpr int kAsgCopies = 32;     // kAsgNarrow * kAsgCopies <= kAsgLdsIso
 
-struct AsgItem {
-   int64_t h0, h1;  // hits [h0, h1) of the locus
-   int32_t locus;
-   int32_t split;   // 1: the locus has other items (global atomics), 0: this item owns its sums (plain stores)
-};
-
 struct AsgArgs {
    int64_t n_loci, n_items;
    int32_t compat_words;
-   const AsgItem *items;
+   const HitItem *items;
    const int64_t *locus_hit_off, *row_off, *iso_off, *f_off; // [n_loci + 1]
    const int32_t *hit_bin_local;  // [n_hits] rank of the hit's bin inside its locus, -1: none
    const uint32_t *compat;        // [n_hits * compat_words]
@@ -107,7 +99,7 @@ __global__ __launch_bounds__(kAsgThreads) void asg_hit_kernel(AsgArgs a)
    __shared__ unsigned int s_unassigned;
    const int tid = threadIdx.x, cw = a.compat_words;
    for (int64_t it = blockIdx.x; it < a.n_items; it += gridDim.x) {
-      const AsgItem item = a.items[it];
+      const HitItem item = a.items[it];
       const int64_t l = item.locus, b0 = a.row_off[l], i0 = a.iso_off[l], f0 = a.f_off[l];
       const int nb = (int)min((int64_t)kAsgMaxBins, a.row_off[l + 1] - b0); // (the launcher refuses loci beyond)
       const int niso = (int)min((int64_t)32 * kAsgMaxWords, a.iso_off[l + 1] - i0);

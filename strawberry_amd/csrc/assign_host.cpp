@@ -7,7 +7,7 @@
 
 #include "../../include/sbgpu.h"
 #include "api_internal.h"
-#include "assign_rules.h"
+#include "stage_host.h"
 
 using sb::api_fail;
 
@@ -35,29 +35,10 @@ extern "C" int sbgpu_fragment_assign_host(const sbgpu_bins_t *bins, const uint32
        rc != SBGPU_OK)
       return rc;
    if (nh == 0) return api_fail(SBGPU_EINVAL, "sbgpu_fragment_assign_host: this handle holds no hit -> bin (use one from sbgpu_bins_create or sbgpu_quantify_host)");
-   // ---- the column pass, locus by locus: kept words, live bins, gains
-   std::vector<int64_t> word_off((size_t)nl + 1, 0);
-   for (int64_t l = 0; l < nl; ++l) word_off[(size_t)l + 1] = word_off[(size_t)l] + (v.iso_off[l + 1] - v.iso_off[l] + 31) / 32;
-   std::vector<uint32_t> kept((size_t)word_off[(size_t)nl] + 1, 0u);
-   std::vector<uint8_t> live((size_t)v.n_bins + 1, 0);
-   std::vector<double> g((size_t)v.n_iso + 1, 0.0);
-   std::vector<int32_t> all_kept;
-   for (int64_t l = 0; l < nl; ++l) {
-      const int64_t i0 = v.iso_off[l], b0 = v.row_off[l], nb = v.row_off[l + 1] - b0, f0 = v.f_off[l];
-      const int niso = (int)(v.iso_off[l + 1] - i0);
-      const int words = (niso + 31) / 32;
-      if (words > cw && nh) return api_fail(SBGPU_ESHAPE, "sbgpu_fragment_assign_host: compat_words does not cover a locus");
-      if (!keep && (int)all_kept.size() < niso) all_kept.assign((size_t)niso, 1); // (no filter given: every isoform is kept)
-      uint32_t *K = kept.data() + word_off[(size_t)l];
-      for (int w = 0; w < words; ++w) K[w] = sb::ctx_kept_word(keep ? keep + i0 : all_kept.data(), niso, status ? status[l] : SBGPU_EM_OK, w);
-      for (int64_t b = 0; b < nb; ++b) live[(size_t)(b0 + b)] = sb::asg_row_live(F + f0 + b * niso, niso);
-      for (int j = 0; j < niso; ++j) {
-         double c = 0.0;
-         for (int64_t b = 0; b < nb; ++b)
-            if (live[(size_t)(b0 + b)]) c += F[f0 + b * niso + j];
-         g[(size_t)(i0 + j)] = sb::asg_gain(theta[i0 + j], c, (K[j >> 5] >> (j & 31)) & 1u);
-      }
-   }
+   // ---- the column pass: kept words, live bins, gains
+   sb::ColumnPass col;
+   if (!sb::column_pass(nl, v.row_off, v.iso_off, v.f_off, F, theta, keep, status, cw, &col))
+      return api_fail(SBGPU_ESHAPE, "sbgpu_fragment_assign_host: compat_words does not cover a locus");
    if (out->unique_mass) std::fill(out->unique_mass, out->unique_mass + v.n_iso, 0.0);
    if (out->map_mass) std::fill(out->map_mass, out->map_mass + v.n_iso, 0.0);
    if (out->post_mass) std::fill(out->post_mass, out->post_mass + v.n_iso, 0.0);
@@ -67,21 +48,16 @@ extern "C" int sbgpu_fragment_assign_host(const sbgpu_bins_t *bins, const uint32
    for (int64_t h = 0; h < nh; ++h) {
       const int64_t b = hit_bin[(size_t)h];
       if (b >= v.n_bins) return api_fail(SBGPU_EINVAL, "sbgpu_fragment_assign_host: hit -> bin out of range");
-      if (b >= 0) {
-         if (b < v.row_off[l] || b >= v.row_off[l + 1]) l = std::upper_bound(v.row_off, v.row_off + nl + 1, b) - v.row_off - 1;
-      } else {
-         // a hit without a bin says nothing of its locus: the hits' grouping does
-         if (!v.locus_hit_off)
-            return api_fail(SBGPU_EINVAL, "sbgpu_fragment_assign_host: a hit without a bin, on a handle whose hits did not come grouped by locus: "
-                                          "its locus is not known");
-         if (h < v.locus_hit_off[l] || h >= v.locus_hit_off[l + 1]) l = std::upper_bound(v.locus_hit_off, v.locus_hit_off + nl + 1, h) - v.locus_hit_off - 1;
-      }
+      // (a hit without a bin says nothing of its locus: the hits' grouping does)
+      if ((l = sb::locus_of_hit(h, b, l, nl, v.row_off, v.locus_hit_off)) < 0)
+         return api_fail(SBGPU_EINVAL, "sbgpu_fragment_assign_host: a hit without a bin, on a handle whose hits did not come grouped by locus: "
+                                       "its locus is not known");
       const int64_t i0 = v.iso_off[l];
       const int niso = (int)(v.iso_off[l + 1] - i0);
       const int words = (niso + 31) / 32;
-      const uint32_t *C = compat + h * cw, *K = kept.data() + word_off[(size_t)l];
-      const double *G = g.data() + i0;
-      const double *row = b >= 0 && live[(size_t)b] ? F + v.f_off[l] + (b - v.row_off[l]) * niso : nullptr;
+      const uint32_t *C = compat + h * cw, *K = col.kept.data() + col.word_off[(size_t)l];
+      const double *G = col.gain.data() + i0;
+      const double *row = b >= 0 && col.live[(size_t)b] ? F + v.f_off[l] + (b - v.row_off[l]) * niso : nullptr;
       const sb::AsgHit r = sb::asg_hit_map(C, K, words, G, row);
       if (out->n_cand) out->n_cand[h] = r.n_cand;
       if (out->map_iso) out->map_iso[h] = r.map_iso;

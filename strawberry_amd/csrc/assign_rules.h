@@ -9,11 +9,10 @@
 // Who is kept is context_rules.h's ctx_kept_word.  Everything here is compiled under -ffp-contract=off.
 #pragma once
 
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/sbgpu.h"
-#include "context_rules.h"
+#include "context_rules.h" // (and, through it, the HIP runtime where the compiler is HIP's)
 
 namespace sb {
 

@@ -11,8 +11,8 @@
 #include <string>
 
 #include "../../include/sbgpu.h"
-#include "api_internal.h"
 #include "bootstrap_device.h"
+#include "stage_common.h"
 
 using sb::api_fail;
 using sb::api_fail_hip;
@@ -241,15 +241,9 @@ int abundance_bootstrap(const char *who, sbgpu_ctx_t *c, const sbgpu_bins_t *bin
    if (const int rc = check_ranks(who, params->n_rep, rank_lo, rank_hi); rc != SBGPU_OK) return rc;
    const sb::BootKeep *rec = sb::ctx_boot_keep(c);
    const sb::BinsContextView v = sb::bins_context_view(bins);
-   if (!v.boot_serial)
-      return api_fail(SBGPU_EINVAL, std::string(who) + ": this handle was made without retention (sbgpu_bootstrap_keep was off for its call, or it is not "
-                                                       "from sbgpu_quantify_resident / sbgpu_front_stream_end)");
-   if (v.boot_serial != rec->serial || !rec->plan)
-      return api_fail(SBGPU_EINVAL, std::string(who) + ": a stale handle: a later call on this context (sbgpu_quantify_*, or another entry that works in the "
-                                                       "context's scratch) has reused what its call kept");
-   const sb::PlanShape ps = sb::plan_shape(rec->plan);
+   sb::PlanShape ps;
+   if (const int rc = sb::check_boot_keep(who, rec, v, false, &ps); rc != SBGPU_OK) return rc;
    const int64_t nl = ps.n_loci, n_iso = ps.n_iso;
-   if (nl != v.n_loci || n_iso != v.n_iso || nl != rec->n_loci || n_iso != rec->n_iso) return api_fail(SBGPU_EINVAL, std::string(who) + ": the handle and the context's record disagree");
    const int32_t B = params->n_rep;
    hipStream_t s = stream ? (hipStream_t)stream : sb::ctx_stream(c);
    if (hipError_t e = hipSetDevice(sb::ctx_device(c)); e != hipSuccess) return api_fail_hip(e, "hipSetDevice");

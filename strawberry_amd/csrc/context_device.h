@@ -20,27 +20,20 @@
 #include <stdint.h>
 
 #include "context_rules.h"
+#include "stage_host.h"
 
 namespace sb {
 
-constexpr int kCtxMaxBins = 5632;     // bins of one locus in LDS (the device grouping stops at 5600: kBinsMaxBig)
-constexpr int kCtxMaxWords = 128;     // compat words of one locus in LDS (4096 isoforms)
+constexpr int kCtxMaxBins = kStageMaxBins, kCtxMaxWords = kStageMaxWords, kCtxItemHits = kStageItemHits; // (stage_host.h)
 constexpr int kCtxThreads = 256;
-constexpr int kCtxItemHits = 16384;   // hits of one count work item: a deeper locus is split
 constexpr int kCtxAllPairs = 256;     // bins up to which a locus is ranked by all-pairs counting
 constexpr int kCtxSortSlots = 8192;   // >= kCtxMaxBins, a power of two
 constexpr int kCtxKeyStage = 4096;    // key words of a locus staged in LDS where they fit (else read through the L2)
 
-struct CtxItem {
-   int64_t h0, h1;  // hits [h0, h1) of the locus
-   int32_t locus;
-   int32_t split;   // 1: the locus has other items (global atomics), 0: this item owns its bins (plain stores)
-};
-
 struct CtxArgs {
    int64_t n_loci, n_items;
    int32_t compat_words, key_words;
-   const CtxItem *items;
+   const HitItem *items;
    const int64_t *locus_hit_off, *row_off, *iso_off, *f_off; // [n_loci + 1]
    const int32_t *hit_bin_local;  // [n_hits] rank of the hit's bin inside its locus, -1: none
    const uint32_t *compat;        // [n_hits * compat_words]
@@ -65,7 +58,7 @@ __global__ __launch_bounds__(kCtxThreads) void ctx_count_kernel(CtxArgs a)
    __shared__ uint32_t s_keep[kCtxMaxWords];
    const int tid = threadIdx.x, cw = a.compat_words;
    for (int64_t it = blockIdx.x; it < a.n_items; it += gridDim.x) {
-      const CtxItem item = a.items[it];
+      const HitItem item = a.items[it];
       const int64_t l = item.locus, b0 = a.row_off[l], q0 = a.locus_hit_off[l], i0 = a.iso_off[l];
       const int nb = (int)min((int64_t)kCtxMaxBins, a.row_off[l + 1] - b0); // (the launcher refuses loci beyond)
       const int niso = (int)(a.iso_off[l + 1] - i0);

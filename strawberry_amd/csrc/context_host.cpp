@@ -9,7 +9,7 @@
 
 #include "../../include/sbgpu.h"
 #include "api_internal.h"
-#include "context_rules.h"
+#include "stage_host.h"
 
 using sb::api_fail;
 
@@ -39,13 +39,9 @@ extern "C" int sbgpu_context_table_host(const sbgpu_bins_t *bins, const uint32_t
    std::vector<int32_t> all_kept;
    int64_t l = 0;
    auto kept_mask_of = [&](int64_t locus) {
-      const int64_t i0 = v.iso_off[locus];
-      const int niso = (int)(v.iso_off[locus + 1] - i0);
+      const int niso = (int)(v.iso_off[locus + 1] - v.iso_off[locus]);
       kept.assign((size_t)(niso + 31) / 32 + 1, 0u);
-      if (!keep && (int)all_kept.size() < niso) all_kept.assign((size_t)niso, 1); // (no filter given: every isoform is kept)
-      for (int w = 0; w < (niso + 31) / 32; ++w)
-         kept[(size_t)w] = sb::ctx_kept_word(keep ? keep + i0 : all_kept.data(), niso, status ? status[locus] : SBGPU_EM_OK, w);
-      return (niso + 31) / 32;
+      return sb::kept_words(keep ? keep + v.iso_off[locus] : nullptr, niso, status ? status + locus : nullptr, all_kept, kept.data());
    };
    int64_t mask_locus = -1;
    int words = 0;
@@ -53,7 +49,7 @@ extern "C" int sbgpu_context_table_host(const sbgpu_bins_t *bins, const uint32_t
       const int64_t b = hit_bin[(size_t)h];
       if (b < 0) continue;
       if (b >= v.n_bins) return api_fail(SBGPU_EINVAL, "sbgpu_context_table_host: hit -> bin out of range");
-      if (b < v.row_off[l] || b >= v.row_off[l + 1]) l = std::upper_bound(v.row_off, v.row_off + nl + 1, b) - v.row_off - 1;
+      l = sb::locus_of_hit(h, b, l, nl, v.row_off, nullptr);
       if (l != mask_locus) {
          words = kept_mask_of(l);
          if (words > cw) return api_fail(SBGPU_ESHAPE, "sbgpu_context_table_host: compat_words does not cover a locus");

@@ -6,7 +6,12 @@
 //   - the order of a locus' rows (ctx_key_less).
 #pragma once
 
+#ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#elif !defined(__host__) // a plain C++ compiler (a host-only program over stage_host.h): the qualifiers mean nothing there
+#define __host__
+#define __device__
+#endif
 #include <stdint.h>
 
 #include "../../include/sbgpu.h"

@@ -24,13 +24,11 @@
 #include <stdint.h>
 
 #include "coverage_rules.h"
+#include "stage_host.h"
 
 namespace sb {
 
-// (the limits and the work items of assign_device.h, restated: that header defines kernels and belongs to one translation unit)
-constexpr int kCovMaxBins = 5632;   // bins of one locus whose live flags fit LDS (= kAsgMaxBins)
-constexpr int kCovMaxWords = 128;   // compat words of one locus in LDS (= kAsgMaxWords: 4096 isoforms)
-constexpr int kCovItemHits = 16384; // hits of one work item: a deeper locus is split (= kAsgItemHits)
+constexpr int kCovMaxBins = kStageMaxBins, kCovMaxWords = kStageMaxWords, kCovItemHits = kStageItemHits; // (stage_host.h)
 constexpr int kCovThreads = 256;
 constexpr int kCovLdsExons = 1024;  // annotated exons of one locus up to which the exon table and the sums are kept in LDS (2 x 4 KB + 2 x 8 KB)
 // Not a threshold of its own: an isoform owns at least one exon, so a locus of at most kCovLdsExons exons has at most as many
@@ -43,16 +41,10 @@ constexpr int kCovCopies = 16;      // kCovCopyExons * kCovCopies <= kCovLdsExon
 static_assert(kCovCopyExons * kCovCopies <= kCovLdsExons, "the copies share the sums' LDS arrays");
 static_assert((kCovCopies & (kCovCopies - 1)) == 0, "a lane's copy is lane & (kCovCopies - 1)");
 
-struct CovItem {
-   int64_t h0, h1;  // hits [h0, h1) of the locus
-   int32_t locus;
-   int32_t split;   // 1: the locus has other items (global atomics), 0: this item owns its sums (plain stores)
-};
-
 struct CovArgs {
    int64_t n_loci, n_items, n_iso;
    int32_t compat_words;
-   const CovItem *items;
+   const HitItem *items;
    const int64_t *row_off, *iso_off, *f_off;   // [n_loci + 1]
    const int64_t *exon_off;                    // [n_iso + 1]
    const uint32_t *exon_left, *exon_right;     // [n_exon]
@@ -82,7 +74,7 @@ __global__ __launch_bounds__(kCovThreads) void cov_hit_kernel(CovArgs a)
    __shared__ double s_unexplained;
    const int tid = threadIdx.x, cw = a.compat_words;
    for (int64_t it = blockIdx.x; it < a.n_items; it += gridDim.x) {
-      const CovItem item = a.items[it];
+      const HitItem item = a.items[it];
       const int64_t l = item.locus, b0 = a.row_off[l], i0 = a.iso_off[l], f0 = a.f_off[l];
       const int nb = (int)min((int64_t)kCovMaxBins, a.row_off[l + 1] - b0); // (the launcher refuses loci beyond)
       const int niso = (int)min((int64_t)32 * kCovMaxWords, a.iso_off[l + 1] - i0);

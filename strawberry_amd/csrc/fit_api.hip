@@ -3,13 +3,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/sbgpu.h"
-#include "api_internal.h"
 #include "fit_device.h"
+#include "stage_common.h"
 
 using sb::api_fail;
 
@@ -41,103 +40,72 @@ int fit_run(const std::string &who, sbgpu_ctx_t *c, const sb::PlanShape &ps, con
    if (n_bins && !d_count) return api_fail(SBGPU_EINVAL, who + ": the counts are not on the device");
    if (any_weight && !d_F) return api_fail(SBGPU_EINVAL, who + ": the weights are not on the device");
    hipStream_t s = stream ? (hipStream_t)stream : sb::ctx_stream(c);
-#define SB_TRY(expr)                                                                                        \
-   do {                                                                                                     \
-      hipError_t e_ = (expr);                                                                               \
-      if (e_ != hipSuccess) {                                                                               \
-         (void)hipStreamSynchronize(s); /* (the upload from `host` below may still be in flight) */         \
-         return api_fail(SBGPU_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));                    \
-      }                                                                                                     \
-   } while (0)
-   SB_TRY(hipSetDevice(sb::ctx_device(c)));
-   // ---- one arena: [uploads: the two lists | keep / status where the caller gave none | live, gains | the results]
-   auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-   const size_t nl1 = (size_t)nl + 1, nb1 = (size_t)std::max<int64_t>(n_bins, 1), ni1 = (size_t)std::max<int64_t>(n_iso, 1);
-   size_t off = 0;
-   const size_t o_small = off; off += up((small.size() + 1) * 4);
-   const size_t o_large = off; off += up((large.size() + 1) * 4);
-   const size_t upload_bytes = off;
-   const size_t o_keep = off; off += d_keep ? 0 : up(ni1 * 4);
-   const size_t o_status = off; off += d_status ? 0 : up(nl1 * 4);
-   const size_t o_live = off; off += up(nb1);
-   const size_t o_gain = off; off += up(ni1 * 8);
-   const size_t o_exp = off; off += up(nb1 * 8);
-   const size_t o_res = off; off += up(nb1 * 8);
-   const size_t o_score = off; off += up(ni1 * 8);
-   const size_t o_ll = off; off += up(nl1 * 8);
-   const size_t o_dev = off; off += up(nl1 * 8);
-   const size_t o_pear = off; off += up(nl1 * 8);
-   const size_t o_nlive = off; off += up(nl1 * 8);
-   const size_t o_ndrop = off; off += up(nl1 * 8);
-   const size_t o_nimp = off; off += up(nl1 * 8);
-   const size_t o_dof = off; off += up(nl1 * 4);
-   const size_t o_worst = off; off += up(nl1 * 4);
+   SB_STAGE_TRY(hipSetDevice(sb::ctx_device(c)));
+   // ---- the arena (stage_host.h: fit_layout): keep / status have room in it where the caller gave none
+   const sb::FitLayout L = sb::fit_layout(nl, n_bins, n_iso, small.size(), large.size(), !d_keep, !d_status);
    char *d = nullptr;
-   if (hipError_t e = sb::ctx_scratch(c, 11, off, &d); e != hipSuccess)
+   if (hipError_t e = sb::ctx_scratch(c, sb::kScratchFit, L.bytes, &d); e != hipSuccess)
       return sb::api_fail_hip(e, "hipMalloc");
-   // (one host block for the uploads: it lives until the call's last synchronisation; SB_TRY synchronises before it leaves early)
-   std::vector<char> host(upload_bytes, 0);
-   if (!small.empty()) std::memcpy(host.data() + o_small, small.data(), small.size() * 4);
-   if (!large.empty()) std::memcpy(host.data() + o_large, large.data(), large.size() * 4);
-   SB_TRY(hipMemcpyAsync(d, host.data(), upload_bytes, hipMemcpyHostToDevice, s));
+   sb::HostBlock host(L.upload_bytes);
+   host.put(L.small, small.data(), small.size()), host.put(L.large, large.data(), large.size());
+   SB_STAGE_TRY(host.upload(d, s));
    // no filter given: every isoform is kept (any non-zero word); no status given: every locus started (SBGPU_EM_OK is 0)
-   if (!d_keep) SB_TRY(hipMemsetAsync(d + o_keep, 1, ni1 * 4, s));
-   if (!d_status) SB_TRY(hipMemsetAsync(d + o_status, 0, nl1 * 4, s));
-   const int32_t *keep = d_keep ? d_keep : (const int32_t *)(d + o_keep), *status = d_status ? d_status : (const int32_t *)(d + o_status);
+   if (!d_keep) SB_STAGE_TRY(hipMemsetAsync(d + L.keep, 1, sb::at_least_1(n_iso) * 4, s));
+   if (!d_status) SB_STAGE_TRY(hipMemsetAsync(d + L.status, 0, ((size_t)nl + 1) * 4, s));
+   const int32_t *keep = d_keep ? d_keep : sb::arena_at<int32_t>(d, L.keep), *status = d_status ? d_status : sb::arena_at<int32_t>(d, L.status);
    sb::AsgColumnPass col;
    col.n_loci = nl;
    col.row_off = ps.d_row_off, col.iso_off = ps.d_iso_off, col.f_off = ps.d_f_off;
    col.keep = keep, col.status = status;
    col.F = d_F, col.theta = d_theta;
-   col.live = (uint8_t *)(d + o_live), col.gain = (double *)(d + o_gain);
+   col.live = sb::arena_at<uint8_t>(d, L.live), col.gain = sb::arena_at<double>(d, L.gain);
    sb::FitArgs a;
    a.row_off = col.row_off, a.iso_off = col.iso_off, a.f_off = col.f_off;
    a.count = d_count, a.F = d_F;
    a.keep = keep, a.status = status;
    a.live = col.live, a.gain = col.gain;
-   a.expected = (double *)(d + o_exp), a.resid = (double *)(d + o_res), a.score = (double *)(d + o_score);
-   a.loglik = (double *)(d + o_ll), a.deviance = (double *)(d + o_dev), a.pearson = (double *)(d + o_pear);
-   a.n_live = (long long *)(d + o_nlive), a.n_dropped = (long long *)(d + o_ndrop), a.n_impossible = (long long *)(d + o_nimp);
-   a.dof = (int32_t *)(d + o_dof), a.worst_bin = (int32_t *)(d + o_worst);
+   a.expected = sb::arena_at<double>(d, L.exp), a.resid = sb::arena_at<double>(d, L.res), a.score = sb::arena_at<double>(d, L.score);
+   a.loglik = sb::arena_at<double>(d, L.ll), a.deviance = sb::arena_at<double>(d, L.dev), a.pearson = sb::arena_at<double>(d, L.pear);
+   a.n_live = sb::arena_at<long long>(d, L.nlive), a.n_dropped = sb::arena_at<long long>(d, L.ndrop), a.n_impossible = sb::arena_at<long long>(d, L.nimp);
+   a.dof = sb::arena_at<int32_t>(d, L.dof), a.worst_bin = sb::arena_at<int32_t>(d, L.worst);
    const int64_t cap = (int64_t)sb::ctx_cu_count(c) * sb::kFitGridPerCu;
    // (sbgpu_set_timing: the three launches as stages of their own, for tools/bench_fit.py)
    sb::ctx_stage_reset(c);
    sb::ctx_stage_begin(c, "fit_column", s);
-   if (nl) SB_TRY(sb::asg_launch_column_pass(col, (unsigned)std::min<int64_t>(nl, cap), s));
+   if (nl) SB_STAGE_TRY(sb::asg_launch_column_pass(col, sb::stage_grid(nl, cap), s));
    sb::ctx_stage_end(c, s);
    sb::ctx_stage_begin(c, "fit_wave", s);
    if (!small.empty()) {
-      a.n_list = (int64_t)small.size(), a.list = (const int32_t *)(d + o_small);
+      a.n_list = (int64_t)small.size(), a.list = sb::arena_at<int32_t>(d, L.small);
       const int64_t blocks = (a.n_list + sb::kFitWaveLoci - 1) / sb::kFitWaveLoci;
-      hipLaunchKernelGGL(sb::fit_wave_kernel, dim3((unsigned)std::min<int64_t>(blocks, cap)), dim3(sb::kFitThreads), 0, s, a);
-      SB_TRY(hipGetLastError());
+      hipLaunchKernelGGL(sb::fit_wave_kernel, dim3(sb::stage_grid(blocks, cap)), dim3(sb::kFitThreads), 0, s, a);
+      SB_STAGE_TRY(hipGetLastError());
    }
    sb::ctx_stage_end(c, s);
    sb::ctx_stage_begin(c, "fit_block", s);
    if (!large.empty()) {
-      a.n_list = (int64_t)large.size(), a.list = (const int32_t *)(d + o_large);
-      hipLaunchKernelGGL(sb::fit_block_kernel, dim3((unsigned)std::min<int64_t>(a.n_list, cap)), dim3(sb::kFitThreads), 0, s, a);
-      SB_TRY(hipGetLastError());
+      a.n_list = (int64_t)large.size(), a.list = sb::arena_at<int32_t>(d, L.large);
+      hipLaunchKernelGGL(sb::fit_block_kernel, dim3(sb::stage_grid(a.n_list, cap)), dim3(sb::kFitThreads), 0, s, a);
+      SB_STAGE_TRY(hipGetLastError());
    }
    sb::ctx_stage_end(c, s);
    // ---- results: what the caller asked for
-   if (out->expected && n_bins) SB_TRY(hipMemcpyAsync(out->expected, d + o_exp, (size_t)n_bins * 8, hipMemcpyDeviceToHost, s));
-   if (out->resid && n_bins) SB_TRY(hipMemcpyAsync(out->resid, d + o_res, (size_t)n_bins * 8, hipMemcpyDeviceToHost, s));
-   if (out->score && n_iso) SB_TRY(hipMemcpyAsync(out->score, d + o_score, (size_t)n_iso * 8, hipMemcpyDeviceToHost, s));
-   if (out->loglik && nl) SB_TRY(hipMemcpyAsync(out->loglik, d + o_ll, (size_t)nl * 8, hipMemcpyDeviceToHost, s));
-   if (out->deviance && nl) SB_TRY(hipMemcpyAsync(out->deviance, d + o_dev, (size_t)nl * 8, hipMemcpyDeviceToHost, s));
-   if (out->pearson && nl) SB_TRY(hipMemcpyAsync(out->pearson, d + o_pear, (size_t)nl * 8, hipMemcpyDeviceToHost, s));
-   if (out->n_live && nl) SB_TRY(hipMemcpyAsync(out->n_live, d + o_nlive, (size_t)nl * 8, hipMemcpyDeviceToHost, s));
-   if (out->n_dropped && nl) SB_TRY(hipMemcpyAsync(out->n_dropped, d + o_ndrop, (size_t)nl * 8, hipMemcpyDeviceToHost, s));
-   if (out->n_impossible && nl) SB_TRY(hipMemcpyAsync(out->n_impossible, d + o_nimp, (size_t)nl * 8, hipMemcpyDeviceToHost, s));
-   if (out->dof && nl) SB_TRY(hipMemcpyAsync(out->dof, d + o_dof, (size_t)nl * 4, hipMemcpyDeviceToHost, s));
-   if (out->worst_bin && nl) SB_TRY(hipMemcpyAsync(out->worst_bin, d + o_worst, (size_t)nl * 4, hipMemcpyDeviceToHost, s));
-   SB_TRY(hipStreamSynchronize(s));
-#undef SB_TRY
-   out->d_expected = (const double *)(d + o_exp), out->d_resid = (const double *)(d + o_res), out->d_score = (const double *)(d + o_score);
-   out->d_loglik = (const double *)(d + o_ll), out->d_deviance = (const double *)(d + o_dev), out->d_pearson = (const double *)(d + o_pear);
-   out->d_n_live = (const int64_t *)(d + o_nlive), out->d_n_dropped = (const int64_t *)(d + o_ndrop), out->d_n_impossible = (const int64_t *)(d + o_nimp);
-   out->d_dof = (const int32_t *)(d + o_dof), out->d_worst_bin = (const int32_t *)(d + o_worst);
+   SB_STAGE_TRY(sb::copy_back(out->expected, d, L.exp, n_bins, s));
+   SB_STAGE_TRY(sb::copy_back(out->resid, d, L.res, n_bins, s));
+   SB_STAGE_TRY(sb::copy_back(out->score, d, L.score, n_iso, s));
+   SB_STAGE_TRY(sb::copy_back(out->loglik, d, L.ll, nl, s));
+   SB_STAGE_TRY(sb::copy_back(out->deviance, d, L.dev, nl, s));
+   SB_STAGE_TRY(sb::copy_back(out->pearson, d, L.pear, nl, s));
+   SB_STAGE_TRY(sb::copy_back(out->n_live, d, L.nlive, nl, s));
+   SB_STAGE_TRY(sb::copy_back(out->n_dropped, d, L.ndrop, nl, s));
+   SB_STAGE_TRY(sb::copy_back(out->n_impossible, d, L.nimp, nl, s));
+   SB_STAGE_TRY(sb::copy_back(out->dof, d, L.dof, nl, s));
+   SB_STAGE_TRY(sb::copy_back(out->worst_bin, d, L.worst, nl, s));
+   SB_STAGE_TRY(hipStreamSynchronize(s));
+   out->d_expected = a.expected, out->d_resid = a.resid, out->d_score = a.score;
+   out->d_loglik = a.loglik, out->d_deviance = a.deviance, out->d_pearson = a.pearson;
+   out->d_n_live = sb::arena_at<int64_t>(d, L.nlive), out->d_n_dropped = sb::arena_at<int64_t>(d, L.ndrop), out->d_n_impossible = sb::arena_at<int64_t>(d, L.nimp);
+   out->d_dof = a.dof, out->d_worst_bin = a.worst_bin;
    return SBGPU_OK;
 }
 
@@ -164,19 +132,12 @@ extern "C" int sbgpu_em_fit_device(sbgpu_ctx_t *c, const sbgpu_plan_t *plan, con
 extern "C" int sbgpu_model_fit_device(sbgpu_ctx_t *c, const sbgpu_bins_t *bins, const double *d_theta, const int32_t *d_keep, const int32_t *d_status,
                                       void *stream, sbgpu_em_fit_t *out)
 {
-   if (!c || !bins || !out) return api_fail(SBGPU_EINVAL, "sbgpu_model_fit_device: null argument");
+   const std::string who = "sbgpu_model_fit_device";
+   if (!c || !bins || !out) return api_fail(SBGPU_EINVAL, who + ": null argument");
    fit_clear_device(out);
-   if (!d_theta) return api_fail(SBGPU_EINVAL, "sbgpu_model_fit_device: d_theta is needed (the fit is theta's: give the call's, or another estimate)");
+   if (!d_theta) return api_fail(SBGPU_EINVAL, who + ": d_theta is needed (the fit is theta's: give the call's, or another estimate)");
    const sb::BootKeep *rec = sb::ctx_boot_keep(c);
-   const sb::BinsContextView v = sb::bins_context_view(bins);
-   if (!v.boot_serial)
-      return api_fail(SBGPU_EINVAL, "sbgpu_model_fit_device: this handle was made without retention (sbgpu_bootstrap_keep was off for its call, or it is not "
-                                    "from sbgpu_quantify_resident / sbgpu_front_stream_end)");
-   if (v.boot_serial != rec->serial || !rec->plan)
-      return api_fail(SBGPU_EINVAL, "sbgpu_model_fit_device: a stale handle: a later call on this context (sbgpu_quantify_*, or another entry that works in the "
-                                    "context's scratch) has reused what its call kept");
-   const sb::PlanShape ps = sb::plan_shape(rec->plan);
-   if (ps.n_loci != v.n_loci || ps.n_iso != v.n_iso || ps.n_rows != v.n_bins || ps.n_loci != rec->n_loci || ps.n_iso != rec->n_iso)
-      return api_fail(SBGPU_EINVAL, "sbgpu_model_fit_device: the handle and the context's record disagree");
-   return fit_run("sbgpu_model_fit_device", c, ps, rec->d_count, rec->d_F, d_theta, d_keep, d_status, stream, out);
+   sb::PlanShape ps;
+   if (const int rc = sb::check_boot_keep(who, rec, sb::bins_context_view(bins), true, &ps); rc != SBGPU_OK) return rc;
+   return fit_run(who, c, ps, rec->d_count, rec->d_F, d_theta, d_keep, d_status, stream, out);
 }

@@ -24,11 +24,11 @@
 #include <stdint.h>
 
 #include "fit_rules.h"
+#include "stage_host.h"
 
 namespace sb {
 
-constexpr int kFitMaxBins = 5632;  // bins of one locus whose ratios fit LDS (the assignment's limit, assign_device.h: kAsgMaxBins)
-constexpr int kFitMaxWords = 128;  // kept words of one locus (4096 isoforms: kAsgMaxWords)
+constexpr int kFitMaxBins = kStageMaxBins, kFitMaxWords = kStageMaxWords; // (stage_host.h)
 constexpr int kFitThreads = 256;
 constexpr int kFitWave = 64;
 constexpr int kFitWaveLoci = kFitThreads / kFitWave; // loci of one workgroup in the wave form

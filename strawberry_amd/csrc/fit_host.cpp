@@ -8,6 +8,7 @@
 #include "../../include/sbgpu.h"
 #include "api_internal.h"
 #include "fit_rules.h"
+#include "stage_host.h"
 
 using sb::api_fail;
 
@@ -45,23 +46,16 @@ extern "C" int sbgpu_em_fit_host(const sbgpu_batch_t *batch, const double *theta
       const int words = (niso + 31) / 32;
       const double *Fl = F + f0;
       const int32_t *n = count + b0;
-      if (!keep && (int)all_kept.size() < niso) all_kept.assign((size_t)niso, 1); // (no filter given: every isoform is kept)
       // ---- rule 1: kept, live, c_j, g_j: the assignment's
       kept.assign((size_t)words + 1, 0u);
+      sb::kept_words(keep ? keep + i0 : nullptr, niso, status ? status + l : nullptr, all_kept, kept.data());
       uint32_t any_kept = 0;
-      for (int w = 0; w < words; ++w) any_kept |= kept[(size_t)w] = sb::ctx_kept_word(keep ? keep + i0 : all_kept.data(), niso, status ? status[l] : SBGPU_EM_OK, w);
+      for (int w = 0; w < words; ++w) any_kept |= kept[(size_t)w];
       live.assign((size_t)nb + 1, 0), possible.assign((size_t)nb + 1, 0);
-      for (int b = 0; b < nb; ++b) live[(size_t)b] = sb::asg_row_live(Fl + (int64_t)b * niso, niso);
       c.assign((size_t)niso + 1, 0.0), g.assign((size_t)niso + 1, 0.0);
+      sb::column_pass_locus(Fl, nb, niso, theta + i0, kept.data(), live.data(), g.data(), c.data());
       int64_t A = 0;
-      for (int j = 0; j < niso; ++j) {
-         double cj = 0.0;
-         for (int b = 0; b < nb; ++b)
-            if (live[(size_t)b]) cj += Fl[(int64_t)b * niso + j];
-         c[(size_t)j] = cj;
-         g[(size_t)j] = sb::asg_gain(theta[i0 + j], cj, (kept[(size_t)(j >> 5)] >> (j & 31)) & 1u);
-         A += g[(size_t)j] > 0.0;
-      }
+      for (int j = 0; j < niso; ++j) A += g[(size_t)j] > 0.0;
       d.assign((size_t)nb + 1, 0.0), e.assign((size_t)nb + 1, 0.0), r.assign((size_t)nb + 1, 0.0);
       int64_t n_live = 0, n_dropped = 0, n_impossible = 0, P = 0;
       double D = 0.0, loglik = 0.0, dev = 0.0, pearson = 0.0, best = -1.0;

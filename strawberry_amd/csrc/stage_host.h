@@ -1,0 +1,209 @@
+// strawberry_amd/csrc/stage_host.h -- what the retained-result stages (the `-f` table, the fragment assignment, the isoform
+// coverage, the model fit) share on the host, free of HIP: a plain C++ compiler takes this header alone.
+//   - the limits of one locus and the work item of the hit kernels (one definition; the stages' headers alias them),
+//   - the builder of the work items,
+//   - the arena's layout: Arena::take, and each stage's offsets as one struct made by one function,
+//   - the two loops the host forms share: the column pass (kept words, live flags, gains) and "which locus is this hit in".
+#pragma once
+
+#include <stdint.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "assign_rules.h"
+
+namespace sb {
+
+constexpr int kStageMaxBins = 5632;   // bins of one locus whose per-bin arrays fit LDS (the device grouping stops at 5600: kBinsMaxBig)
+constexpr int kStageMaxWords = 128;   // compat / kept words of one locus in LDS (4096 isoforms)
+constexpr int kStageItemHits = 16384; // hits of one work item: a deeper locus is split
+
+struct HitItem {
+   int64_t h0, h1;  // hits [h0, h1) of the locus
+   int32_t locus;
+   int32_t split;   // 1: the locus has other items (global atomics), 0: this item owns its results (plain stores)
+};
+
+// A locus' hits in ranges of kStageItemHits, loci in ascending order.  row_off given: a locus without bins gets no item (the
+// table counts hits per bin); null: it does (its hits are counted as unassigned / unexplained).
+inline std::vector<HitItem> build_hit_items(const int64_t *locus_hit_off, int64_t n_loci, const int64_t *row_off)
+{
+   std::vector<HitItem> items;
+   for (int64_t l = 0; l < n_loci; ++l) {
+      const int64_t q0 = locus_hit_off[l], q1 = locus_hit_off[l + 1];
+      if (row_off && row_off[l + 1] == row_off[l]) continue;
+      const int32_t split = q1 - q0 > kStageItemHits;
+      for (int64_t h = q0; h < q1; h += kStageItemHits) items.push_back({h, std::min<int64_t>(h + kStageItemHits, q1), (int32_t)l, split});
+   }
+   return items;
+}
+
+// One device block cut into arrays that begin at multiples of 256 bytes, in the order they are taken
+struct Arena {
+   size_t size = 0;
+   size_t take(size_t bytes)
+   {
+      const size_t at = size;
+      size += (bytes + 255) & ~(size_t)255;
+      return at;
+   }
+};
+inline size_t at_least_1(int64_t n) { return (size_t)std::max<int64_t>(n, 1); }
+
+// The stages' arenas.  Every member but the *_bytes is an offset; `upload_bytes` ends the part that one host block fills.
+struct CtxLayout {
+   size_t hoff, roff, ioff, foff, items, upload_bytes; // the four offset arrays, the items
+   size_t nin, last;                                   // per-bin scratch
+   size_t nrows, lhits, lroff, tot;                    // per-locus results, the row count
+   size_t rbin, rhits, rlast, prob, bytes;             // rows
+};
+inline CtxLayout ctx_layout(int64_t n_loci, int64_t n_bins, int64_t n_elem, int64_t n_items)
+{
+   const size_t nl1 = (size_t)n_loci + 1, nb1 = at_least_1(n_bins);
+   Arena a;
+   CtxLayout L;
+   L.hoff = a.take(nl1 * 8), L.roff = a.take(nl1 * 8), L.ioff = a.take(nl1 * 8), L.foff = a.take(nl1 * 8);
+   L.items = a.take(at_least_1(n_items) * sizeof(HitItem));
+   L.upload_bytes = a.size;
+   L.nin = a.take(nb1 * 4), L.last = a.take(nb1 * 4);
+   L.nrows = a.take(nl1 * 4), L.lhits = a.take(nl1 * 4), L.lroff = a.take(nl1 * 8), L.tot = a.take(256);
+   L.rbin = a.take(nb1 * 8), L.rhits = a.take(nb1 * 4), L.rlast = a.take(nb1 * 8), L.prob = a.take(at_least_1(n_elem) * 8);
+   L.bytes = a.size;
+   return L;
+}
+
+struct AsgLayout {
+   size_t hoff, roff, ioff, foff, items, upload_bytes; // the four offset arrays, the items
+   size_t live, gain;
+   size_t uniq, map, post, unas, sums_bytes;           // the sums, zeroed per call: [uniq, uniq + sums_bytes)
+   size_t iso, cand, prob, bytes;                      // the per-hit results
+};
+inline AsgLayout asg_layout(int64_t n_loci, int64_t n_bins, int64_t n_iso, int64_t n_hits, int64_t n_items)
+{
+   const size_t nl1 = (size_t)n_loci + 1, ni1 = at_least_1(n_iso), nh1 = at_least_1(n_hits);
+   Arena a;
+   AsgLayout L;
+   L.hoff = a.take(nl1 * 8), L.roff = a.take(nl1 * 8), L.ioff = a.take(nl1 * 8), L.foff = a.take(nl1 * 8);
+   L.items = a.take(at_least_1(n_items) * sizeof(HitItem));
+   L.upload_bytes = a.size;
+   L.live = a.take(at_least_1(n_bins)), L.gain = a.take(ni1 * 8);
+   L.uniq = a.take(ni1 * 8), L.map = a.take(ni1 * 8), L.post = a.take(ni1 * 8), L.unas = a.take(nl1 * 8);
+   L.sums_bytes = a.size - L.uniq;
+   L.iso = a.take(nh1 * 4), L.cand = a.take(nh1 * 4), L.prob = a.take(nh1 * 8);
+   L.bytes = a.size;
+   return L;
+}
+
+struct CovLayout {
+   size_t roff, ioff, foff, items, eoff, eleft, eright, upload_bytes; // the three offset arrays, the items, the exon arrays
+   size_t live, gain;
+   size_t bases, junc, unex, sums_bytes;                              // the sums, zeroed per call: [bases, bases + sums_bytes)
+   size_t iso, bytes;
+};
+// upload_exons: the exon arrays travel with the offsets (false: the context holds the annotation pinned; they take no room)
+inline CovLayout cov_layout(int64_t n_loci, int64_t n_bins, int64_t n_iso, int64_t n_exon, int64_t n_items, bool upload_exons)
+{
+   const size_t nl1 = (size_t)n_loci + 1, ni1 = (size_t)n_iso + 1, ne1 = at_least_1(n_exon);
+   Arena a;
+   CovLayout L;
+   L.roff = a.take(nl1 * 8), L.ioff = a.take(nl1 * 8), L.foff = a.take(nl1 * 8);
+   L.items = a.take(at_least_1(n_items) * sizeof(HitItem));
+   L.eoff = a.take(upload_exons ? ni1 * 8 : 0), L.eleft = a.take(upload_exons ? ne1 * 4 : 0), L.eright = a.take(upload_exons ? ne1 * 4 : 0);
+   L.upload_bytes = a.size;
+   L.live = a.take(at_least_1(n_bins)), L.gain = a.take(ni1 * 8);
+   L.bases = a.take(ne1 * 8), L.junc = a.take(ne1 * 8), L.unex = a.take(nl1 * 8);
+   L.sums_bytes = a.size - L.bases;
+   L.iso = a.take(ni1 * 8);
+   L.bytes = a.size;
+   return L;
+}
+
+struct FitLayout {
+   size_t small, large, upload_bytes; // the two lists of loci
+   size_t keep, status;               // where the caller gave none
+   size_t live, gain;
+   size_t exp, res, score, ll, dev, pear, nlive, ndrop, nimp, dof, worst, bytes;
+};
+inline FitLayout fit_layout(int64_t n_loci, int64_t n_bins, int64_t n_iso, size_t n_small, size_t n_large, bool own_keep, bool own_status)
+{
+   const size_t nl1 = (size_t)n_loci + 1, nb1 = at_least_1(n_bins), ni1 = at_least_1(n_iso);
+   Arena a;
+   FitLayout L;
+   L.small = a.take((n_small + 1) * 4), L.large = a.take((n_large + 1) * 4);
+   L.upload_bytes = a.size;
+   L.keep = a.take(own_keep ? ni1 * 4 : 0), L.status = a.take(own_status ? nl1 * 4 : 0);
+   L.live = a.take(nb1), L.gain = a.take(ni1 * 8);
+   L.exp = a.take(nb1 * 8), L.res = a.take(nb1 * 8), L.score = a.take(ni1 * 8);
+   L.ll = a.take(nl1 * 8), L.dev = a.take(nl1 * 8), L.pear = a.take(nl1 * 8);
+   L.nlive = a.take(nl1 * 8), L.ndrop = a.take(nl1 * 8), L.nimp = a.take(nl1 * 8);
+   L.dof = a.take(nl1 * 4), L.worst = a.take(nl1 * 4);
+   L.bytes = a.size;
+   return L;
+}
+
+// ---- the host forms' shared loops.  Every sum runs in the order the kernels' do: a column's over the live bins, ascending.
+
+// The kept words of one locus into K [(niso + 31) / 32] -> their number.  keep_of_locus null: no filter was given and every
+// isoform is kept (`ones` is the caller's scratch for that); status null: every locus started.
+inline int kept_words(const int32_t *keep_of_locus, int niso, const int32_t *status_of_locus, std::vector<int32_t> &ones, uint32_t *K)
+{
+   if (!keep_of_locus && (int)ones.size() < niso) ones.assign((size_t)niso, 1);
+   const int words = (niso + 31) / 32;
+   for (int w = 0; w < words; ++w) K[w] = ctx_kept_word(keep_of_locus ? keep_of_locus : ones.data(), niso, status_of_locus ? *status_of_locus : SBGPU_EM_OK, w);
+   return words;
+}
+
+// One locus' column pass: live [nb], then per column the sum c_j over the live bins (kept where `c` is given) and the gain g_j.
+// Fl: the locus' weights, row-major; K: its kept words.
+inline void column_pass_locus(const double *Fl, int64_t nb, int niso, const double *theta_of_locus, const uint32_t *K, uint8_t *live, double *g, double *c)
+{
+   for (int64_t b = 0; b < nb; ++b) live[b] = asg_row_live(Fl + b * niso, niso);
+   for (int j = 0; j < niso; ++j) {
+      double cj = 0.0;
+      for (int64_t b = 0; b < nb; ++b)
+         if (live[b]) cj += Fl[b * niso + j];
+      if (c) c[j] = cj;
+      g[j] = asg_gain(theta_of_locus[j], cj, (K[j >> 5] >> (j & 31)) & 1u);
+   }
+}
+
+// The column pass of a whole sample: what asg_column_kernel leaves, plus the kept words (locus l's begin at word_off[l])
+struct ColumnPass {
+   std::vector<int64_t> word_off; // [n_loci + 1]
+   std::vector<uint32_t> kept;
+   std::vector<uint8_t> live;     // [n_bins]
+   std::vector<double> gain;      // [n_iso]
+};
+// -> false when a locus has more kept words than max_words (the hits' compat words do not cover it)
+inline bool column_pass(int64_t n_loci, const int64_t *row_off, const int64_t *iso_off, const int64_t *f_off, const double *F, const double *theta,
+                        const int32_t *keep, const int32_t *status, int max_words, ColumnPass *out)
+{
+   out->word_off.assign((size_t)n_loci + 1, 0);
+   for (int64_t l = 0; l < n_loci; ++l) out->word_off[(size_t)l + 1] = out->word_off[(size_t)l] + (iso_off[l + 1] - iso_off[l] + 31) / 32;
+   out->kept.assign((size_t)out->word_off[(size_t)n_loci] + 1, 0u);
+   out->live.assign((size_t)row_off[n_loci] + 1, 0);
+   out->gain.assign((size_t)iso_off[n_loci] + 1, 0.0);
+   std::vector<int32_t> ones;
+   for (int64_t l = 0; l < n_loci; ++l) {
+      const int64_t i0 = iso_off[l], b0 = row_off[l];
+      const int niso = (int)(iso_off[l + 1] - i0);
+      if ((niso + 31) / 32 > max_words) return false;
+      uint32_t *K = out->kept.data() + out->word_off[(size_t)l];
+      kept_words(keep ? keep + i0 : nullptr, niso, status ? status + l : nullptr, ones, K);
+      column_pass_locus(F + f_off[l], row_off[l + 1] - b0, niso, theta + i0, K, out->live.data() + b0, out->gain.data() + i0, nullptr);
+   }
+   return true;
+}
+
+// Which locus hit h is in, given its bin b (< 0: none) and the answer for the hit before, l: the bin's locus, or -- a hit
+// without a bin says nothing of its locus -- the hits' grouping's.  -1: no bin and no grouping (locus_hit_off null).
+inline int64_t locus_of_hit(int64_t h, int64_t b, int64_t l, int64_t n_loci, const int64_t *row_off, const int64_t *locus_hit_off)
+{
+   const int64_t *off = b >= 0 ? row_off : locus_hit_off;
+   const int64_t x = b >= 0 ? b : h;
+   if (!off) return -1;
+   return x < off[l] || x >= off[l + 1] ? std::upper_bound(off, off + n_loci + 1, x) - off - 1 : l;
+}
+
+} // namespace sb

@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._results import Results, addr, as_array, bins_info, check_lengths, check_tensors, ptr
 
 NAMES = _lib.sbgpu_em_fit_t._NAMES
 PER_BIN, PER_ISO = ("expected", "resid"), ("score",)
@@ -28,38 +29,17 @@ def limits():
     return dict(zip(LIMIT_NAMES, (int(x) for x in out)))
 
 
-class ModelFit:
+class ModelFit(Results):
     """expected, resid [n_bins]; score [n_iso]; loglik, deviance, pearson (float64), n_live, n_dropped, n_impossible (int64), dof,
     worst_bin (int32) [n_loci].  want: the names to bring to the host (None: all) -- the device forms copy nothing else over
-    PCIe; the others are None.  row_off / iso_off: the batch's, for the per-locus views."""
+    PCIe; the others are None.  row_off / iso_off: the batch's, for the per-locus views.
+    .device: name -> device address of the context's copy (device forms; valid until its next quantify / fit call)."""
+    STRUCT = _lib.sbgpu_em_fit_t
 
     def __init__(self, row_off, iso_off, want=None):
         self.row_off, self.iso_off = np.asarray(row_off, np.int64), np.asarray(iso_off, np.int64)
         self.n_loci, self.n_bins, self.n_iso = len(self.row_off) - 1, int(self.row_off[-1]), int(self.iso_off[-1])
-        unknown = set(want or ()) - set(NAMES)
-        if unknown:
-            raise ValueError("ModelFit: unknown arrays %s" % sorted(unknown))
-        self._sizes = {k: self.n_bins if k in PER_BIN else self.n_iso if k in PER_ISO else self.n_loci for k in NAMES}
-        for k, n in self._sizes.items():
-            setattr(self, k, np.zeros(max(n, 1), DTYPES[k]) if want is None or k in want else None)
-        self.device = {}     # device forms: name -> device address of the context's copy (valid until its next quantify / fit call)
-
-    def _struct(self):
-        s = _lib.sbgpu_em_fit_t()
-        for k in NAMES:
-            a = getattr(self, k)
-            setattr(s, k, None if a is None else a.ctypes.data)
-        return s
-
-    def _finish(self, s):
-        for k, n in self._sizes.items():
-            a = getattr(self, k)
-            if a is not None:
-                setattr(self, k, a[:n])
-            p = getattr(s, "d_" + k)
-            if p:
-                self.device[k] = int(p)
-        return self
+        self._arrays({k: (self.n_bins if k in PER_BIN else self.n_iso if k in PER_ISO else self.n_loci, DTYPES[k]) for k in NAMES}, want)
 
     def reduced_chi2(self):
         """pearson / dof where dof > 0, NaN elsewhere"""
@@ -87,29 +67,15 @@ class ModelFit:
             yield row if step is None else row + (float(step[l]),)
 
 
-def _addr(x):
-    return None if x is None else (int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x))
-
-
-def _check_tensors(who, **tensors):
-    for name, (x, dt) in tensors.items():
-        if hasattr(x, "data_ptr") and (str(x.dtype) != dt or not x.is_cuda or not x.is_contiguous()):
-            raise ValueError("%s: %s must be a contiguous %s tensor on the context's device" % (who, name, dt))
-
-
 def em_fit_host(batch, theta, keep=None, status=None, want=None):
     """batch: row_off, iso_off, f_off, count, F (synth.LocusBatch); theta [n_iso]; keep [n_iso] / status [n_loci] or None."""
     L = _lib.load()
     row_off, iso_off, f_off = (np.ascontiguousarray(a, np.int64) for a in (batch.row_off, batch.iso_off, batch.f_off))
     count, F = np.ascontiguousarray(batch.count, np.int32), np.ascontiguousarray(batch.F, np.float64)
-    as_ = lambda a, dt: None if a is None else np.ascontiguousarray(a, dt)  # noqa: E731
-    theta, keep, status = as_(theta, np.float64), as_(keep, np.int32), as_(status, np.int32)
+    theta, keep, status = as_array(theta, np.float64), as_array(keep, np.int32), as_array(status, np.int32)
     t = ModelFit(row_off, iso_off, want)
-    for name, a, n in (("theta", theta, t.n_iso), ("keep", keep, t.n_iso), ("status", status, t.n_loci), ("count", count, t.n_bins),
-                       ("F", F, int(f_off[-1]))):
-        if a is not None and a.size < n:
-            raise ValueError("em_fit_host: %s holds %d entries, %d are needed" % (name, a.size, n))
-    ptr = lambda x: None if x is None or x.size == 0 else x.ctypes.data  # noqa: E731
+    check_lengths("em_fit_host", ("theta", theta, t.n_iso), ("keep", keep, t.n_iso), ("status", status, t.n_loci), ("count", count, t.n_bins),
+                  ("F", F, int(f_off[-1])))
     b = _lib.sbgpu_batch_t(t.n_loci, row_off.ctypes.data, iso_off.ctypes.data, f_off.ctypes.data, ptr(count), ptr(F))
     s = t._struct()
     _lib.check(L.sbgpu_em_fit_host(C.byref(b), theta.ctypes.data if theta is not None else None, ptr(keep), ptr(status), C.byref(s)),
@@ -120,11 +86,11 @@ def em_fit_host(batch, theta, keep=None, status=None, want=None):
 def em_fit_device(ctx, plan, d_count, d_F, d_theta, d_keep=None, d_status=None, stream=None, want=None):
     """plan: an em.Plan; d_count (int32), d_F, d_theta (float64), d_keep, d_status (int32): torch tensors on the context's
     device, or device addresses; d_theta: the EM's, or any other estimate (a bootstrap mean)."""
-    _check_tensors("em_fit_device", d_count=(d_count, "torch.int32"), d_F=(d_F, "torch.float64"), d_theta=(d_theta, "torch.float64"),
+    check_tensors("em_fit_device", d_count=(d_count, "torch.int32"), d_F=(d_F, "torch.float64"), d_theta=(d_theta, "torch.float64"),
                    d_keep=(d_keep, "torch.int32"), d_status=(d_status, "torch.int32"))
     t = ModelFit(plan.row_off, plan.iso_off, want)
     s = t._struct()
-    _lib.check(ctx.L.sbgpu_em_fit_device(ctx.h, plan.h, _addr(d_count), _addr(d_F), _addr(d_theta), _addr(d_keep), _addr(d_status), stream,
+    _lib.check(ctx.L.sbgpu_em_fit_device(ctx.h, plan.h, addr(d_count), addr(d_F), addr(d_theta), addr(d_keep), addr(d_status), stream,
                                          C.byref(s)), "sbgpu_em_fit_device")
     return t._finish(s)
 
@@ -135,14 +101,12 @@ def model_fit_device(ctx, handle, d_theta, d_keep=None, d_status=None, stream=No
     mean); d_keep / d_status: the call's (int32), or None: everything kept / every locus started."""
     L = ctx.L
     handle = getattr(handle, "h", handle)
-    _check_tensors("model_fit_device", d_theta=(d_theta, "torch.float64"), d_keep=(d_keep, "torch.int32"), d_status=(d_status, "torch.int32"))
-    info = (C.c_int64 * 8)()
-    _lib.check(L.sbgpu_bins_info(handle, info), "sbgpu_bins_info")
-    n_loci = int(info[0])
+    check_tensors("model_fit_device", d_theta=(d_theta, "torch.float64"), d_keep=(d_keep, "torch.int32"), d_status=(d_status, "torch.int32"))
+    n_loci = bins_info(L, handle)[0]
     row_off, iso_off = np.zeros(n_loci + 1, np.int64), np.zeros(n_loci + 1, np.int64)
     _lib.check(L.sbgpu_bins_export(handle, row_off.ctypes.data, iso_off.ctypes.data, *([None] * 11)), "sbgpu_bins_export")
     t = ModelFit(row_off, iso_off, want)
     s = t._struct()
-    _lib.check(L.sbgpu_model_fit_device(ctx.h, handle, _addr(d_theta), _addr(d_keep), _addr(d_status), stream, C.byref(s)),
+    _lib.check(L.sbgpu_model_fit_device(ctx.h, handle, addr(d_theta), addr(d_keep), addr(d_status), stream, C.byref(s)),
                "sbgpu_model_fit_device")
     return t._finish(s)

@@ -31,7 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 ITEM_HITS = 16384       # csrc/assign_device.h: kAsgItemHits
-ITEM_BYTES = 24         # sizeof(sb::AsgItem)
+ITEM_BYTES = 24         # sizeof(sb::HitItem), csrc/stage_host.h
 
 
 def summary(ms):

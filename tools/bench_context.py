@@ -31,7 +31,7 @@ sys.path.insert(0, ROOT)
 
 
 COUNT_ITEM_HITS = 16384     # csrc/context_device.h: kCtxItemHits
-COUNT_ITEM_BYTES = 24       # sizeof(sb::CtxItem)
+COUNT_ITEM_BYTES = 24       # sizeof(sb::HitItem), csrc/stage_host.h
 
 
 def timed(fn, reps, warmup=1):

@@ -30,7 +30,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-ITEM_BYTES = 24         # sizeof(sb::CovItem)
+ITEM_BYTES = 24         # sizeof(sb::HitItem), csrc/stage_host.h
 
 
 def summary(ms):
