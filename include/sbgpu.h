@@ -1133,6 +1133,100 @@ int sbgpu_model_fit_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins, const dou
  * most isoforms of one locus.                                                                                              */
 int sbgpu_em_fit_limits(int64_t out[8]);
 
+/* ---- isoform information: identifiability and analytic covariance ----------------------------------------
+ * Which isoforms of a locus the counted bins can tell apart, which are confounded with which, and how strongly: the observed
+ * information matrix of the locus' mixture at theta, its factorisation, and the covariance of theta that follows -- one pass
+ * over arrays a batch holds anyway, where a bootstrap costs one EM solve per replicate and cannot report rank deficiency.  The
+ * rule (csrc/info_rules.h, shared by both forms, compiled under -ffp-contract=off).  One locus: bins b with counts n_b, isoforms
+ * j, raw weights F[b][j], the caller's theta, keep, status.  Every sum starts from 0.0 and adds in ascending index unless said.
+ *    1. kept(j), the live bins, c_j, g_j, d_b and "possible" ARE the assignment's and the fit's above (ctx_kept_word,
+ *       asg_row_live, asg_gain, fit_bin_mass, fit_possible): called, not restated.
+ *    2. w_b = ((double)n_b / d_b) / d_b for a possible bin (fit_ratio, then one more division), 0.0 otherwise.
+ *    3. j is FREE when it is kept, c_j != 0 and g_j > 0 (a NaN is not free); n_free counts the free isoforms.
+ *    4. For free j <= k: H_jk = (S_jk / c_j) / c_k, the information matrix in theta units.  S_jk is the WAVE-ORDER sum over the
+ *       locus' bins of (w_b * F[b][j]) * F[b][k]: partial[t], t = 0 .. 63, is the ascending sum of the terms of the bins
+ *       b = t (mod 64), 0.0 where there are none; then for s = 32, 16, ..., 1: partial[i] += partial[i + s] for i < s; the
+ *       result is partial[0].  (A wave's natural reduction: lane i adds lane i + s.  Both forms run this order.)
+ *    5. A free j with !(H_jj > 0) is UNOBSERVED -- no counted bin carries it -- and is left out of everything below.
+ *    6. dg_j = sqrt(H_jj); C_jk = (H_jk / dg_j) / dg_k.  C_jj is taken as computed, not set to 1.
+ *    7. C is factorised without pivoting, in ascending j over the observed free isoforms; R is the set retained so far.
+ *       piv_j = C_jj - sum over k in R of L_jk * L_jk.  If !(piv_j > SBGPU_INFO_PIVOT_EPS), j is ALIASED: on the observed
+ *       bins its column is a combination of the retained ones; it does not join R, and alias_of[j] is the k in R of largest
+ *       |L_jk| (strict > in ascending k; a NaN never wins; -1 where there is none).  Otherwise j joins R with
+ *       L_jj = sqrt(piv_j) and, for every later observed i, L_ij = (C_ij - sum over k in R, k < j, of L_ik * L_jk) / L_jj.
+ *       rank = |R|; min_pivot = the smallest retained piv_j, 0.0 where R is empty.
+ *    8. Y = L_R^-1, a column at a time: Y_jj = 1 / L_jj, Y_ij = -(sum over k in R, j <= k < i, of L_ik * Y_kj) / L_ii.
+ *       V_ij = sum over k in R, k >= max(i, j), of Y_ki * Y_kj.  Hinv_ij = (V_ij / dg_i) / dg_j.
+ *    9. The covariance of theta GIVEN THE LOCUS' TOTAL (on the simplex): u_i = sum over j in R of Hinv_ij; t = sum over i in R of
+ *       u_i; cov_ij = Hinv_ij - (u_i * u_j) / t where t > 0, Hinv_ij otherwise; se[j] = sqrt(max(cov_jj, 0.0)).  In a locus
+ *       whose rank is below its number of observed free isoforms these describe the model WITH THE ALIASED ISOFORMS HELD
+ *       FIXED at the caller's theta: the data say nothing about moving mass between an aliased isoform and its alias_of.
+ *       This is normal theory at an interior point; for a theta_j near 0 it is one-sided (theta_j cannot go below 0) and
+ *       se[j] overstates the spread downwards.  Intervals and p-values are the caller's.
+ *   10. For j in R: corr_jk = cov_jk / (se_j * se_k) where both are > 0; partner[j] is the k in R, k != j, of largest |corr_jk|
+ *       (strict > in ascending k; -1 where there is none); partner_corr[j] is that signed value, 0.0 where there is none.
+ *   11. ident[j]: SBGPU_INFO_IDENTIFIED (j in R), _ALIASED, _UNOBSERVED, _NOT_FREE, or _SKIPPED (its locus was not analysed).
+ *       alias_of and partner are locus-local isoform indices.
+ *   12. info_status[l]: SBGPU_INFO_OK; SBGPU_INFO_EMPTY -- status SBGPU_EM_INIT_EMPTY, nothing kept, or n_free == 0: every
+ *       isoform is _NOT_FREE, everything else zero or -1; SBGPU_INFO_TOO_WIDE -- n_free exceeds out[0] of sbgpu_em_info_limits,
+ *       or (device forms only) the locus exceeds the assignment's shape limits: every isoform is _SKIPPED, everything else zero
+ *       or -1.  A status, not a refusal of the call.
+ *   13. cov (optional): packed by locus, the upper triangle over ALL of the locus' niso isoforms in row-major order -- entry
+ *       (j, k), j <= k, at cov_off[l] + j * niso - j (j - 1) / 2 + (k - j) -- zero where either isoform is not in R.
+ *       cov_off[l + 1] - cov_off[l] = niso (niso + 1) / 2 for niso <= out[0] of sbgpu_em_info_limits, 0 beyond;
+ *       sbgpu_em_info_cov_offsets fills it, so that the caller can size cov before the call.
+ * Out of this rule: pivoted factorisations, loci of more free isoforms than the limit, boundary corrections.
+ * The struct: host arrays to fill (any may be NULL; cov needs cov_off) and, on return -- device forms only -- the device arrays
+ * of all of them: the context's memory, in a scratch slot of their own, valid until the context's next sbgpu_quantify_* or
+ * info call.                                                                                                               */
+#define SBGPU_INFO_PIVOT_EPS 1e-9
+#define SBGPU_INFO_IDENTIFIED 0
+#define SBGPU_INFO_ALIASED 1
+#define SBGPU_INFO_UNOBSERVED 2
+#define SBGPU_INFO_NOT_FREE 3
+#define SBGPU_INFO_SKIPPED 4
+#define SBGPU_INFO_OK 0
+#define SBGPU_INFO_EMPTY 1
+#define SBGPU_INFO_TOO_WIDE 2
+typedef struct {
+   double *se, *partner_corr;                      /* in: [n_iso]   */
+   int32_t *ident, *alias_of, *partner;            /* in: [n_iso]   */
+   double *min_pivot;                              /* in: [n_loci]  */
+   int32_t *rank, *n_free, *info_status;           /* in: [n_loci]  */
+   double *cov;                                    /* in: [cov_off[n_loci]], or NULL */
+   const int64_t *cov_off;                         /* in: [n_loci + 1], needed where cov is given (sbgpu_em_info_cov_offsets) */
+   const double *d_se, *d_partner_corr;            /* out: device forms only */
+   const int32_t *d_ident, *d_alias_of, *d_partner;
+   const double *d_min_pivot;
+   const int32_t *d_rank, *d_n_free, *d_info_status;
+   const double *d_cov;
+   const int64_t *d_cov_off;
+} sbgpu_em_info_t;
+/* cov_off [n_loci + 1] from iso_off [n_loci + 1] (rule 13).  SBGPU_EINVAL: a NULL array, n_loci < 0, offsets that do not ascend. */
+int sbgpu_em_info_cov_offsets(const int64_t *iso_off, int64_t n_loci, int64_t *cov_off);
+/* Host form (csrc/info_host.cpp; no GPU needed, free of HIP), the plain statement of the rule.  Arguments and refusals as
+ * sbgpu_em_fit_host's; further SBGPU_EINVAL: cov given without cov_off, or a cov_off that is not rule 13's.                 */
+int sbgpu_em_info_host(const sbgpu_batch_t *batch, const double *theta, const int32_t *keep, const int32_t *status, sbgpu_em_info_t *out);
+/* Device form (csrc/info_device.h) for any batch sbgpu_em_run_device solves; arguments as sbgpu_em_fit_device's.  The
+ * assignment's column pass (unchanged), then one pass per locus: a wave per locus of at most out[1] weights and out[2] isoforms
+ * of sbgpu_em_info_limits, a workgroup per larger locus.  Every sum runs in the rule's order (S_jk along the wave's own
+ * reduction), there are no floating-point atomics: every array is the host form's, bit for bit, and two calls give the same
+ * bits.  A locus beyond the assignment's shape limits (4096 isoforms, 5632 bins) is SBGPU_INFO_TOO_WIDE, not a refusal.  Only
+ * the arrays the caller gave pointers for cross PCIe.  Synchronises on `stream` (NULL: the context's own).                  */
+int sbgpu_em_info_device(sbgpu_ctx_t *ctx, const sbgpu_plan_t *plan, const int32_t *d_count, const double *d_F, const double *d_theta,
+                         const int32_t *d_keep, const int32_t *d_status, void *stream, sbgpu_em_info_t *out);
+/* The same right after a resident call or an sbgpu_front_stream_end made with sbgpu_bootstrap_keep on, from that record, as
+ * sbgpu_model_fit_device: nothing more is retained, the call's seven results are the same bits with and without it, and info,
+ * fit, table, assignment and coverage may be asked for in any order.                                                     */
+int sbgpu_model_info_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins, const double *d_theta, const int32_t *d_keep, const int32_t *d_status,
+                            void *stream, sbgpu_em_info_t *out);
+/* The thresholds (csrc/info_rules.h, csrc/info_device.h; reasoned from LDS sizes, not tuned): out[0] the most free isoforms of
+ * an analysed locus (both forms; also the niso up to which cov has room); [1] weights (and bins) and [2] isoforms of a locus up
+ * to which a wave serves it, a workgroup beyond; [3] bins up to which the workgroup form keeps w_b, and weights up to which it
+ * stages F, in LDS (global memory beyond); [4] loci per workgroup in the wave form; [5] workgroups per CU a launch's grid is
+ * capped at; [6] the most bins and [7] the most isoforms of one locus the device form analyses.  A workgroup is 256 threads.  */
+int sbgpu_em_info_limits(int64_t out[8]);
+
 /* ---- the EM bootstrap: how far theta can be trusted -------------------------
  * The reference prints theta with no statement of its spread.  The bootstrap resamples every locus' fragments over its
  * bins, solves again, and reports mean and variance of theta over the replicates.

@@ -827,6 +827,89 @@ class ModelFit {
    }
 };
 
+/* The isoform information (sbgpu_em_info_* / sbgpu_model_info_device, include/sbgpu.h states the rule): which isoforms of every
+ * locus the counted bins identify, alias or never see, the standard error of theta given the locus' total, the strongest
+ * partner of every isoform, and -- packed by cov_off, the upper triangle over a locus' isoforms -- the covariance itself.
+ * host(): any batch with theta; no GPU.  device(plan, iso_off, ...) / device(bins, iso_off, ...): as ModelFit's; iso_off: the
+ * batch's host offsets [n_loci + 1], from which cov is sized (nullptr: no cov is brought to the host).                        */
+class IsoformInfo {
+ public:
+   std::vector<double> se, partner_corr;          /* [n_iso] */
+   std::vector<int32_t> ident, alias_of, partner; /* [n_iso] */
+   std::vector<double> min_pivot;                 /* [n_loci] */
+   std::vector<int32_t> rank, n_free, info_status; /* [n_loci] */
+   std::vector<double> cov;                       /* [cov_off[n_loci]] */
+   std::vector<int64_t> cov_off;                  /* [n_loci + 1] */
+   sbgpu_em_info_t raw{}; /* device(): the device arrays -- the context's, valid until its next quantify or info call; its host
+                             pointers are null after the call */
+
+   static IsoformInfo host(const sbgpu_batch_t &batch, const double *theta, const int32_t *keep = nullptr, const int32_t *status = nullptr)
+   {
+      if (batch.n_loci < 0 || !batch.row_off || !batch.iso_off) throw std::invalid_argument("IsoformInfo::host: bad n_loci or null offset array");
+      IsoformInfo t;
+      t.prepare(batch.n_loci, batch.iso_off[batch.n_loci], batch.iso_off);
+      check(sbgpu_em_info_host(&batch, theta, keep, status, &t.raw), "sbgpu_em_info_host");
+      t.done();
+      return t;
+   }
+   static IsoformInfo device(const Context &ctx, const sbgpu_plan_t *plan, const int64_t *iso_off, const int32_t *d_count, const double *d_F,
+                             const double *d_theta, const int32_t *d_keep = nullptr, const int32_t *d_status = nullptr, void *stream = nullptr)
+   {
+      int64_t info[8];
+      check(sbgpu_plan_info(plan, info), "sbgpu_plan_info");
+      IsoformInfo t;
+      t.prepare(info[0], info[2], iso_off);
+      check(sbgpu_em_info_device(ctx.get(), plan, d_count, d_F, d_theta, d_keep, d_status, stream, &t.raw), "sbgpu_em_info_device");
+      t.done();
+      return t;
+   }
+   static IsoformInfo device(const Context &ctx, const sbgpu_bins_t *bins, const int64_t *iso_off, const double *d_theta,
+                             const int32_t *d_keep = nullptr, const int32_t *d_status = nullptr, void *stream = nullptr)
+   {
+      int64_t info[8];
+      check(sbgpu_bins_info(bins, info), "sbgpu_bins_info");
+      IsoformInfo t;
+      t.prepare(info[0], info[1], iso_off);
+      check(sbgpu_model_info_device(ctx.get(), bins, d_theta, d_keep, d_status, stream, &t.raw), "sbgpu_model_info_device");
+      t.done();
+      return t;
+   }
+   /* entry (j, k) of locus l's covariance; 0.0 where the locus has no packed block */
+   double covariance(int64_t l, int64_t niso, int64_t j, int64_t k) const
+   {
+      if (j > k) std::swap(j, k);
+      if (cov_off.empty() || cov_off[(size_t)l + 1] - cov_off[(size_t)l] != niso * (niso + 1) / 2) return 0.0;
+      return cov[(size_t)(cov_off[(size_t)l] + j * niso - j * (j - 1) / 2 + (k - j))];
+   }
+
+ private:
+   void prepare(int64_t n_loci, int64_t n_iso, const int64_t *iso_off)
+   {
+      const size_t nl = (size_t)n_loci + 1, ni = (size_t)n_iso + 1; /* (one spare entry: data() of an empty vector may be null) */
+      se.assign(ni, 0.0), partner_corr.assign(ni, 0.0), ident.assign(ni, 0), alias_of.assign(ni, -1), partner.assign(ni, -1);
+      min_pivot.assign(nl, 0.0), rank.assign(nl, 0), n_free.assign(nl, 0), info_status.assign(nl, 0);
+      raw = sbgpu_em_info_t{};
+      cov_off.clear(), cov.clear();
+      if (iso_off) {
+         cov_off.assign(nl, 0);
+         check(sbgpu_em_info_cov_offsets(iso_off, n_loci, cov_off.data()), "sbgpu_em_info_cov_offsets");
+         cov.assign((size_t)cov_off[(size_t)n_loci] + 1, 0.0);
+         raw.cov = cov.data(), raw.cov_off = cov_off.data();
+      }
+      raw.se = se.data(), raw.partner_corr = partner_corr.data(), raw.ident = ident.data(), raw.alias_of = alias_of.data(), raw.partner = partner.data();
+      raw.min_pivot = min_pivot.data(), raw.rank = rank.data(), raw.n_free = n_free.data(), raw.info_status = info_status.data();
+   }
+   void done()
+   {
+      raw.se = raw.partner_corr = raw.min_pivot = raw.cov = nullptr;
+      raw.ident = raw.alias_of = raw.partner = raw.rank = raw.n_free = raw.info_status = nullptr;
+      raw.cov_off = nullptr;
+      se.pop_back(), partner_corr.pop_back(), ident.pop_back(), alias_of.pop_back(), partner.pop_back();
+      min_pivot.pop_back(), rank.pop_back(), n_free.pop_back(), info_status.pop_back();
+      if (!cov.empty()) cov.pop_back();
+   }
+};
+
 /* The bootstrap of the resident path (sbgpu_bootstrap_keep / sbgpu_abundance_bootstrap_device, include/sbgpu.h): FPKM and TPM
  * mean, variance and percentile interval over resampled bin counts, with the replicates in which the expression filter kept
  * each isoform.  keep(): before the resident call; device(): right after it, on that call's handle.  interval_ranks(): the two

@@ -48,6 +48,7 @@ SYMBOLS = [
     "sbgpu_fragment_assign_host", "sbgpu_fragment_assign_device",
     "sbgpu_isoform_coverage_host", "sbgpu_isoform_coverage_device", "sbgpu_isoform_coverage_limits",
     "sbgpu_em_fit_host", "sbgpu_em_fit_device", "sbgpu_model_fit_device", "sbgpu_em_fit_limits",
+    "sbgpu_em_info_host", "sbgpu_em_info_device", "sbgpu_model_info_device", "sbgpu_em_info_limits", "sbgpu_em_info_cov_offsets",
 ]
 
 
@@ -166,6 +167,11 @@ class sbgpu_isoform_coverage_t(C.Structure):
 
 class sbgpu_em_fit_t(C.Structure):
     _NAMES = ("expected", "resid", "score", "loglik", "deviance", "pearson", "n_live", "n_dropped", "n_impossible", "dof", "worst_bin")
+    _fields_ = [(n, C.c_void_p) for n in _NAMES] + [("d_" + n, C.c_void_p) for n in _NAMES]
+
+
+class sbgpu_em_info_t(C.Structure):
+    _NAMES = ("se", "partner_corr", "ident", "alias_of", "partner", "min_pivot", "rank", "n_free", "info_status", "cov", "cov_off")
     _fields_ = [(n, C.c_void_p) for n in _NAMES] + [("d_" + n, C.c_void_p) for n in _NAMES]
 
 
@@ -359,6 +365,11 @@ def load():
     L.sbgpu_em_fit_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(sbgpu_em_fit_t)]
     L.sbgpu_model_fit_device.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(sbgpu_em_fit_t)]
     L.sbgpu_em_fit_limits.argtypes = [C.POINTER(C.c_int64)]
+    L.sbgpu_em_info_host.argtypes = [C.POINTER(sbgpu_batch_t), vp, vp, vp, C.POINTER(sbgpu_em_info_t)]
+    L.sbgpu_em_info_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(sbgpu_em_info_t)]
+    L.sbgpu_model_info_device.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(sbgpu_em_info_t)]
+    L.sbgpu_em_info_limits.argtypes = [C.POINTER(C.c_int64)]
+    L.sbgpu_em_info_cov_offsets.argtypes = [vp, C.c_int64, vp]
     L.sbgpu_bootstrap_counts_host.argtypes = [C.c_int64, vp, vp, vp, C.c_uint64, C.c_int32, vp]
     L.sbgpu_bootstrap_counts_device.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp]
     L.sbgpu_em_bootstrap_device.argtypes = [vp, vp, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp, vp, vp, vp, vp, vp]

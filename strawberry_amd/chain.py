@@ -233,7 +233,8 @@ class ChainQuantifier:
         posterior, isoform_coverage() the per-exon bases and junction support (all from the same retention, in any order,
         repeatedly).
         keep_bootstrap=True (resident only): likewise for the bootstrap (sbgpu_bootstrap_keep); abundance_bootstrap() runs it on the
-        last step's handle, model_fit() the model fit (fit.model_fit_device), which works from the same retention."""
+        last step's handle, model_fit() the model fit (fit.model_fit_device) and isoform_information() the isoform information
+        (info.model_info_device), which work from the same retention."""
         import torch
         self.torch, self.ctx = torch, ctx
         self.dev = torch.device("cuda", ctx.device)
@@ -382,6 +383,16 @@ class ChainQuantifier:
             raise _lib.SbgpuError("model_fit: no step has run with keep_bootstrap=True")
         return fit.model_fit_device(self.ctx, self.context_handle, int(self._out.d_theta) if d_theta is None else d_theta,
                                     int(self._out.d_keep), int(self._out.d_status), want=want)
+
+    def isoform_information(self, d_theta=None, want=None):
+        """The isoform information of the last step (keep_bootstrap=True: it works from the bootstrap's retention):
+        info.model_info_device on its handle under the step's own theta -- or d_theta, a float64 tensor / device address [n_iso]
+        -- with the step's keep and status -> an info.IsoformInfo.  want: the arrays to bring to the host (None: all)."""
+        from . import info
+        if self.context_handle is None or not self.keep_bootstrap:
+            raise _lib.SbgpuError("isoform_information: no step has run with keep_bootstrap=True")
+        return info.model_info_device(self.ctx, self.context_handle, int(self._out.d_theta) if d_theta is None else d_theta,
+                                      int(self._out.d_keep), int(self._out.d_status), want=want)
 
     def locus_abundance(self):
         """Abundances per locus of the last resident step (bootstrap.locus_abundance_device on the device arrays the call left:

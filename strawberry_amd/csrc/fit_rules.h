@@ -7,7 +7,9 @@
 // Everything here is compiled under -ffp-contract=off.
 #pragma once
 
+#ifdef __HIPCC__ // (a plain C++ compiler takes this header too: context_rules.h, below, gives it the qualifiers)
 #include <hip/hip_runtime.h>
+#endif
 #include <math.h>
 #include <stdint.h>
 

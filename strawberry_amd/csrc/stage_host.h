@@ -1,5 +1,5 @@
 // strawberry_amd/csrc/stage_host.h -- what the retained-result stages (the `-f` table, the fragment assignment, the isoform
-// coverage, the model fit) share on the host, free of HIP: a plain C++ compiler takes this header alone.
+// coverage, the model fit, the isoform information) share on the host, free of HIP: a plain C++ compiler takes this header alone.
 //   - the limits of one locus and the work item of the hit kernels (one definition; the stages' headers alias them),
 //   - the builder of the work items,
 //   - the arena's layout: Arena::take, and each stage's offsets as one struct made by one function,
@@ -138,6 +138,31 @@ inline FitLayout fit_layout(int64_t n_loci, int64_t n_bins, int64_t n_iso, size_
    L.ll = a.take(nl1 * 8), L.dev = a.take(nl1 * 8), L.pear = a.take(nl1 * 8);
    L.nlive = a.take(nl1 * 8), L.ndrop = a.take(nl1 * 8), L.nimp = a.take(nl1 * 8);
    L.dof = a.take(nl1 * 4), L.worst = a.take(nl1 * 4);
+   L.bytes = a.size;
+   return L;
+}
+
+struct InfoLayout {
+   size_t small, large, covoff, upload_bytes; // the two lists of loci, the packed covariance's offsets
+   size_t keep, status;                       // where the caller gave none
+   size_t live, gain, w;
+   size_t se, pcorr, ident, alias, partner, minpiv, rank, nfree, istatus;
+   size_t cov, cov_bytes, bytes;              // zeroed per call: [cov, cov + cov_bytes)
+};
+inline InfoLayout info_layout(int64_t n_loci, int64_t n_bins, int64_t n_iso, int64_t n_cov, size_t n_small, size_t n_large, bool own_keep, bool own_status)
+{
+   const size_t nl1 = (size_t)n_loci + 1, nb1 = at_least_1(n_bins), ni1 = at_least_1(n_iso);
+   Arena a;
+   InfoLayout L;
+   L.small = a.take((n_small + 1) * 4), L.large = a.take((n_large + 1) * 4), L.covoff = a.take(nl1 * 8);
+   L.upload_bytes = a.size;
+   L.keep = a.take(own_keep ? ni1 * 4 : 0), L.status = a.take(own_status ? nl1 * 4 : 0);
+   L.live = a.take(nb1), L.gain = a.take(ni1 * 8), L.w = a.take(nb1 * 8);
+   L.se = a.take(ni1 * 8), L.pcorr = a.take(ni1 * 8);
+   L.ident = a.take(ni1 * 4), L.alias = a.take(ni1 * 4), L.partner = a.take(ni1 * 4);
+   L.minpiv = a.take(nl1 * 8), L.rank = a.take(nl1 * 4), L.nfree = a.take(nl1 * 4), L.istatus = a.take(nl1 * 4);
+   L.cov = a.take(at_least_1(n_cov) * 8);
+   L.cov_bytes = a.size - L.cov;
    L.bytes = a.size;
    return L;
 }

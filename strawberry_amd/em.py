@@ -267,6 +267,15 @@ class EmBatchSolver:
         return fit.em_fit_device(self.ctx, self.plan, self.d_count, self.d_F, self.d_theta if d_theta is None else d_theta, d_keep,
                                  self.d_status if d_status is None else d_status, stream=self._stream(), want=want)
 
+    def run_info(self, d_theta=None, d_keep=None, d_status=None, want=None):
+        """The isoform information of the batch (sbgpu_em_info_device; info.py): which isoforms of every locus the counted bins
+        identify, alias or never see, and the analytic covariance of theta, under the last run_em's theta and status -- or
+        d_theta / d_status, device tensors of another estimate -- and d_keep (None: every isoform kept).  Synchronises on torch's
+        current stream -> an info.IsoformInfo of host arrays (want: which)."""
+        from . import info
+        return info.em_info_device(self.ctx, self.plan, self.d_count, self.d_F, self.d_theta if d_theta is None else d_theta, d_keep,
+                                   self.d_status if d_status is None else d_status, stream=self._stream(), want=want)
+
     def bootstrap_counts(self, n_rep, seed, rep_first=0, locus_id=None):
         """The replicates' counts alone (sbgpu_bootstrap_counts_device) -> int32 device tensor [n_rep, total rows]"""
         n = self.batch.n_loci

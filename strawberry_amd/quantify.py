@@ -228,7 +228,7 @@ class BinsHandle:
 
 def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=False, ctx=None, device=0, comm=None,
                       min_isoform_frac=0.0, filter_by_expression=True, effective_len_norm=False, with_context=False, bootstrap=None,
-                      keep_bootstrap=False, keep_handle=False, with_assignment=False, with_coverage=False, with_fit=False):
+                      keep_bootstrap=False, keep_handle=False, with_assignment=False, with_coverage=False, with_fit=False, with_info=False):
     """sbgpu_quantify_resident on host hits brought to the device first (torch owns the copies): pass 1 (insert=None: the
     empirical insert-size law, built on the device), bins, weights, EM, FPKM / Frac / keep, the FPKM all-reduce over `comm`
     (dist.AbiComm / dist.HostComm; None: a world of one), TPM.  The hits must come grouped by locus.
@@ -243,6 +243,8 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     With locus=True among them the bootstrap is sbgpu_locus_bootstrap_device: "bootstrap" also holds "frac" and "locus" (DESIGN 3.19).
     with_fit: the bootstrap's retention, and the model fit under the call's theta, keep and status, built on the device
     (fit.model_fit_device) -> "fit": a fit.ModelFit; "bins" as with_context.
+    with_info: the bootstrap's retention, and the isoform information under the call's theta, keep and status, built on the device
+    (info.model_info_device) -> "isoform_info": an info.IsoformInfo ("info" is the handle's sizes); "bins" as with_context.
     keep_bootstrap: retention for the bootstrap on, without running it (for a caller that runs it several times).
     keep_handle: the handle is not exported but returned as "handle", a BinsHandle that owns it -- it is destroyed by its close(),
     as a context manager, or when the object is collected; the caller runs bootstrap.abundance_bootstrap_device /
@@ -279,7 +281,7 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     retain = bool(with_context) or bool(with_assignment) or bool(with_coverage)
     if retain:
         _lib.check(L.sbgpu_context_table_keep(ctx.h, 1), "sbgpu_context_table_keep")
-    keep_bootstrap = bool(keep_bootstrap) or bootstrap is not None or bool(with_fit)
+    keep_bootstrap = bool(keep_bootstrap) or bootstrap is not None or bool(with_fit) or bool(with_info)
     if keep_bootstrap:
         _lib.check(L.sbgpu_bootstrap_keep(ctx.h, 1), "sbgpu_bootstrap_keep")
     try:
@@ -298,9 +300,10 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     owner = BinsHandle(L, handle) if keep_handle else None     # (from here on an exception frees the handle with the object)
     info = (C.c_int64 * 8)()
     _lib.check(L.sbgpu_bins_info(handle, info), "sbgpu_bins_info")
-    table = bins = boot = assignment = cov = model_fit = None
-    if retain or bootstrap is not None or with_fit:
+    table = bins = boot = assignment = cov = model_fit = iso_info = None
+    if retain or bootstrap is not None or with_fit or with_info:
         from . import assign, context, coverage, fit
+        from . import info as isoform_info
         from .bootstrap import abundance_bootstrap_device
         from .exonbin import LocusBins
         try:
@@ -314,6 +317,8 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
                 cov = coverage.isoform_coverage_device(ctx, handle, annot, hs, int(out.d_theta), d_hit_mass=d_mass)
             if with_fit:
                 model_fit = fit.model_fit_device(ctx, handle, int(out.d_theta), int(out.d_keep), int(out.d_status))
+            if with_info:
+                iso_info = isoform_info.model_info_device(ctx, handle, int(out.d_theta), int(out.d_keep), int(out.d_status))
         except Exception:
             if owner is None:
                 L.sbgpu_bins_destroy(handle)
@@ -338,6 +343,8 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
         r.update(bootstrap=boot, bins=bins)
     if with_fit:
         r.update(fit=model_fit, bins=bins)
+    if with_info:
+        r.update(isoform_info=iso_info, bins=bins)
     if keep_handle:
         r["handle"] = owner
     return r
