@@ -1227,6 +1227,116 @@ int sbgpu_model_info_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins, const do
  * capped at; [6] the most bins and [7] the most isoforms of one locus the device form analyses.  A workgroup is 256 threads.  */
 int sbgpu_em_info_limits(int64_t out[8]);
 
+/* ---- isoform support: drop-one likelihood-ratio statistics ------------------------------------------------
+ * Do the fragments of a locus need isoform j, or do its neighbours explain them as well?  Drop j, solve the locus again, compare
+ * the likelihoods.  The information pass above is one-sided exactly where this question lives (theta_j near 0), and a bootstrap
+ * costs B solves and only spreads a dispensable isoform's mass around.  The rule (csrc/loo_rules.h, shared by both forms,
+ * compiled under -ffp-contract=off).  One locus: bins b with counts n_b, isoforms j, raw weights F[b][j], keep (NULL: all kept;
+ * kept(j) is ctx_kept_word's bit under status SBGPU_EM_OK).  K is the number of kept isoforms.
+ *    1. loo_status[l]: SBGPU_LOO_EMPTY when K = 0; SBGPU_LOO_TOO_WIDE when K > SBGPU_LOO_MAX_KEPT -- a status, not a refusal of
+ *       the call: the neighbours are untouched; SBGPU_LOO_OK otherwise.  A locus beyond the fit's shape limits (5632 bins, 4096
+ *       isoforms) refuses the call with SBGPU_ESHAPE, as the fit does.
+ *    2. The sub-problems of an OK locus, in this order: the BASE -- the kept columns, ascending -- then, when K >= 2, one per kept
+ *       j, ascending: the kept columns without j.  Each is a locus of its own: the same bins and counts, F compacted row-major to
+ *       its columns.  The sub-problems of all loci are numbered consecutively (a sub-batch).  A K = 1 locus has the base only.
+ *    3. Each sub-problem is solved as sbgpu_em_run_device solves any locus (theta_0, the row drop, the statuses, the iteration
+ *       contract); the fit above then runs on it with nothing erased (keep NULL, status the solve's): loglik, n_live, n_dropped
+ *       and n_impossible are its rules 4 and 7.  The base is always solved inside the call, never taken from the caller: a locus
+ *       solved again alone does not always return a batch's theta bits.
+ *    4. n_unique[j] = (n_dropped + n_impossible) of j's sub-problem - the same of the base: the fragments no other kept isoform
+ *       explains.  An integer: exact.
+ *    5. lr_stat[j] = +inf when n_unique[j] > 0, else 2.0 * (loglik_base - loglik_without_j): one subtraction and one product.
+ *       Both solves stop at SBGPU_EM_THETA_CHANGE_LIMIT, not at the optimum: small negative values are real and are reported
+ *       raw.  The isoform of a K = 1 locus is SOLE: +inf, and its n_unique is the base's n_live - n_impossible.
+ *    6. heir[j] = the locus-local index of the kept k != j of largest theta_without_j[k] - theta_refit[k] under strict > in
+ *       ascending k, -1 when no gain is > 0 (a NaN never wins); heir_gain[j] is that difference, 0.0 where there is none: where
+ *       j's fragments go.
+ *    7. theta_refit [n_iso]: the base's theta scattered back, 0.0 for an isoform that is not kept or whose locus is not OK.
+ *       status_without[j], iters_without[j]: the sub-problem's, -1 for an isoform that is not TESTED.  support[j]:
+ *       SBGPU_LOO_NOT_KEPT, _TESTED, _SOLE, or _LOCUS_SKIPPED (kept, in a TOO_WIDE locus).  An isoform that is not TESTED or
+ *       SOLE has lr_stat 0.0, n_unique 0, heir -1, heir_gain 0.0.
+ *    8. Per locus: loo_status, and the base's loglik_base, status_base, iters_base (0.0, -1, -1 where the locus is not OK).
+ *    9. theta_without (optional) is packed: for a TESTED j, the K - 1 values of the other kept isoforms, ascending, at
+ *       without_off[j]; sbgpu_em_loo_offsets fills without_off [n_iso + 1], so that the caller can size it before the call.
+ * p-values are the caller's (the boundary mixture 1/2 chi2_0 + 1/2 chi2_1; strawberry_amd/support.py has one).
+ * Out of this rule: warm starts, loci of more kept isoforms than the limit, sets of isoforms, multiple-testing corrections.
+ * The struct: host arrays to fill (any may be NULL; theta_without needs without_off) and, on return -- device forms only -- the
+ * device arrays of all of them: the context's memory, in a scratch slot of their own, valid until the context's next
+ * sbgpu_quantify_* or support call.                                                                                       */
+#define SBGPU_LOO_MAX_KEPT 64
+#define SBGPU_LOO_OK 0
+#define SBGPU_LOO_EMPTY 1
+#define SBGPU_LOO_TOO_WIDE 2
+#define SBGPU_LOO_NOT_KEPT 0
+#define SBGPU_LOO_TESTED 1
+#define SBGPU_LOO_SOLE 2
+#define SBGPU_LOO_LOCUS_SKIPPED 3
+typedef struct {
+   double *lr_stat, *heir_gain, *theta_refit;                       /* in: [n_iso]   */
+   int64_t *n_unique;                                               /* in: [n_iso]   */
+   int32_t *heir, *status_without, *iters_without, *support;        /* in: [n_iso]   */
+   double *loglik_base;                                             /* in: [n_loci]  */
+   int32_t *loo_status, *status_base, *iters_base;                  /* in: [n_loci]  */
+   double *theta_without;                                           /* in: [without_off[n_iso]], or NULL */
+   const int64_t *without_off;                                      /* in: [n_iso + 1], needed where theta_without is given */
+   const double *d_lr_stat, *d_heir_gain, *d_theta_refit;           /* out: device forms only */
+   const int64_t *d_n_unique;
+   const int32_t *d_heir, *d_status_without, *d_iters_without, *d_support;
+   const double *d_loglik_base;
+   const int32_t *d_loo_status, *d_status_base, *d_iters_base;
+   const double *d_theta_without;
+   const int64_t *d_without_off;
+   int32_t *sub_count;                                              /* in, device forms only: [sizes[1]] and [sizes[3]] of the shapes  */
+   double *sub_F;                                                   /* call, or NULL: the expanded sub-batch, for a caller that checks it */
+} sbgpu_em_loo_t;
+typedef struct {
+   int64_t max_bytes; /* device scratch one chunk of sub-problems may take; 0: 1 GiB.  Any positive value is legal: consecutive
+                         whole loci form a chunk, and a locus above the budget is a chunk alone */
+   int64_t reserved;  /* 0 */
+} sbgpu_loo_params_t;
+/* without_off [n_iso + 1] from iso_off [n_loci + 1] and keep ([n_iso] or NULL) (rule 9).  SBGPU_EINVAL: a NULL array, n_loci < 0,
+ * offsets that do not begin at 0 or do not ascend.                                                                        */
+int sbgpu_em_loo_offsets(const int64_t *iso_off, const int32_t *keep, int64_t n_loci, int64_t *without_off);
+/* Host form (csrc/loo_host.cpp; no GPU needed, free of HIP) in three calls, because the library has no CPU EM: the caller solves
+ * the sub-batch between the second and the third.
+ * Shapes (rules 1, 2): sizes[4] = the sub-problems, their bins, isoforms and weights together -- always filled; every other
+ * output may be NULL (sizes first, then fill): loo_status [n_loci]; sub_locus, sub_drop [sizes[0]]: the parent locus, and the
+ * locus-local index of the dropped isoform, -1 for a base; sub_row_off, sub_iso_off, sub_f_off [sizes[0] + 1].  SBGPU_EINVAL:
+ * NULL offsets, n_loci < 0, offsets that do not begin at 0 or do not ascend; SBGPU_ESHAPE: rule 1.                          */
+int sbgpu_em_loo_shapes_host(int64_t n_loci, const int64_t *row_off, const int64_t *iso_off, const int32_t *keep, int64_t sizes[4],
+                             int32_t *loo_status, int32_t *sub_locus, int32_t *sub_drop, int64_t *sub_row_off, int64_t *sub_iso_off,
+                             int64_t *sub_f_off);
+/* Expansion (rule 2): the sub-batch's counts [sizes[1]] and weights [sizes[3]], a copy of the parent's.  Refusals as
+ * sbgpu_em_fit_host's for the batch.                                                                                      */
+int sbgpu_em_loo_expand_host(const sbgpu_batch_t *batch, const int32_t *keep, int32_t *sub_count, double *sub_F);
+/* Statistics (rules 4-9) from the sub-batch's solve -- sub_theta [sizes[2]], sub_status, sub_iters [sizes[0]] -- and its fit --
+ * sub_loglik, sub_n_live, sub_n_dropped, sub_n_impossible [sizes[0]].  SBGPU_EINVAL: a NULL input, malformed offsets,
+ * theta_without given without without_off, or a without_off that is not sbgpu_em_loo_offsets' for this batch.              */
+int sbgpu_em_loo_stat_host(int64_t n_loci, const int64_t *iso_off, const int32_t *keep, const double *sub_theta, const int32_t *sub_status,
+                           const int32_t *sub_iters, const double *sub_loglik, const int64_t *sub_n_live, const int64_t *sub_n_dropped,
+                           const int64_t *sub_n_impossible, sbgpu_em_loo_t *out);
+/* Device form (csrc/loo_device.h) for any batch sbgpu_em_run_device solves: the plan, d_count and d_F as given to it; d_keep: a
+ * device [n_iso] array or NULL; params: NULL for the defaults.  keep is read back once (the shapes are made on the host); then
+ * per chunk of loci: a plan for the chunk's sub-batch, loo_expand_kernel -- a workgroup per (locus, row tile), the tile's kept
+ * columns staged in LDS once and every sub-copy written from there: bitwise the host expansion, because it is a copy --, the EM
+ * through sbgpu_em_run_device, the fit's three launches in this stage's scratch (an earlier fit result of the caller stays
+ * valid), loo_stat_kernel.  No atomics.  The integer arrays, support, and which statistics are +inf are the host form's given
+ * the same solves; the doubles follow the device EM and the device fit.  Only the arrays the caller gave pointers for cross
+ * PCIe.  Synchronises on `stream` (NULL: the context's own).  SBGPU_ESHAPE: rule 1; SBGPU_EINVAL: a NULL argument, counts or
+ * weights that are not on the device, theta_without without without_off, a wrong without_off, a negative max_bytes.          */
+int sbgpu_em_loo_device(sbgpu_ctx_t *ctx, const sbgpu_plan_t *plan, const int32_t *d_count, const double *d_F, const int32_t *d_keep,
+                        const sbgpu_loo_params_t *params, void *stream, sbgpu_em_loo_t *out);
+/* The same right after a resident call or an sbgpu_front_stream_end made with sbgpu_bootstrap_keep on, from that record, as
+ * sbgpu_model_fit_device: nothing more is retained, the call's seven results are the same bits with and without it, and support,
+ * info, fit, table, assignment and coverage may be asked for in any order.                                               */
+int sbgpu_model_loo_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins, const int32_t *d_keep, const sbgpu_loo_params_t *params, void *stream,
+                           sbgpu_em_loo_t *out);
+/* The thresholds (csrc/loo_rules.h, csrc/loo_device.h; reasoned from LDS sizes, not tuned): out[0] the most kept isoforms of a
+ * locus whose isoforms are tested; [1] weights of one row tile of the expand kernel (its LDS), [2] the most rows of one tile: a
+ * locus of K kept isoforms is cut into tiles of min(out[2], out[1] / K) rows; [3] threads of a workgroup; [4] workgroups per CU
+ * a launch's grid is capped at; [5] the default scratch budget in bytes; [6] the most bins and [7] the most isoforms of a locus. */
+int sbgpu_em_loo_limits(int64_t out[8]);
+
 /* ---- the EM bootstrap: how far theta can be trusted -------------------------
  * The reference prints theta with no statement of its spread.  The bootstrap resamples every locus' fragments over its
  * bins, solves again, and reports mean and variance of theta over the replicates.

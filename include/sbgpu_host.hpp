@@ -910,6 +910,84 @@ class IsoformInfo {
    }
 };
 
+/* The drop-one isoform support (sbgpu_em_loo_device / sbgpu_model_loo_device, include/sbgpu.h): for every kept
+ * isoform of a locus of 2..64 kept isoforms, the likelihood-ratio statistic of the locus solved without it, the fragments only it
+ * explains and where its mass goes.  device(): for a batch (plan) or right after a resident call (bins); iso_off and keep
+ * ([n_iso] or null: everything kept) on the host size the packed theta_without.                                            */
+class IsoformSupport {
+ public:
+   std::vector<double> lr_stat, heir_gain, theta_refit;                 /* [n_iso] */
+   std::vector<int64_t> n_unique;                                       /* [n_iso] */
+   std::vector<int32_t> heir, status_without, iters_without, support;   /* [n_iso] */
+   std::vector<double> loglik_base;                                     /* [n_loci] */
+   std::vector<int32_t> loo_status, status_base, iters_base;            /* [n_loci] */
+   std::vector<double> theta_without;                                   /* [without_off[n_iso]] */
+   std::vector<int64_t> without_off;                                    /* [n_iso + 1] */
+   sbgpu_em_loo_t raw{}; /* the device arrays -- the context's, valid until its next quantify or support call; its host pointers
+                            are null after the call */
+
+   static IsoformSupport device(const Context &ctx, const sbgpu_plan_t *plan, const int64_t *iso_off, const int32_t *d_count, const double *d_F,
+                                const int32_t *d_keep = nullptr, const int32_t *keep = nullptr, int64_t max_bytes = 0, void *stream = nullptr)
+   {
+      int64_t info[8];
+      check(sbgpu_plan_info(plan, info), "sbgpu_plan_info");
+      IsoformSupport t;
+      t.prepare(info[0], info[2], iso_off, keep);
+      const sbgpu_loo_params_t par{max_bytes, 0};
+      check(sbgpu_em_loo_device(ctx.get(), plan, d_count, d_F, d_keep, &par, stream, &t.raw), "sbgpu_em_loo_device");
+      t.done();
+      return t;
+   }
+   static IsoformSupport device(const Context &ctx, const sbgpu_bins_t *bins, const int64_t *iso_off, const int32_t *d_keep = nullptr,
+                                const int32_t *keep = nullptr, int64_t max_bytes = 0, void *stream = nullptr)
+   {
+      int64_t info[8];
+      check(sbgpu_bins_info(bins, info), "sbgpu_bins_info");
+      IsoformSupport t;
+      t.prepare(info[0], info[1], iso_off, keep);
+      const sbgpu_loo_params_t par{max_bytes, 0};
+      check(sbgpu_model_loo_device(ctx.get(), bins, d_keep, &par, stream, &t.raw), "sbgpu_model_loo_device");
+      t.done();
+      return t;
+   }
+   /* 0.5 * erfc(sqrt(max(stat, 0) / 2)): the boundary mixture 1/2 chi2_0 + 1/2 chi2_1; 0 for +inf, 1 for a statistic <= 0 */
+   double p_value(int64_t i) const
+   {
+      const double x = lr_stat[(size_t)i];
+      return x == HUGE_VAL ? 0.0 : !(x > 0.0) ? 1.0 : 0.5 * std::erfc(std::sqrt(x / 2.0));
+   }
+
+   /* (public for a caller that fills raw through the host form's three calls) */
+   void prepare(int64_t n_loci, int64_t n_iso, const int64_t *iso_off, const int32_t *keep)
+   {
+      const size_t nl = (size_t)n_loci + 1, ni = (size_t)n_iso + 1; /* (one spare entry: data() of an empty vector may be null) */
+      lr_stat.assign(ni, 0.0), heir_gain.assign(ni, 0.0), theta_refit.assign(ni, 0.0), n_unique.assign(ni, 0);
+      heir.assign(ni, -1), status_without.assign(ni, -1), iters_without.assign(ni, -1), support.assign(ni, 0);
+      loglik_base.assign(nl, 0.0), loo_status.assign(nl, 0), status_base.assign(nl, -1), iters_base.assign(nl, -1);
+      raw = sbgpu_em_loo_t{};
+      without_off.clear(), theta_without.clear();
+      if (iso_off) {
+         without_off.assign(ni, 0);
+         check(sbgpu_em_loo_offsets(iso_off, keep, n_loci, without_off.data()), "sbgpu_em_loo_offsets");
+         theta_without.assign((size_t)without_off[(size_t)n_iso] + 1, 0.0);
+         raw.theta_without = theta_without.data(), raw.without_off = without_off.data();
+      }
+      raw.lr_stat = lr_stat.data(), raw.heir_gain = heir_gain.data(), raw.theta_refit = theta_refit.data(), raw.n_unique = n_unique.data();
+      raw.heir = heir.data(), raw.status_without = status_without.data(), raw.iters_without = iters_without.data(), raw.support = support.data();
+      raw.loglik_base = loglik_base.data(), raw.loo_status = loo_status.data(), raw.status_base = status_base.data(), raw.iters_base = iters_base.data();
+   }
+   void done()
+   {
+      raw.lr_stat = raw.heir_gain = raw.theta_refit = raw.loglik_base = raw.theta_without = nullptr;
+      raw.n_unique = nullptr, raw.without_off = nullptr;
+      raw.heir = raw.status_without = raw.iters_without = raw.support = raw.loo_status = raw.status_base = raw.iters_base = nullptr;
+      lr_stat.pop_back(), heir_gain.pop_back(), theta_refit.pop_back(), n_unique.pop_back();
+      heir.pop_back(), status_without.pop_back(), iters_without.pop_back(), support.pop_back();
+      loglik_base.pop_back(), loo_status.pop_back(), status_base.pop_back(), iters_base.pop_back();
+      if (!theta_without.empty()) theta_without.pop_back();
+   }
+};
+
 /* The bootstrap of the resident path (sbgpu_bootstrap_keep / sbgpu_abundance_bootstrap_device, include/sbgpu.h): FPKM and TPM
  * mean, variance and percentile interval over resampled bin counts, with the replicates in which the expression filter kept
  * each isoform.  keep(): before the resident call; device(): right after it, on that call's handle.  interval_ranks(): the two

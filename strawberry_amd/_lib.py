@@ -49,6 +49,8 @@ SYMBOLS = [
     "sbgpu_isoform_coverage_host", "sbgpu_isoform_coverage_device", "sbgpu_isoform_coverage_limits",
     "sbgpu_em_fit_host", "sbgpu_em_fit_device", "sbgpu_model_fit_device", "sbgpu_em_fit_limits",
     "sbgpu_em_info_host", "sbgpu_em_info_device", "sbgpu_model_info_device", "sbgpu_em_info_limits", "sbgpu_em_info_cov_offsets",
+    "sbgpu_em_loo_offsets", "sbgpu_em_loo_shapes_host", "sbgpu_em_loo_expand_host", "sbgpu_em_loo_stat_host", "sbgpu_em_loo_device",
+    "sbgpu_model_loo_device", "sbgpu_em_loo_limits",
 ]
 
 
@@ -173,6 +175,16 @@ class sbgpu_em_fit_t(C.Structure):
 class sbgpu_em_info_t(C.Structure):
     _NAMES = ("se", "partner_corr", "ident", "alias_of", "partner", "min_pivot", "rank", "n_free", "info_status", "cov", "cov_off")
     _fields_ = [(n, C.c_void_p) for n in _NAMES] + [("d_" + n, C.c_void_p) for n in _NAMES]
+
+
+class sbgpu_em_loo_t(C.Structure):
+    _NAMES = ("lr_stat", "heir_gain", "theta_refit", "n_unique", "heir", "status_without", "iters_without", "support", "loglik_base",
+              "loo_status", "status_base", "iters_base", "theta_without", "without_off")
+    _fields_ = [(n, C.c_void_p) for n in _NAMES] + [("d_" + n, C.c_void_p) for n in _NAMES] + [("sub_count", C.c_void_p), ("sub_F", C.c_void_p)]
+
+
+class sbgpu_loo_params_t(C.Structure):
+    _fields_ = [("max_bytes", C.c_int64), ("reserved", C.c_int64)]
 
 
 class sbgpu_bootstrap_params_t(C.Structure):
@@ -370,6 +382,13 @@ def load():
     L.sbgpu_model_info_device.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(sbgpu_em_info_t)]
     L.sbgpu_em_info_limits.argtypes = [C.POINTER(C.c_int64)]
     L.sbgpu_em_info_cov_offsets.argtypes = [vp, C.c_int64, vp]
+    L.sbgpu_em_loo_offsets.argtypes = [vp, vp, C.c_int64, vp]
+    L.sbgpu_em_loo_shapes_host.argtypes = [C.c_int64, vp, vp, vp, C.POINTER(C.c_int64), vp, vp, vp, vp, vp, vp]
+    L.sbgpu_em_loo_expand_host.argtypes = [C.POINTER(sbgpu_batch_t), vp, vp, vp]
+    L.sbgpu_em_loo_stat_host.argtypes = [C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(sbgpu_em_loo_t)]
+    L.sbgpu_em_loo_device.argtypes = [vp, vp, vp, vp, vp, C.POINTER(sbgpu_loo_params_t), vp, C.POINTER(sbgpu_em_loo_t)]
+    L.sbgpu_model_loo_device.argtypes = [vp, vp, vp, C.POINTER(sbgpu_loo_params_t), vp, C.POINTER(sbgpu_em_loo_t)]
+    L.sbgpu_em_loo_limits.argtypes = [C.POINTER(C.c_int64)]
     L.sbgpu_bootstrap_counts_host.argtypes = [C.c_int64, vp, vp, vp, C.c_uint64, C.c_int32, vp]
     L.sbgpu_bootstrap_counts_device.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp]
     L.sbgpu_em_bootstrap_device.argtypes = [vp, vp, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp, vp, vp, vp, vp, vp]

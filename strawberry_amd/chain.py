@@ -234,7 +234,8 @@ class ChainQuantifier:
         repeatedly).
         keep_bootstrap=True (resident only): likewise for the bootstrap (sbgpu_bootstrap_keep); abundance_bootstrap() runs it on the
         last step's handle, model_fit() the model fit (fit.model_fit_device) and isoform_information() the isoform information
-        (info.model_info_device), which work from the same retention."""
+        (info.model_info_device) and isoform_support() the drop-one support (support.model_loo_device), which work from the same
+        retention."""
         import torch
         self.torch, self.ctx = torch, ctx
         self.dev = torch.device("cuda", ctx.device)
@@ -393,6 +394,16 @@ class ChainQuantifier:
             raise _lib.SbgpuError("isoform_information: no step has run with keep_bootstrap=True")
         return info.model_info_device(self.ctx, self.context_handle, int(self._out.d_theta) if d_theta is None else d_theta,
                                       int(self._out.d_keep), int(self._out.d_status), want=want)
+
+    def isoform_support(self, max_bytes=0, want=None):
+        """The drop-one isoform support of the last step (keep_bootstrap=True: it works from the bootstrap's retention):
+        support.model_loo_device on its handle with the step's keep -> a support.IsoformSupport.  max_bytes: the scratch budget
+        of one chunk of sub-problems (0: 1 GiB); want: the arrays to bring to the host (None: all)."""
+        from . import support
+        if self.context_handle is None or not self.keep_bootstrap:
+            raise _lib.SbgpuError("isoform_support: no step has run with keep_bootstrap=True")
+        return support.model_loo_device(self.ctx, self.context_handle, int(self._out.d_keep), keep=self.keep[:self.n_iso], max_bytes=max_bytes,
+                                        want=want)
 
     def locus_abundance(self):
         """Abundances per locus of the last resident step (bootstrap.locus_abundance_device on the device arrays the call left:

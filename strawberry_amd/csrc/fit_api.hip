@@ -22,31 +22,32 @@ void fit_clear_device(sbgpu_em_fit_t *out)
    out->d_dof = nullptr, out->d_worst_bin = nullptr;
 }
 
-// the two entry points' common part: `ps` says the shapes, everything else is device memory
-int fit_run(const std::string &who, sbgpu_ctx_t *c, const sb::PlanShape &ps, const int32_t *d_count, const double *d_F, const double *d_theta,
-            const int32_t *d_keep, const int32_t *d_status, void *stream, sbgpu_em_fit_t *out)
+} // namespace
+
+namespace sb {
+// The loci by form (fit_device.h): a wave each, or a workgroup each; and the arena that follows from the two lists
+int fit_plan(const std::string &who, const PlanShape &ps, bool own_keep, bool own_status, FitPlan *out)
 {
-   const int64_t nl = ps.n_loci, n_bins = ps.n_rows, n_iso = ps.n_iso;
-   // ---- the loci by form (fit_device.h): a wave each, or a workgroup each
-   std::vector<int32_t> small, large;
-   bool any_weight = false;
-   for (int64_t l = 0; l < nl; ++l) {
+   out->small.clear(), out->large.clear(), out->any_weight = false;
+   for (int64_t l = 0; l < ps.n_loci; ++l) {
       const int64_t nb = ps.row_off[l + 1] - ps.row_off[l], niso = ps.iso_off[l + 1] - ps.iso_off[l];
-      if (nb > sb::kFitMaxBins) return api_fail(SBGPU_ESHAPE, who + ": a locus of more than 5632 bins");
-      if (niso > 32 * (int64_t)sb::kFitMaxWords) return api_fail(SBGPU_ESHAPE, who + ": a locus of more than 4096 isoforms");
-      any_weight |= nb * niso > 0;
-      (sb::fit_wave_form(nb, niso) ? small : large).push_back((int32_t)l);
+      if (nb > kFitMaxBins) return api_fail(SBGPU_ESHAPE, who + ": a locus of more than 5632 bins");
+      if (niso > 32 * (int64_t)kFitMaxWords) return api_fail(SBGPU_ESHAPE, who + ": a locus of more than 4096 isoforms");
+      out->any_weight |= nb * niso > 0;
+      (fit_wave_form(nb, niso) ? out->small : out->large).push_back((int32_t)l);
    }
-   if (n_bins && !d_count) return api_fail(SBGPU_EINVAL, who + ": the counts are not on the device");
-   if (any_weight && !d_F) return api_fail(SBGPU_EINVAL, who + ": the weights are not on the device");
-   hipStream_t s = stream ? (hipStream_t)stream : sb::ctx_stream(c);
-   SB_STAGE_TRY(hipSetDevice(sb::ctx_device(c)));
-   // ---- the arena (stage_host.h: fit_layout): keep / status have room in it where the caller gave none
-   const sb::FitLayout L = sb::fit_layout(nl, n_bins, n_iso, small.size(), large.size(), !d_keep, !d_status);
-   char *d = nullptr;
-   if (hipError_t e = sb::ctx_scratch(c, sb::kScratchFit, L.bytes, &d); e != hipSuccess)
-      return sb::api_fail_hip(e, "hipMalloc");
-   sb::HostBlock host(L.upload_bytes);
+   out->L = fit_layout(ps.n_loci, ps.n_rows, ps.n_iso, out->small.size(), out->large.size(), own_keep, own_status);
+   return SBGPU_OK;
+}
+
+// The fit's launches on `s`, in arena `d` (p.L.bytes; any memory of the caller's): the lists' upload through `host`
+// (p.L.upload_bytes, the caller's: it lives until the caller has synchronised), the column pass, the two forms.
+int fit_launch(sbgpu_ctx_t *c, const PlanShape &ps, const FitPlan &p, HostBlock &host, char *d, const int32_t *d_count, const double *d_F,
+               const double *d_theta, const int32_t *d_keep, const int32_t *d_status, hipStream_t s)
+{
+   const int64_t nl = ps.n_loci, n_iso = ps.n_iso;
+   const FitLayout &L = p.L;
+   const std::vector<int32_t> &small = p.small, &large = p.large;
    host.put(L.small, small.data(), small.size()), host.put(L.large, large.data(), large.size());
    SB_STAGE_TRY(host.upload(d, s));
    // no filter given: every isoform is kept (any non-zero word); no status given: every locus started (SBGPU_EM_OK is 0)
@@ -70,7 +71,6 @@ int fit_run(const std::string &who, sbgpu_ctx_t *c, const sb::PlanShape &ps, con
    a.dof = sb::arena_at<int32_t>(d, L.dof), a.worst_bin = sb::arena_at<int32_t>(d, L.worst);
    const int64_t cap = (int64_t)sb::ctx_cu_count(c) * sb::kFitGridPerCu;
    // (sbgpu_set_timing: the three launches as stages of their own, for tools/bench_fit.py)
-   sb::ctx_stage_reset(c);
    sb::ctx_stage_begin(c, "fit_column", s);
    if (nl) SB_STAGE_TRY(sb::asg_launch_column_pass(col, sb::stage_grid(nl, cap), s));
    sb::ctx_stage_end(c, s);
@@ -89,6 +89,31 @@ int fit_run(const std::string &who, sbgpu_ctx_t *c, const sb::PlanShape &ps, con
       SB_STAGE_TRY(hipGetLastError());
    }
    sb::ctx_stage_end(c, s);
+   return SBGPU_OK;
+}
+} // namespace sb
+
+namespace {
+
+// the two entry points' common part: `ps` says the shapes, everything else is device memory
+int fit_run(const std::string &who, sbgpu_ctx_t *c, const sb::PlanShape &ps, const int32_t *d_count, const double *d_F, const double *d_theta,
+            const int32_t *d_keep, const int32_t *d_status, void *stream, sbgpu_em_fit_t *out)
+{
+   const int64_t nl = ps.n_loci, n_bins = ps.n_rows, n_iso = ps.n_iso;
+   sb::FitPlan p;
+   if (const int rc = sb::fit_plan(who, ps, !d_keep, !d_status, &p); rc != SBGPU_OK) return rc;
+   if (n_bins && !d_count) return api_fail(SBGPU_EINVAL, who + ": the counts are not on the device");
+   if (p.any_weight && !d_F) return api_fail(SBGPU_EINVAL, who + ": the weights are not on the device");
+   hipStream_t s = stream ? (hipStream_t)stream : sb::ctx_stream(c);
+   SB_STAGE_TRY(hipSetDevice(sb::ctx_device(c)));
+   // ---- the arena (stage_host.h: fit_layout): keep / status have room in it where the caller gave none
+   const sb::FitLayout &L = p.L;
+   char *d = nullptr;
+   if (hipError_t e = sb::ctx_scratch(c, sb::kScratchFit, L.bytes, &d); e != hipSuccess)
+      return sb::api_fail_hip(e, "hipMalloc");
+   sb::HostBlock host(L.upload_bytes);
+   sb::ctx_stage_reset(c);
+   if (const int rc = sb::fit_launch(c, ps, p, host, d, d_count, d_F, d_theta, d_keep, d_status, s); rc != SBGPU_OK) return rc;
    // ---- results: what the caller asked for
    SB_STAGE_TRY(sb::copy_back(out->expected, d, L.exp, n_bins, s));
    SB_STAGE_TRY(sb::copy_back(out->resid, d, L.res, n_bins, s));
@@ -102,10 +127,10 @@ int fit_run(const std::string &who, sbgpu_ctx_t *c, const sb::PlanShape &ps, con
    SB_STAGE_TRY(sb::copy_back(out->dof, d, L.dof, nl, s));
    SB_STAGE_TRY(sb::copy_back(out->worst_bin, d, L.worst, nl, s));
    SB_STAGE_TRY(hipStreamSynchronize(s));
-   out->d_expected = a.expected, out->d_resid = a.resid, out->d_score = a.score;
-   out->d_loglik = a.loglik, out->d_deviance = a.deviance, out->d_pearson = a.pearson;
+   out->d_expected = sb::arena_at<double>(d, L.exp), out->d_resid = sb::arena_at<double>(d, L.res), out->d_score = sb::arena_at<double>(d, L.score);
+   out->d_loglik = sb::arena_at<double>(d, L.ll), out->d_deviance = sb::arena_at<double>(d, L.dev), out->d_pearson = sb::arena_at<double>(d, L.pear);
    out->d_n_live = sb::arena_at<int64_t>(d, L.nlive), out->d_n_dropped = sb::arena_at<int64_t>(d, L.ndrop), out->d_n_impossible = sb::arena_at<int64_t>(d, L.nimp);
-   out->d_dof = a.dof, out->d_worst_bin = a.worst_bin;
+   out->d_dof = sb::arena_at<int32_t>(d, L.dof), out->d_worst_bin = sb::arena_at<int32_t>(d, L.worst);
    return SBGPU_OK;
 }
 

@@ -100,6 +100,19 @@ static inline hipError_t copy_back(T *host, const char *d, size_t at, int64_t n,
    return host && n ? hipMemcpyAsync(host, d + at, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, s) : hipSuccess;
 }
 
+// fit_api.hip: the model fit's launches for a stage that runs them in memory of its own (loo_api.hip), as
+// asg_launch_column_pass serves the stages behind the assignment.  fit_plan: the loci by form and the arena's layout
+// (SBGPU_ESHAPE for a locus beyond the fit's limits); fit_launch: the lists' upload through `host` (p.L.upload_bytes, alive until
+// the caller has synchronised `s`), the column pass and the two forms, in arena `d` (p.L.bytes), results at p.L's offsets.
+struct FitPlan {
+   std::vector<int32_t> small, large;
+   bool any_weight = false;
+   FitLayout L;
+};
+int fit_plan(const std::string &who, const PlanShape &ps, bool own_keep, bool own_status, FitPlan *out);
+int fit_launch(sbgpu_ctx_t *c, const PlanShape &ps, const FitPlan &p, HostBlock &host, char *d, const int32_t *d_count, const double *d_F,
+               const double *d_theta, const int32_t *d_keep, const int32_t *d_status, hipStream_t s);
+
 // The grid of a kernel that strides over n units of work: min(n, cap), at least one workgroup
 static inline unsigned stage_grid(int64_t n, int64_t cap) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(n, cap)); }
 

@@ -167,6 +167,50 @@ inline InfoLayout info_layout(int64_t n_loci, int64_t n_bins, int64_t n_iso, int
    return L;
 }
 
+// The isoform support: the results of the whole batch and what the host makes of its shapes, then -- behind
+// `chunk` -- the working set of one chunk of sub-problems, which every chunk of a call reuses.
+struct LooLayout {
+   size_t lstat, woff, rank, first, koff, kcol, upload_bytes; // made on the host: statuses, packed offsets, kept ranks and lists
+   size_t lr, hgain, refit, nuniq, heir, stw, itw, supp;      // per isoform
+   size_t llb, stb, itb;                                      // per locus
+   size_t wo, chunk, bytes;
+};
+inline LooLayout loo_layout(int64_t n_loci, int64_t n_iso, int64_t n_kept, int64_t n_without, size_t chunk_bytes)
+{
+   const size_t nl1 = (size_t)n_loci + 1, ni1 = (size_t)n_iso + 1;
+   Arena a;
+   LooLayout L;
+   L.lstat = a.take(nl1 * 4), L.woff = a.take(ni1 * 8), L.rank = a.take(ni1 * 4), L.first = a.take(nl1 * 8), L.koff = a.take(nl1 * 8);
+   L.kcol = a.take(at_least_1(n_kept) * 4);
+   L.upload_bytes = a.size;
+   L.lr = a.take(ni1 * 8), L.hgain = a.take(ni1 * 8), L.refit = a.take(ni1 * 8), L.nuniq = a.take(ni1 * 8);
+   L.heir = a.take(ni1 * 4), L.stw = a.take(ni1 * 4), L.itw = a.take(ni1 * 4), L.supp = a.take(ni1 * 4);
+   L.llb = a.take(nl1 * 8), L.stb = a.take(nl1 * 4), L.itb = a.take(nl1 * 4);
+   L.wo = a.take(at_least_1(n_without) * 8);
+   L.chunk = a.take(chunk_bytes);
+   L.bytes = a.size;
+   return L;
+}
+struct LooTile {
+   int32_t locus, row0, rows, pad; // rows [row0, row0 + rows) of the locus
+};
+struct LooChunkLayout {
+   size_t tiles, upload_bytes;
+   size_t count, F, theta, status, iters, fit, bytes;
+};
+inline LooChunkLayout loo_chunk_layout(int64_t n_tiles, int64_t n_sub, int64_t sub_rows, int64_t sub_iso, int64_t sub_elem, size_t fit_bytes)
+{
+   Arena a;
+   LooChunkLayout L;
+   L.tiles = a.take(at_least_1(n_tiles) * sizeof(LooTile));
+   L.upload_bytes = a.size;
+   L.count = a.take(at_least_1(sub_rows) * 4), L.F = a.take(at_least_1(sub_elem) * 8), L.theta = a.take(at_least_1(sub_iso) * 8);
+   L.status = a.take(at_least_1(n_sub) * 4), L.iters = a.take(at_least_1(n_sub) * 4);
+   L.fit = a.take(fit_bytes);
+   L.bytes = a.size;
+   return L;
+}
+
 // ---- the host forms' shared loops.  Every sum runs in the order the kernels' do: a column's over the live bins, ascending.
 
 // The kept words of one locus into K [(niso + 31) / 32] -> their number.  keep_of_locus null: no filter was given and every

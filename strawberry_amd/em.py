@@ -276,6 +276,16 @@ class EmBatchSolver:
         return info.em_info_device(self.ctx, self.plan, self.d_count, self.d_F, self.d_theta if d_theta is None else d_theta, d_keep,
                                    self.d_status if d_status is None else d_status, stream=self._stream(), want=want)
 
+    def run_loo(self, d_keep=None, max_bytes=0, want=None, with_sub_batch=False):
+        """The drop-one isoform support of the batch (sbgpu_em_loo_device; support.py): every kept isoform of a locus of 2..64
+        kept isoforms is dropped in turn, the locus solved again and the likelihoods compared.  d_keep: an int32 device tensor
+        (None: every isoform kept; the epilogue's is self.d_keep); max_bytes: the scratch budget of one chunk of sub-problems
+        (0: 1 GiB).  The base model is solved inside the call: no run_em is needed before.  Synchronises on torch's current
+        stream -> a support.IsoformSupport of host arrays (want: which)."""
+        from . import support
+        return support.em_loo_device(self.ctx, self.plan, self.d_count, self.d_F, d_keep, max_bytes=max_bytes, stream=self._stream(), want=want,
+                                     with_sub_batch=with_sub_batch)
+
     def bootstrap_counts(self, n_rep, seed, rep_first=0, locus_id=None):
         """The replicates' counts alone (sbgpu_bootstrap_counts_device) -> int32 device tensor [n_rep, total rows]"""
         n = self.batch.n_loci

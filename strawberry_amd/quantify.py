@@ -228,7 +228,8 @@ class BinsHandle:
 
 def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=False, ctx=None, device=0, comm=None,
                       min_isoform_frac=0.0, filter_by_expression=True, effective_len_norm=False, with_context=False, bootstrap=None,
-                      keep_bootstrap=False, keep_handle=False, with_assignment=False, with_coverage=False, with_fit=False, with_info=False):
+                      keep_bootstrap=False, keep_handle=False, with_assignment=False, with_coverage=False, with_fit=False, with_info=False,
+                      with_support=False):
     """sbgpu_quantify_resident on host hits brought to the device first (torch owns the copies): pass 1 (insert=None: the
     empirical insert-size law, built on the device), bins, weights, EM, FPKM / Frac / keep, the FPKM all-reduce over `comm`
     (dist.AbiComm / dist.HostComm; None: a world of one), TPM.  The hits must come grouped by locus.
@@ -245,6 +246,8 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     (fit.model_fit_device) -> "fit": a fit.ModelFit; "bins" as with_context.
     with_info: the bootstrap's retention, and the isoform information under the call's theta, keep and status, built on the device
     (info.model_info_device) -> "isoform_info": an info.IsoformInfo ("info" is the handle's sizes); "bins" as with_context.
+    with_support: the bootstrap's retention, and the drop-one isoform support under the call's keep, built on the device
+    (support.model_loo_device) -> "isoform_support": a support.IsoformSupport; "bins" as with_context.
     keep_bootstrap: retention for the bootstrap on, without running it (for a caller that runs it several times).
     keep_handle: the handle is not exported but returned as "handle", a BinsHandle that owns it -- it is destroyed by its close(),
     as a context manager, or when the object is collected; the caller runs bootstrap.abundance_bootstrap_device /
@@ -281,7 +284,7 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     retain = bool(with_context) or bool(with_assignment) or bool(with_coverage)
     if retain:
         _lib.check(L.sbgpu_context_table_keep(ctx.h, 1), "sbgpu_context_table_keep")
-    keep_bootstrap = bool(keep_bootstrap) or bootstrap is not None or bool(with_fit) or bool(with_info)
+    keep_bootstrap = bool(keep_bootstrap) or bootstrap is not None or bool(with_fit) or bool(with_info) or bool(with_support)
     if keep_bootstrap:
         _lib.check(L.sbgpu_bootstrap_keep(ctx.h, 1), "sbgpu_bootstrap_keep")
     try:
@@ -300,9 +303,9 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     owner = BinsHandle(L, handle) if keep_handle else None     # (from here on an exception frees the handle with the object)
     info = (C.c_int64 * 8)()
     _lib.check(L.sbgpu_bins_info(handle, info), "sbgpu_bins_info")
-    table = bins = boot = assignment = cov = model_fit = iso_info = None
-    if retain or bootstrap is not None or with_fit or with_info:
-        from . import assign, context, coverage, fit
+    table = bins = boot = assignment = cov = model_fit = iso_info = iso_support = None
+    if retain or bootstrap is not None or with_fit or with_info or with_support:
+        from . import assign, context, coverage, fit, support
         from . import info as isoform_info
         from .bootstrap import abundance_bootstrap_device
         from .exonbin import LocusBins
@@ -319,6 +322,8 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
                 model_fit = fit.model_fit_device(ctx, handle, int(out.d_theta), int(out.d_keep), int(out.d_status))
             if with_info:
                 iso_info = isoform_info.model_info_device(ctx, handle, int(out.d_theta), int(out.d_keep), int(out.d_status))
+            if with_support:
+                iso_support = support.model_loo_device(ctx, handle, int(out.d_keep), keep=res["keep"][:n_iso])
         except Exception:
             if owner is None:
                 L.sbgpu_bins_destroy(handle)
@@ -345,6 +350,8 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
         r.update(fit=model_fit, bins=bins)
     if with_info:
         r.update(isoform_info=iso_info, bins=bins)
+    if with_support:
+        r.update(isoform_support=iso_support, bins=bins)
     if keep_handle:
         r["handle"] = owner
     return r
