@@ -1580,6 +1580,68 @@ int sbgpu_format_context_row_seq(char *buf, int cap, const char *sample, int32_t
                                  const uint32_t *seg_left, const uint32_t *seg_right, uint32_t path_count,
                                  double gc, double entropy, uint32_t flags);
 
+/* ---- transcript-body coverage profile: posterior-weighted bases by 5' -> 3' position ---------------------------
+ * Where along an isoform its fragments lie, at a fixed number of positional bins: the gene-body curve of a sample, and per
+ * isoform how even its coverage is.  The rule (csrc/body_rules.h, shared by both forms, compiled under -ffp-contract=off).  Who is
+ * assigned, its candidates J(h), the posterior p(j|h) and the weight w(h,j) = (double)m_h * p(j|h) ARE the isoform-resolved
+ * coverage's above, under the same theta, keep, status, weights and masses.
+ *   - BINS    P = n_pos, 1 <= P <= SBGPU_BODY_MAX_POS; anything else: SBGPU_EINVAL.
+ *   - LENGTH  L_j = the sum of R_e - L_e + 1 over isoform j's exons (exon_off, closed coordinates), an int64.
+ *   - COORDINATE  a base at genomic g inside exon e of j has t = pre_e + (g - L_e), pre_e the total length of j's exons before e.
+ *   - BIN OF A BASE  q(t) = floor(t * P / L_j) in exact 64-bit integer arithmetic: bin q holds t in [ceil(q L_j / P),
+ *     ceil((q + 1) L_j / P) - 1]; where L_j < P its width may be 0.
+ *   - ORIENTATION  iso_strand[j] (a HOST array; NULL: all 0) is coded as the clusters' strands: 0 unknown, 1 '+', 2 '-'; a value
+ *     above 2: SBGPU_EINVAL.  The reported bin is q for 0 and 1, P - 1 - q for 2: orientation changes the index only.
+ *   - TERM    n(h,j,p), an integer: the bases of hit h's S_MATCH features that lie inside j's exons and fall in reported bin p
+ *     (S_GAP and S_INTRON features add nothing).  body_bases[j * P + p] = sum over the assigned hits h with j in J(h) of
+ *     w(h,j) * (double)n(h,j,p): one product per (hit, candidate, bin) with n != 0.
+ *   - PER ISOFORM, functions of the isoform's finished bins' bits, taken in ascending p:
+ *       body_total[j]   the ascending sum;
+ *       body_center[j]  (sum_p bases_p * (double)(2p + 1)) / ((double)(2P) * total): 0.5 for a uniform profile, above 0.5 towards
+ *                       the 3' end of a stranded isoform;
+ *       body_cv[j]      over the bins of non-zero width wd_p: depth_p = bases_p / (double)wd_p, m their mean,
+ *                       sqrt(mean of (depth_p - m)^2) / m;
+ *       body_center[j] = body_cv[j] = -1.0 exactly where body_total[j] is exactly 0.0.
+ *   - PER SAMPLE  the length class of j is c = (L_j >= 1000) + (L_j >= 2000) + (L_j >= 4000).  For every isoform with total > 0:
+ *     class_profile[c * P + p] += bases_p / total and class_n[c] += 1 -- the sample's gene-body curve, every expressed isoform
+ *     with the same weight.  The host form adds in ascending j.
+ * An isoform that is not kept, and a locus whose status is SBGPU_EM_INIT_EMPTY, hold zeros and -1.0 and are in no class.
+ * The struct: host arrays to fill (any may be NULL) and, on return -- device form only -- the device arrays of all six (the
+ * context's memory: valid until its next quantify or body-profile call).                                                    */
+#define SBGPU_BODY_MAX_POS 100
+typedef struct {
+   double *body_bases;     /* in: [n_iso * n_pos]                                           */
+   double *body_total;     /* in: [n_iso]                                                   */
+   double *body_center;    /* in: [n_iso]                                                   */
+   double *body_cv;        /* in: [n_iso]                                                   */
+   double *class_profile;  /* in: [4 * n_pos]                                               */
+   int64_t *class_n;       /* in: [4]                                                       */
+   const double *d_body_bases, *d_body_total, *d_body_center, *d_body_cv, *d_class_profile; /* out: device form only */
+   const int64_t *d_class_n;                                                                 /* out: device form only */
+} sbgpu_body_profile_t;
+/* Host form, the plain statement of the rule: hits in index order, inside a hit the candidates in ascending j.  Every argument
+ * up to hit_mass is sbgpu_isoform_coverage_host's, with its NULL conventions and its refusals.                             */
+int sbgpu_body_profile_host(const sbgpu_bins_t *bins, const sbgpu_annotation_t *annot, const sbgpu_hits_t *hits,
+                            const uint32_t *compat, int32_t compat_words, const double *F, const double *theta,
+                            const int32_t *keep, const int32_t *status, const float *hit_mass, const uint8_t *iso_strand,
+                            int32_t n_pos, sbgpu_body_profile_t *out);
+/* Device form (csrc/body_device.h): valid exactly where sbgpu_isoform_coverage_device is -- same handles, same refusals, the
+ * same annot / d_hits / d_theta / d_hit_mass -- and nothing more is retained by a resident call.  The assignment's column pass,
+ * one pass over the hits, one over the isoforms.  The sums are added in another order than the host form's: equal within the
+ * rounding of a sum of non-negative terms, exactly where every term is an integer; body_total, body_center and body_cv are the
+ * rule's functions of the device's own body_bases; class_n is exact.  The results live in a scratch slot of their own: table,
+ * assignment, coverage, fit, information, support and profile may be asked for in any order, repeatedly.  Only the arrays the
+ * caller gave pointers for cross PCIe.  Synchronises on `stream` (NULL: the context's own).  Loci of more than 4096 isoforms or
+ * more than 5632 bins: SBGPU_ESHAPE.                                                                                       */
+int sbgpu_body_profile_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins, const sbgpu_annotation_t *annot, const sbgpu_hits_t *d_hits,
+                              const double *d_theta, const float *d_hit_mass, const uint8_t *iso_strand, int32_t n_pos, void *stream,
+                              sbgpu_body_profile_t *out);
+/* The device form's thresholds (csrc/body_device.h; reasoned from LDS sizes, not tuned): out[0] hits of one work item; a locus
+ * keeps its tables and sums in LDS where it has at most [1] annotated exons, at most [2] isoforms and niso * n_pos is at most
+ * [3]; its sums are kept in [5] copies where it has at most [4] isoforms and niso * n_pos * [5] is at most [3]; [6] the most
+ * bins and [7] the most isoforms of one locus.                                                                              */
+int sbgpu_body_profile_limits(int64_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif

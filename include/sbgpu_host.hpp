@@ -750,6 +750,70 @@ class IsoformCoverage {
    void done() { raw.exon_bases = raw.junction_mass = raw.iso_bases = raw.unexplained_bases = nullptr; }
 };
 
+/* Transcript-body coverage profile (sbgpu_body_profile_*, include/sbgpu.h states the rule): per isoform the posterior-weighted
+ * sequenced bases in n_pos positional bins from 5' to 3' (iso_strand: 0 / 1 / 2 per isoform, a HOST array; nullptr: all 0), their
+ * total, centre and coefficient of variation; per length class the sum of the expressed isoforms' profiles and their number.
+ * host() / device(): under IsoformCoverage's conditions, with its arguments.  class_curve(c): class_profile over class_n.    */
+class BodyProfile {
+ public:
+   int32_t n_pos = 0;
+   std::vector<double> body_bases;                          /* [n_iso * n_pos] */
+   std::vector<double> body_total, body_center, body_cv;    /* [n_iso] */
+   std::vector<double> class_profile;                       /* [4 * n_pos] */
+   std::vector<int64_t> class_n;                            /* [4] */
+   sbgpu_body_profile_t raw{};  /* device(): the device arrays -- the context's, valid until its next quantify or body-profile call;
+                                   its host pointers are null after the call: the vectors above are the results, in a copy too */
+
+   static BodyProfile host(const sbgpu_bins_t *bins, const sbgpu_annotation_t &annot, const sbgpu_hits_t &hits, const uint32_t *compat,
+                           int32_t compat_words, const double *F, const double *theta, const int32_t *keep, const int32_t *status,
+                           const float *hit_mass, const uint8_t *iso_strand = nullptr, int32_t n_pos = 20)
+   {
+      BodyProfile t;
+      t.prepare(bins, n_pos);
+      check(sbgpu_body_profile_host(bins, &annot, &hits, compat, compat_words, F, theta, keep, status, hit_mass, iso_strand, n_pos, &t.raw),
+            "sbgpu_body_profile_host");
+      t.done();
+      return t;
+   }
+   static BodyProfile device(const Context &ctx, const sbgpu_bins_t *bins, const sbgpu_annotation_t &annot, const sbgpu_hits_t &d_hits,
+                             const double *d_theta, const float *d_hit_mass = nullptr, const uint8_t *iso_strand = nullptr, int32_t n_pos = 20,
+                             void *stream = nullptr)
+   {
+      BodyProfile t;
+      t.prepare(bins, n_pos);
+      check(sbgpu_body_profile_device(ctx.get(), bins, &annot, &d_hits, d_theta, d_hit_mass, iso_strand, n_pos, stream, &t.raw),
+            "sbgpu_body_profile_device");
+      t.done();
+      return t;
+   }
+   std::vector<double> class_curve(int c) const
+   {
+      std::vector<double> d((size_t)n_pos, 0.0);
+      if (class_n[(size_t)c])
+         for (int p = 0; p < n_pos; ++p) d[(size_t)p] = class_profile[(size_t)(c * n_pos + p)] / (double)class_n[(size_t)c];
+      return d;
+   }
+
+ private:
+   void prepare(const sbgpu_bins_t *bins, int32_t P)
+   {
+      int64_t info[8];
+      check(sbgpu_bins_info(bins, info), "sbgpu_bins_info");
+      n_pos = P;
+      const size_t n_iso = (size_t)info[1], p = (size_t)(P < 1 ? 1 : P > SBGPU_BODY_MAX_POS ? SBGPU_BODY_MAX_POS : P);
+      body_bases.assign(n_iso * p, 0.0), body_total.assign(n_iso, 0.0), body_center.assign(n_iso, 0.0), body_cv.assign(n_iso, 0.0);
+      class_profile.assign(4 * p, 0.0), class_n.assign(4, 0);
+      raw = sbgpu_body_profile_t{};
+      raw.body_bases = body_bases.data(), raw.body_total = body_total.data(), raw.body_center = body_center.data(), raw.body_cv = body_cv.data();
+      raw.class_profile = class_profile.data(), raw.class_n = class_n.data();
+   }
+   void done()
+   {
+      raw.body_bases = raw.body_total = raw.body_center = raw.body_cv = raw.class_profile = nullptr;
+      raw.class_n = nullptr;
+   }
+};
+
 /* The model fit (sbgpu_em_fit_* / sbgpu_model_fit_device, include/sbgpu.h states the rule): expected counts and Pearson residuals
  * per bin, the EM's score per isoform, likelihood, deviance, Pearson statistic, fragment counts, degrees of freedom and the worst
  * bin per locus.  host(): any batch with theta (keep / status: nullptr = everything kept / every locus started); no GPU.

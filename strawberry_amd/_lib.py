@@ -51,6 +51,7 @@ SYMBOLS = [
     "sbgpu_em_info_host", "sbgpu_em_info_device", "sbgpu_model_info_device", "sbgpu_em_info_limits", "sbgpu_em_info_cov_offsets",
     "sbgpu_em_loo_offsets", "sbgpu_em_loo_shapes_host", "sbgpu_em_loo_expand_host", "sbgpu_em_loo_stat_host", "sbgpu_em_loo_device",
     "sbgpu_model_loo_device", "sbgpu_em_loo_limits",
+    "sbgpu_body_profile_host", "sbgpu_body_profile_device", "sbgpu_body_profile_limits",
 ]
 
 
@@ -164,6 +165,11 @@ class sbgpu_fragment_assign_t(C.Structure):
 
 class sbgpu_isoform_coverage_t(C.Structure):
     _NAMES = ("exon_bases", "junction_mass", "iso_bases", "unexplained_bases")
+    _fields_ = [(n, C.c_void_p) for n in _NAMES] + [("d_" + n, C.c_void_p) for n in _NAMES]
+
+
+class sbgpu_body_profile_t(C.Structure):
+    _NAMES = ("body_bases", "body_total", "body_center", "body_cv", "class_profile", "class_n")
     _fields_ = [(n, C.c_void_p) for n in _NAMES] + [("d_" + n, C.c_void_p) for n in _NAMES]
 
 
@@ -389,6 +395,11 @@ def load():
     L.sbgpu_em_loo_device.argtypes = [vp, vp, vp, vp, vp, C.POINTER(sbgpu_loo_params_t), vp, C.POINTER(sbgpu_em_loo_t)]
     L.sbgpu_model_loo_device.argtypes = [vp, vp, vp, C.POINTER(sbgpu_loo_params_t), vp, C.POINTER(sbgpu_em_loo_t)]
     L.sbgpu_em_loo_limits.argtypes = [C.POINTER(C.c_int64)]
+    L.sbgpu_body_profile_host.argtypes = [vp, C.POINTER(sbgpu_annotation_t), C.POINTER(sbgpu_hits_t), vp, C.c_int32, vp, vp, vp, vp, vp, vp,
+                                          C.c_int32, C.POINTER(sbgpu_body_profile_t)]
+    L.sbgpu_body_profile_device.argtypes = [vp, vp, C.POINTER(sbgpu_annotation_t), C.POINTER(sbgpu_hits_t), vp, vp, vp, C.c_int32, vp,
+                                            C.POINTER(sbgpu_body_profile_t)]
+    L.sbgpu_body_profile_limits.argtypes = [C.POINTER(C.c_int64)]
     L.sbgpu_bootstrap_counts_host.argtypes = [C.c_int64, vp, vp, vp, C.c_uint64, C.c_int32, vp]
     L.sbgpu_bootstrap_counts_device.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp]
     L.sbgpu_em_bootstrap_device.argtypes = [vp, vp, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp, vp, vp, vp, vp, vp]

@@ -230,8 +230,8 @@ class ChainQuantifier:
         keep_context=True (resident only): every step asks the context to keep what the `-f` table needs (sbgpu_context_table_keep,
         switched on for the step's own call only: the context may be shared) and the last step's handle lives on in
         `context_handle`; context_table() builds the table from it on the device, fragment_assignment() every hit's isoform
-        posterior, isoform_coverage() the per-exon bases and junction support (all from the same retention, in any order,
-        repeatedly).
+        posterior, isoform_coverage() the per-exon bases and junction support, body_profile() the bases by positional bin (all
+        from the same retention, in any order, repeatedly).
         keep_bootstrap=True (resident only): likewise for the bootstrap (sbgpu_bootstrap_keep); abundance_bootstrap() runs it on the
         last step's handle, model_fit() the model fit (fit.model_fit_device) and isoform_information() the isoform information
         (info.model_info_device) and isoform_support() the drop-one support (support.model_loo_device), which work from the same
@@ -364,6 +364,18 @@ class ChainQuantifier:
         d_hits, d_mass = self._coverage_hits()
         return coverage.isoform_coverage_device(self.ctx, self.context_handle, self.annot, d_hits, int(self._out.d_theta) if d_theta is None else d_theta,
                                                 d_hit_mass=d_mass, want=want)
+
+    def body_profile(self, iso_strand=None, n_pos=20, d_theta=None, want=None):
+        """Every isoform's posterior-weighted bases by 5' -> 3' positional bin, its total, centre and coefficient of variation, and
+        the sample's curve per length class for the last step (body.BodyProfile), built on the device under the step's own theta
+        -- or d_theta, as for fragment_assignment() -- and the hits' masses.  iso_strand: 0 / 1 / 2 per isoform (None: all 0);
+        want: the arrays to bring to the host (None: all)."""
+        from . import body
+        if self.context_handle is None or not self.keep_context:
+            raise _lib.SbgpuError("body_profile: no step has run with keep_context=True")
+        d_hits, d_mass = self._coverage_hits()
+        return body.body_profile_device(self.ctx, self.context_handle, self.annot, d_hits, int(self._out.d_theta) if d_theta is None else d_theta,
+                                        d_hit_mass=d_mass, iso_strand=iso_strand, n_pos=n_pos, want=want)
 
     def abundance_bootstrap(self, n_rep, seed, **kw):
         """The bootstrap of the last step (keep_bootstrap=True): bootstrap.abundance_bootstrap_device on its handle, over this

@@ -9,11 +9,10 @@
 // Everything here is compiled under -ffp-contract=off.
 #pragma once
 
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/sbgpu.h"
-#include "assign_rules.h"
+#include "assign_rules.h" // (and, through context_rules.h, the HIP runtime where the compiler is HIP's: a plain C++ compiler takes this header too)
 
 namespace sb {
 

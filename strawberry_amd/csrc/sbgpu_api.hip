@@ -68,8 +68,8 @@ struct sbgpu_ctx {
    int n_phase_timed = 0;
    // grow-only device scratch of the multi-stage entry points (a hipMalloc / hipFree pair of a few GB per call costs
    // tens to hundreds of milliseconds): sb::ctx_scratch
-   char *scratch[14] = {};
-   size_t scratch_bytes[14] = {};
+   char *scratch[sb::kScratchSlots] = {};
+   size_t scratch_bytes[sb::kScratchSlots] = {};
    int32_t *d_pdf_support = nullptr; // [5] device: support of the insert-size table of the bin-weight launch in flight (pdf_support_kernel)
    int32_t *wide_error = nullptr; // pinned host word the wide-locus kernel raises when a barrier times out
    // kernel stages of the chain entry points, bracketed by events while `timing` is on (sb::ctx_stage_begin / _end)
@@ -298,11 +298,11 @@ void ctx_set_pairs_hint(sbgpu_ctx_t *ctx, size_t bytes) { ctx->pairs_hint = byte
 hipError_t ctx_scratch(sbgpu_ctx_t *ctx, int slot, size_t bytes, char **out)
 {
    *out = nullptr;
-   if (slot < 0 || slot >= 14) return hipErrorInvalidValue;
+   if (slot < 0 || slot >= kScratchSlots) return hipErrorInvalidValue;
    // what a resident call kept for sbgpu_context_table_device lies in slots 0..7: whoever asks for one of them (any entry that
    // works in the context's scratch, not only sbgpu_quantify_*) may overwrite or free it, so the record ends here
-   // (8 .. 13 hold what is made FROM the record: the context table, the fragment assignment, the isoform coverage,
-   // the model fit, the isoform information, the isoform support)
+   // (8 .. 14 hold what is made FROM the record: the context table, the fragment assignment, the isoform coverage,
+   // the model fit, the isoform information, the isoform support, the body profile)
    if (slot < 8) ctx->context_keep.serial = 0, ctx->boot_keep.serial = 0;
    if (bytes < 256) bytes = 256;
    if (ctx->scratch_bytes[slot] < bytes) {
@@ -677,7 +677,7 @@ int sbgpu_finalize(sbgpu_ctx_t *c)
       for (hipEvent_t e : ev)
          if (e) (void)hipEventDestroy(e);
    if (c->d_pdf_support) (void)hipFree(c->d_pdf_support);
-   for (int i = 0; i < 14; ++i)
+   for (int i = 0; i < sb::kScratchSlots; ++i)
       if (c->scratch[i]) (void)hipFree(c->scratch[i]);
    for (int i = 0; i < 4; ++i)
       if (c->pinned[i]) (void)hipHostFree(c->pinned[i]);

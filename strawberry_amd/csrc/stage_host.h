@@ -1,5 +1,5 @@
 // strawberry_amd/csrc/stage_host.h -- what the retained-result stages (the `-f` table, the fragment assignment, the isoform
-// coverage, the model fit, the isoform information) share on the host, free of HIP: a plain C++ compiler takes this header alone.
+// coverage, the model fit, the isoform information, the body profile) share on the host, free of HIP: a plain C++ compiler takes this header alone.
 //   - the limits of one locus and the work item of the hit kernels (one definition; the stages' headers alias them),
 //   - the builder of the work items,
 //   - the arena's layout: Arena::take, and each stage's offsets as one struct made by one function,
@@ -115,6 +115,32 @@ inline CovLayout cov_layout(int64_t n_loci, int64_t n_bins, int64_t n_iso, int64
    L.bases = a.take(ne1 * 8), L.junc = a.take(ne1 * 8), L.unex = a.take(nl1 * 8);
    L.sums_bytes = a.size - L.bases;
    L.iso = a.take(ni1 * 8);
+   L.bytes = a.size;
+   return L;
+}
+
+// The body profile.  epre: every exon's prefix length inside its isoform; ilen: every isoform's length; strand:
+// one byte per isoform -- all three made on the host, once per call.
+struct BodyLayout {
+   size_t roff, ioff, foff, items, eoff, eleft, eright, epre, ilen, strand, upload_bytes;
+   size_t live, gain;
+   size_t bases, cprof, cn, sums_bytes; // the sums, zeroed per call: [bases, bases + sums_bytes)
+   size_t total, center, cv, bytes;
+};
+inline BodyLayout body_layout(int64_t n_loci, int64_t n_bins, int64_t n_iso, int64_t n_exon, int64_t n_items, int n_pos, bool upload_exons)
+{
+   const size_t nl1 = (size_t)n_loci + 1, ni1 = (size_t)n_iso + 1, ne1 = at_least_1(n_exon);
+   Arena a;
+   BodyLayout L;
+   L.roff = a.take(nl1 * 8), L.ioff = a.take(nl1 * 8), L.foff = a.take(nl1 * 8);
+   L.items = a.take(at_least_1(n_items) * sizeof(HitItem));
+   L.eoff = a.take(upload_exons ? ni1 * 8 : 0), L.eleft = a.take(upload_exons ? ne1 * 4 : 0), L.eright = a.take(upload_exons ? ne1 * 4 : 0);
+   L.epre = a.take(ne1 * 8), L.ilen = a.take(ni1 * 8), L.strand = a.take(ni1);
+   L.upload_bytes = a.size;
+   L.live = a.take(at_least_1(n_bins)), L.gain = a.take(ni1 * 8);
+   L.bases = a.take(ni1 * (size_t)n_pos * 8), L.cprof = a.take(4 * (size_t)n_pos * 8), L.cn = a.take(4 * 8);
+   L.sums_bytes = a.size - L.bases;
+   L.total = a.take(ni1 * 8), L.center = a.take(ni1 * 8), L.cv = a.take(ni1 * 8);
    L.bytes = a.size;
    return L;
 }

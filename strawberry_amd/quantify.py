@@ -229,7 +229,7 @@ class BinsHandle:
 def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=False, ctx=None, device=0, comm=None,
                       min_isoform_frac=0.0, filter_by_expression=True, effective_len_norm=False, with_context=False, bootstrap=None,
                       keep_bootstrap=False, keep_handle=False, with_assignment=False, with_coverage=False, with_fit=False, with_info=False,
-                      with_support=False):
+                      with_support=False, with_body_profile=False, iso_strand=None, n_pos=20):
     """sbgpu_quantify_resident on host hits brought to the device first (torch owns the copies): pass 1 (insert=None: the
     empirical insert-size law, built on the device), bins, weights, EM, FPKM / Frac / keep, the FPKM all-reduce over `comm`
     (dist.AbiComm / dist.HostComm; None: a world of one), TPM.  The hits must come grouped by locus.
@@ -239,6 +239,9 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     the device (assign.fragment_assign_device) -> "assignment"; "bins" as with_context.
     with_coverage: the same retention, and the isoform-resolved coverage under the call's theta and the hits' masses, built on the
     device from the hits the call was given (coverage.isoform_coverage_device) -> "coverage"; "bins" as with_context.
+    with_body_profile: the same retention, and the transcript-body coverage profile under the call's theta and the hits' masses at
+    n_pos positional bins, oriented by iso_strand (one of 0, 1, 2 per isoform; None: all 0), built on the device
+    (body.body_profile_device) -> "body_profile": a body.BodyProfile; "bins" as with_context.
     bootstrap = dict(n_rep=, seed=, level=0.95, locus_id=None, ...): the call keeps what the bootstrap needs (sbgpu_bootstrap_keep)
     and bootstrap.abundance_bootstrap_device runs on its handle with these arguments (and `comm`) -> "bootstrap": its dict; "bins" as above.
     With locus=True among them the bootstrap is sbgpu_locus_bootstrap_device: "bootstrap" also holds "frac" and "locus" (DESIGN 3.19).
@@ -281,7 +284,7 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     ins = insert._struct(read_len, long_read) if insert is not None else None
     handle = C.c_void_p()
     torch.cuda.synchronize(dev)
-    retain = bool(with_context) or bool(with_assignment) or bool(with_coverage)
+    retain = bool(with_context) or bool(with_assignment) or bool(with_coverage) or bool(with_body_profile)
     if retain:
         _lib.check(L.sbgpu_context_table_keep(ctx.h, 1), "sbgpu_context_table_keep")
     keep_bootstrap = bool(keep_bootstrap) or bootstrap is not None or bool(with_fit) or bool(with_info) or bool(with_support)
@@ -303,9 +306,9 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     owner = BinsHandle(L, handle) if keep_handle else None     # (from here on an exception frees the handle with the object)
     info = (C.c_int64 * 8)()
     _lib.check(L.sbgpu_bins_info(handle, info), "sbgpu_bins_info")
-    table = bins = boot = assignment = cov = model_fit = iso_info = iso_support = None
+    table = bins = boot = assignment = cov = model_fit = iso_info = iso_support = profile = None
     if retain or bootstrap is not None or with_fit or with_info or with_support:
-        from . import assign, context, coverage, fit, support
+        from . import assign, body, context, coverage, fit, support
         from . import info as isoform_info
         from .bootstrap import abundance_bootstrap_device
         from .exonbin import LocusBins
@@ -318,6 +321,8 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
                 assignment = assign.fragment_assign_device(ctx, handle, int(out.d_theta), hits.n_hits, d_hit_mass=d_mass)
             if with_coverage:
                 cov = coverage.isoform_coverage_device(ctx, handle, annot, hs, int(out.d_theta), d_hit_mass=d_mass)
+            if with_body_profile:
+                profile = body.body_profile_device(ctx, handle, annot, hs, int(out.d_theta), d_hit_mass=d_mass, iso_strand=iso_strand, n_pos=n_pos)
             if with_fit:
                 model_fit = fit.model_fit_device(ctx, handle, int(out.d_theta), int(out.d_keep), int(out.d_status))
             if with_info:
@@ -344,6 +349,8 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
         r.update(assignment=assignment, bins=bins)
     if with_coverage:
         r.update(coverage=cov, bins=bins)
+    if with_body_profile:
+        r.update(body_profile=profile, bins=bins)
     if bootstrap is not None:
         r.update(bootstrap=boot, bins=bins)
     if with_fit:
