@@ -582,8 +582,21 @@ __device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballo
 
 constexpr int kBlockWaves = 4; // block form: 256 lanes, one wave per SIMD, up to 512 VGPRs each
 
+// Block form, tiles of R = 4 or 6 rows: f(ru_tag) with the rows the current locus uses (workgroup-uniform) as a
+// compile-time constant, 2..R.  A locus of one row runs the two-row loop: its second row is an unused row's zeros.
+template <int R, class Fn>
+__device__ __forceinline__ void with_block_rows(int r_used, Fn f)
+{
+   static_assert(R == 4 || R == 6, "the row counts of the 4- and 6-row tiles");
+   if (r_used <= 2) f(std::integral_constant<int, 2>());
+   else if (r_used == 3) f(std::integral_constant<int, 3>());
+   else if (R == 4 || r_used == 4) f(std::integral_constant<int, 4>());
+   else if (r_used == 5) f(std::integral_constant<int, (R > 4 ? 5 : R)>());
+   else f(std::integral_constant<int, R>());
+}
+
 // NWAVES = 0: wave form; NWAVES = 4: block form.  R is the register-tile capacity
-// in rows per row lane; the block form skips the row blocks a locus does not need.
+// in rows per row lane; the block form skips the rows a locus does not need (kRowsCT below).
 // HIMAP (wave form only): the row lanes of a group are the TOP lane bits and the groups of a wave are
 // interleaved between them and the column lanes -- lane = gc | group << log2(CL) | gr << (6 - log2(GR)) -- so that
 // the all-reduce over the row lanes runs over lane bits 4 and 5 first, which one matrix instruction covers
@@ -623,6 +636,11 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
    bool batch_taken = false; // the one refill has happened
    int phase = 0;
    int r_used = R; // block form: rows per row lane the current locus needs (workgroup-uniform)
+   // Block form, fp64 tiles of up to 6 rows (99 % of the kind's iterations on C3): only the r_used rows exist.  The steady
+   // loop is instantiated once per row count (with_block_rows: one uniform switch outside the loop, no branch on a row
+   // inside) and the passes that run once per locus skip by row.  The taller tiles and the fp32 variant skip the rows a
+   // locus does not use in blocks of four.
+   constexpr bool kRowsCT = BLOCK && std::is_same<T, double>::value && R <= 6;
 #ifdef SB_STAMPS
    unsigned long long st_refill = 0, st_events = 0, st_first = 0, st_batches = 0, st_iters = 0, st_t = 0;
 #endif
@@ -682,7 +700,7 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
          T sum = T(0);
 #pragma unroll
          for (int r = 0; r < R; ++r)
-            if (!BLOCK || (r & ~3) < r_used) sum += F[r][jj];
+            if (!BLOCK || (kRowsCT ? r : (r & ~3)) < r_used) sum += F[r][jj];
          cs[jj] = sum;
       }
       row_lane_sum(cs, std::integral_constant<int, CPL>(), std::integral_constant<int, -1>());
@@ -694,7 +712,7 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
    auto normalise_tile = [&](bool mine) {
 #pragma unroll
       for (int r = 0; r < R; ++r) {
-         if (BLOCK && (r & ~3) >= r_used) continue;
+         if (BLOCK && (kRowsCT ? r : (r & ~3)) >= r_used) continue;
 #pragma unroll
          for (int jj = 0; jj < CPL; ++jj) F[r][jj] = mine ? F[r][jj] * scale[jj] : F[r][jj];
       }
@@ -713,8 +731,8 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
    // that split the R rows evenly, so that a lane takes the reciprocals of R >> kLbScat rows instead of all R, and the
    // weights are gathered back (col_lanes_scatter).  The tile then holds the rows of a lane in its own order: slot r
    // holds row r ^ perm of the row lane, set once as the tile is loaded.  (kLbScat = 0: every lane all R rows, in
-   // order, as for one column lane.)  The block form keeps the all-reduce: it skips the row blocks a locus does not
-   // need, and the exchange, which runs over all R slots, cost it more than it saved (profiles/EXPERIMENTS_r07.md).
+   // order, as for one column lane.)  The block form keeps the all-reduce: it skips the rows a locus does not need, and
+   // the exchange, which runs over all R slots, cost it more than it saved (profiles/EXPERIMENTS_r07.md).
    constexpr int kLbScat = (kBatchDiv && !HIMAP && !BLOCK && LB_CL >= 1)
                               ? (pow2_factor(R) < LB_CL ? pow2_factor(R) : LB_CL)
                               : 0;
@@ -779,7 +797,7 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
          red[1] = T(0); // number of kept rows
 #pragma unroll
          for (int r = 0; r < R; ++r) {
-            if (BLOCK && (r & ~3) >= r_used) continue; // row block not needed by this locus
+            if (BLOCK && (kRowsCT ? r : (r & ~3)) >= r_used) continue; // row (or row block) not needed by this locus
             const int i = tile_row(r) * GR + gr;
             const bool valid = got && i < nrow;
             // clamped indices: loads stay inside the locus (or touch nothing when it
@@ -910,8 +928,13 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
       const unsigned long long have_mask = __builtin_amdgcn_ballot_w64(have); // (have changes only outside the loop)
       T d2_last; // ||next - theta||^2 of the iteration just done
       // one EM iteration: reads tin, writes tout (all lanes, no predication)
-      auto iterate = [&](const T *tin, T *tout, auto exact_tag, auto lb_tag) {
+      // (ru_tag: the rows of this instantiation (with_block_rows) -- the rows beyond them get no dot product, no
+      // column-lane sum, no weight and no place in a reciprocal batch -- or -1: all R rows, in the block form minus the
+      // unused blocks of four)
+      auto iterate = [&](const T *tin, T *tout, auto exact_tag, auto lb_tag, auto ru_tag) {
          constexpr bool kExact = decltype(exact_tag)::value;
+         constexpr int RUC = decltype(ru_tag)::value;
+         constexpr int RN = RUC > 0 ? RUC : R;
          T acc[NV];
 #pragma unroll
          for (int v = 0; v < NV; ++v) acc[v] = T(0);
@@ -925,7 +948,7 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
             // of its slots 0, P, 2P, ..., takes their reciprocals and weights, and the weights are gathered back into
             // every column lane's own row order.  A zero denominator still makes its owner's weight a NaN, and the
             // gather hands that NaN to every column lane of the group.
-            static_assert(!BLOCK, "the block form skips row blocks: it keeps the all-reduce");
+            static_assert(!BLOCK, "the block form skips unused rows: it keeps the all-reduce");
             constexpr int P = 1 << kLbScat;
             T x[R];
 #pragma unroll
@@ -963,12 +986,12 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
          } else {
          // rows in blocks of 4 to bound the live temporaries
 #pragma unroll
-         for (int rb = 0; rb < R; rb += 4) {
-            if (BLOCK && rb >= r_used) continue;
+         for (int rb = 0; rb < RN; rb += 4) {
+            if (BLOCK && RUC < 0 && rb >= r_used) continue;
             T d[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-               if (rb + q < R) {
+               if (rb + q < RN) {
                   T sum = kDfix ? dfix[rb + q] : T(0);
 #pragma unroll
                   for (int jj = 0; jj < CPL; ++jj) sum = fma_t(F[rb + q][jj], tin[jj], sum); // :450
@@ -977,7 +1000,7 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
             }
             if constexpr (kBatchDiv && !kExact) {
                // the block's reciprocals from one v_rcp_f64 (see batch_reciprocals)
-               const int nb = R - rb < 4 ? R - rb : 4; // a constant once the loop is unrolled
+               const int nb = RN - rb < 4 ? RN - rb : 4; // a constant once the loop is unrolled
                double dd[4], inv[4];
 #pragma unroll
                for (int q = 0; q < 4; ++q) dd[q] = q < nb ? d[q] : 1.0;
@@ -996,7 +1019,7 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
             } else {
 #pragma unroll
                for (int q = 0; q < 4; ++q) {
-                  if (rb + q < R) {
+                  if (rb + q < RN) {
                      const int r = rb + q;
                      T w = fast_div(nn[r], d[q]);
                      if (!kDfix) w = act[r] ? w : T(0);
@@ -1034,9 +1057,9 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
          conv = d2_last <= ThetaLimitSq<T>::value;
          dz = __builtin_isnan(d2_last);
       };
-      auto run = [&](auto lb_tag) {
+      auto run = [&](auto lb_tag, auto ru_tag) {
       for (;;) {
-         iterate(theta, nt, std::false_type(), lb_tag); // old in theta, new in nt
+         iterate(theta, nt, std::false_type(), lb_tag, ru_tag); // old in theta, new in nt
 #ifdef SB_STAMPS
          st_iters += 1;
 #endif
@@ -1050,7 +1073,7 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
             break;
          }
          ++it;
-         iterate(nt, theta, std::false_type(), lb_tag); // old in nt, new in theta
+         iterate(nt, theta, std::false_type(), lb_tag, ru_tag); // old in nt, new in theta
 #ifdef SB_STAMPS
          st_iters += 1;
 #endif
@@ -1069,16 +1092,19 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
          ++it;
       }
       };
-      // the loop once per common group height (wave form; the block form's is a constant anyway)
-      if (BLOCK || HIMAP) run(std::integral_constant<int, -1>());
-      else if (lbGR == 4 && LB_CL <= 2) run(std::integral_constant<int, (LB_CL <= 2 ? 4 : -1)>());
-      else if (lbGR == 3) run(std::integral_constant<int, 3>());
-      else if (lbGR == 5 && LB_CL <= 1) run(std::integral_constant<int, (LB_CL <= 1 ? 5 : -1)>());
-      else if (lbGR == 2) run(std::integral_constant<int, 2>());
-      else if (lbGR == 1) run(std::integral_constant<int, 1>());
-      else if (lbGR == 6 && LB_CL == 0) run(std::integral_constant<int, (LB_CL == 0 ? 6 : -1)>());
-      else if (lbGR == 0) run(std::integral_constant<int, 0>()); // (a group of CL lanes: no row lanes to sum over)
-      else run(std::integral_constant<int, -1>());
+      // the loop once per common group height (wave form; the block form's is a constant anyway) -- and, in the block
+      // form, once per row count of the locus (with_block_rows)
+      constexpr std::integral_constant<int, -1> all_rows{};
+      if constexpr (kRowsCT) with_block_rows<R>(r_used, [&](auto ru_tag) { run(std::integral_constant<int, -1>(), ru_tag); });
+      else if (BLOCK || HIMAP) run(std::integral_constant<int, -1>(), all_rows);
+      else if (lbGR == 4 && LB_CL <= 2) run(std::integral_constant<int, (LB_CL <= 2 ? 4 : -1)>(), all_rows);
+      else if (lbGR == 3) run(std::integral_constant<int, 3>(), all_rows);
+      else if (lbGR == 5 && LB_CL <= 1) run(std::integral_constant<int, (LB_CL <= 1 ? 5 : -1)>(), all_rows);
+      else if (lbGR == 2) run(std::integral_constant<int, 2>(), all_rows);
+      else if (lbGR == 1) run(std::integral_constant<int, 1>(), all_rows);
+      else if (lbGR == 6 && LB_CL == 0) run(std::integral_constant<int, (LB_CL == 0 ? 6 : -1)>(), all_rows);
+      else if (lbGR == 0) run(std::integral_constant<int, 0>(), all_rows); // (a group of CL lanes: no row lanes to sum over)
+      else run(std::integral_constant<int, -1>(), all_rows);
 
       // ------------------------------------------------------- per-group events
       // (`it` still counts the iterations BEFORE the one whose results are looked at here)
@@ -1094,7 +1120,12 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
             const unsigned long long keep_mask = special_mask;
 #pragma unroll
             for (int jj = 0; jj < CPL; ++jj) keep_nt[jj] = nt[jj];
-            iterate(theta, nt, std::true_type(), std::integral_constant<int, -1>());
+            if constexpr (kRowsCT)
+               with_block_rows<R>(r_used, [&](auto ru_tag) {
+                  iterate(theta, nt, std::true_type(), std::integral_constant<int, -1>(), ru_tag);
+               });
+            else
+               iterate(theta, nt, std::true_type(), std::integral_constant<int, -1>(), std::integral_constant<int, -1>());
             classify();
 #pragma unroll
             for (int jj = 0; jj < CPL; ++jj) nt[jj] = suspect ? nt[jj] : keep_nt[jj];
