@@ -4,11 +4,13 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
+#include <cstring>
 #include <thread>
 #include <map>
 #include <tuple>
 
 #include "../../include/sbgpu.h"
+#include "stage_host.h"
 
 namespace sb {
 
@@ -448,6 +450,158 @@ int build_host_plan(int64_t n_loci, const int64_t *row_off, const int64_t *iso_o
       }
    }
    return SBGPU_OK;
+}
+
+WidePacking pack_wide_rounds(HostPlan *plan, const int64_t *row_off, const int64_t *iso_off, int n_cu, bool no_wide)
+{
+   WidePacking out;
+   for (SizeClass &sc : plan->classes) {
+      if (sc.kind != kStream) continue;
+      // A locus' layout is the one that serves it with the fewest workgroups (em_wide_layout.h: 16 / 32 / 64 column lanes x
+      // 4-8 columns; rows per workgroup = register rows + LDS rows); the rows are then dealt evenly.
+      struct Wide {
+         int G, layout;
+         int32_t locus;
+      };
+      // A round's time is its slowest locus', and an iteration costs the more the more workgroups exchange partials, so
+      // loci of like workgroup counts share rounds: largest first
+      std::vector<Wide> wide;
+      std::vector<int32_t> rest;
+      for (int32_t l : sc.loci) {
+         const int64_t nrow = row_off[l + 1] - row_off[l], niso = iso_off[l + 1] - iso_off[l];
+         const int layout = wide_layout_for(niso, nrow);
+         const int64_t rpb = layout < 0 ? 1 : wide_rows_per_block(layout);
+         const int64_t G = (nrow + rpb - 1) / rpb;
+         if (layout >= 0 && nrow > 0 && G <= n_cu && !no_wide) wide.push_back({(int)G, layout, l});
+         else rest.push_back(l);
+      }
+      std::stable_sort(wide.begin(), wide.end(), [](const Wide &x, const Wide &y) { return x.G > y.G; });
+      // Rounds: every launch holds at most n_cu workgroups, all resident.  First fit, most workgroups first: a locus goes
+      // to the first round that has room (a round is as long as its slowest locus, and a locus of fewer workgroups is never
+      // slower than one of more: filling the gaps of the early rounds with small loci costs nothing and can save the last,
+      // mostly empty launch).  A round's descriptors are consecutive in the table, ordered by their first workgroup.
+      std::vector<std::vector<Wide>> members;
+      std::vector<int> used;
+      for (const Wide &w : wide) {
+         size_t r = 0;
+         while (r < used.size() && used[r] + w.G > n_cu) ++r;
+         if (r == used.size()) {
+            used.push_back(0);
+            members.emplace_back();
+         }
+         used[r] += w.G;
+         members[r].push_back(w);
+      }
+      sc.loci.clear();
+      for (const std::vector<Wide> &round_members : members) {
+         WideRound round;
+         round.first_desc = (int)out.table.size();
+         for (const Wide &w : round_members) {
+            const int64_t nrow = row_off[w.locus + 1] - row_off[w.locus];
+            WideDesc d;
+            d.locus = w.locus;
+            d.first_block = round.n_blocks;
+            d.n_blocks = w.G;
+            d.rows_per_block = (int32_t)std::max<int64_t>(1, (nrow + w.G - 1) / w.G);
+            d.npad = wide_cols(w.layout);
+            d.buf_off = (int64_t)out.buf_doubles;
+            d.layout = w.layout;
+            d.lb_slice = wide_lb_slice(d.npad, w.G);
+            d.pad_ = 0;
+            out.buf_doubles += (size_t)4 * w.G * d.npad + (size_t)4 * d.npad; // two buffers of G x npad 16-byte granules (partials) + two of npad (totals)
+            round.n_blocks += w.G;
+            round.n_desc += 1;
+            round.lds_bytes = std::max(round.lds_bytes, wide_lds_bytes(w.layout));
+            out.table.push_back(d);
+            sc.loci.push_back(w.locus);
+         }
+         out.rounds.push_back(round);
+      }
+      out.n_wide_loci = (int32_t)sc.loci.size();
+      sc.loci.insert(sc.loci.end(), rest.begin(), rest.end());
+      sc.n_blocks = (int)rest.size(); // what is left for the streaming kernel
+   }
+   return out;
+}
+
+PlanLayout plan_arena_layout(const HostPlan &plan, size_t n_wide_desc, size_t wide_buf_doubles)
+{
+   const size_t nl1 = (size_t)plan.n_loci + 1, ncls1 = plan.classes.size() + 1, nlat = plan.lat.size();
+   size_t n_phased = 0; // loci of the phased wave kind = capacity of every later phase's lists
+   if (nlat)
+      for (int32_t cap : plan.lat[0].capacity) n_phased += (size_t)cap;
+   Arena a;
+   PlanLayout L;
+   L.lat.resize(nlat);
+   L.row_off = a.take(nl1 * 8), L.iso_off = a.take(nl1 * 8), L.f_off = a.take(nl1 * 8);
+   L.loci = a.take(nl1 * 4);
+   L.tables = a.take(ncls1 * sizeof(ClassRecord)), L.class_n = a.take(ncls1 * 4);
+   L.wide_table = a.take((n_wide_desc + 1) * sizeof(WideDesc));
+   for (size_t i = 0; i < nlat; ++i) {
+      L.lat[i].table = a.take((plan.lat[i].classes.size() + 1) * sizeof(ClassRecord));
+      L.lat[i].route = a.take(nl1 * 4);
+   }
+   L.epi_ticket = a.take(sizeof(unsigned)); // (zero: it goes up with the staged head)
+   L.staged = a.size;
+   L.zero = a.size;
+   for (size_t i = 0; i < nlat; ++i) {
+      L.lat[i].counts = a.take((plan.lat[i].classes.size() + 1) * 4);
+      L.lat[i].total = a.take(4);
+   }
+   L.zero_bytes = a.size - L.zero;
+   for (size_t i = 0; i < nlat; ++i) L.lat[i].lists = a.take((n_phased + 1) * 4);
+   L.row_keep = a.take((size_t)plan.n_rows + 1);
+   L.locus_sum = a.take(nl1 * 8);
+   L.wide_bufs = a.take((wide_buf_doubles + 1) * 8);
+   L.bytes = a.size;
+   return L;
+}
+
+PlanHead stage_plan_head(const HostPlan &plan, const PlanLayout &L, const int64_t *row_off, const int64_t *iso_off, const int64_t *f_off,
+                         const std::vector<WideDesc> &wide_table, char *head)
+{
+   PlanHead out;
+   if (plan.n_loci > 0) {
+      const size_t nb = (size_t)(plan.n_loci + 1) * sizeof(int64_t);
+      std::memcpy(head + L.row_off, row_off, nb);
+      std::memcpy(head + L.iso_off, iso_off, nb);
+      std::memcpy(head + L.f_off, f_off, nb);
+   }
+   if (!wide_table.empty()) std::memcpy(head + L.wide_table, wide_table.data(), wide_table.size() * sizeof(WideDesc));
+   auto record = [](const SizeClass &sc, int32_t block_begin, int32_t n, int32_t loci_off) {
+      return ClassRecord{block_begin, n, loci_off, sc.layout | (sc.rmult << 8) | (sc.lbG << 16)};
+   };
+   for (size_t i = 0; i < plan.lat.size(); ++i) {
+      const LatPhase &lp = plan.lat[i];
+      ClassRecord *lt = (ClassRecord *)(head + L.lat[i].table);
+      int32_t loff = 0;
+      for (size_t ci = 0; ci < lp.classes.size(); ++ci) {
+         lt[ci] = record(lp.classes[ci], 0, lp.capacity[ci], loff); // (its first block: phase_prepare_kernel fills it from the survivor counts)
+         loff += lp.capacity[ci];
+      }
+      if (!lp.route.empty()) std::memcpy(head + L.lat[i].route, lp.route.data(), lp.route.size() * sizeof(int32_t));
+   }
+   int32_t *loci = (int32_t *)(head + L.loci), *class_n = (int32_t *)(head + L.class_n);
+   ClassRecord *table = (ClassRecord *)(head + L.tables);
+   size_t off = 0;
+   for (size_t ci = 0; ci < plan.classes.size(); ++ci) {
+      const SizeClass &sc = plan.classes[ci];
+      KindLaunch &kl = out.launches[sc.kind];
+      if (kl.n_classes == 0) {
+         kl.first_class = (int)ci;
+         kl.block_threads = sc.block_threads;
+      }
+      table[ci] = record(sc, kl.n_blocks, (int32_t)sc.loci.size(), (int32_t)off);
+      class_n[ci] = table[ci].n;
+      kl.n_blocks += sc.n_blocks;
+      kl.n_classes += 1;
+      if (!sc.loci.empty()) std::memcpy(loci + off, sc.loci.data(), sc.loci.size() * sizeof(int32_t));
+      out.loci_off.push_back((int64_t)off);
+      off += sc.loci.size();
+      if (sc.kind == kStream)
+         for (int32_t l : sc.loci) out.max_stream_iso = std::max(out.max_stream_iso, (size_t)(iso_off[l + 1] - iso_off[l]));
+   }
+   return out;
 }
 
 } // namespace sb

@@ -8,8 +8,11 @@
 // kernel launch whose workgroups look their class up in a descriptor table.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 #include <vector>
+
+#include "em_wide_layout.h"
 
 namespace sb {
 
@@ -122,5 +125,62 @@ bool lat_layout_for(int64_t nrow, int64_t niso, double lambda, LatLayout *out);
 int build_host_plan(int64_t n_loci, const int64_t *row_off, const int64_t *iso_off,
                     const int64_t *f_off, int n_cu, const PlanTuning &tune, HostPlan *out,
                     const char **err);
+
+// ---- what sbgpu_plan_create makes of a HostPlan before anything goes to the device (plan.cpp; tests/test_plan_wide_cpp.py)
+
+// Wide loci (kStream class) served by the cooperative multi-workgroup kernel, in launches ("rounds") of at most n_cu workgroups
+struct WideRound {
+   int first_desc = 0, n_desc = 0, n_blocks = 0; // its descriptors in the table; its workgroups
+   size_t lds_bytes = 0;                         // the largest any of its loci's layouts asks for
+};
+struct WidePacking {
+   std::vector<WideDesc> table;   // all rounds' descriptors, a round's consecutive and ordered by first workgroup
+   std::vector<WideRound> rounds;
+   size_t buf_doubles = 0;        // the exchange buffers of all loci
+   int32_t n_wide_loci = 0;       // the first n_wide_loci of the stream class' list go to the wide kernel
+};
+// The streaming class is served by the multi-workgroup kernel wherever a locus has rows and they fit into n_cu workgroups
+// (no_wide: nowhere).  Such loci move to the front of the class' list, in the table's order; the rest keeps its order and
+// the streaming kernel, and the class' n_blocks becomes the rest's count.
+WidePacking pack_wide_rounds(HostPlan *plan, const int64_t *row_off, const int64_t *iso_off, int n_cu, bool no_wide);
+
+// The plan's one device arena (Arena::take, stage_host.h), in the order the arrays are taken.  Three things hold:
+//   - [0, staged) is the head that the host stages and ONE copy uploads: offsets, class lists, tables, class sizes, the wide
+//     table, the later phases' tables and routes, and the epilogue's ticket (zero);
+//   - [zero, zero + zero_bytes) is what every run zeroes first, in one memset: every later phase's survivor counts and batch total;
+//   - every array has one element more than it needs (none is empty, whatever the batch).
+struct PlanLatLayout {
+   size_t table, route;  // staged
+   size_t counts, total; // zeroed per run
+   size_t lists;
+};
+struct PlanLayout {
+   size_t row_off, iso_off, f_off, loci, tables, class_n, wide_table;
+   std::vector<PlanLatLayout> lat;
+   size_t epi_ticket, staged;
+   size_t zero, zero_bytes;
+   size_t row_keep, locus_sum, wide_bufs, bytes;
+};
+PlanLayout plan_arena_layout(const HostPlan &plan, size_t n_wide_desc, size_t wide_buf_doubles);
+
+// One kernel launch per kind: its classes (a range of HostPlan::classes), its workgroups
+struct KindLaunch {
+   int first_class = 0, n_classes = 0;
+   int n_blocks = 0;
+   int block_threads = 0;
+};
+// A class inside a launch's table as the kernels read it (em_device.h: ClassDesc -- sbgpu_api.hip asserts they are one layout)
+struct ClassRecord {
+   int32_t block_begin, n, loci_off, shape;
+};
+struct PlanHead {
+   KindLaunch launches[kNumKinds];
+   std::vector<int64_t> loci_off; // per class: offset of its list in the concatenated lists
+   size_t max_stream_iso = 0;     // widest locus of the stream class
+};
+// Fills the arena's head -- `head`: L.staged bytes, zeroed by the caller -- and derives the per-kind launch records.
+// (pack_wide_rounds comes first: it reorders the stream class' list.)
+PlanHead stage_plan_head(const HostPlan &plan, const PlanLayout &L, const int64_t *row_off, const int64_t *iso_off, const int64_t *f_off,
+                         const std::vector<WideDesc> &wide_table, char *head);
 
 } // namespace sb

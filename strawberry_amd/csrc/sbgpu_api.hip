@@ -20,6 +20,7 @@
 #include "api_internal.h"
 #include "binweight_device.h"
 #include "em_device.h"
+#include "em_schedule.h"
 #include "em_wide.h"
 #include "plan.h"
 
@@ -40,14 +41,15 @@ int fail(int code, const std::string &msg)
          return fail(SBGPU_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));          \
    } while (0)
 
-constexpr int kAuxStreams = 8;
+using sb::kAuxStreams; // em_schedule.h: the side streams, and which of them each kernel kind runs on
+using sb::kKindStream;
 constexpr int kMaxPhaseEvents = 6; // later phases of the wave kind that get timing events
-// Which aux stream each kernel kind runs on.  HIP folds streams onto a few hardware queues
-// (4 by default: GPU_MAX_HW_QUEUES) in creation order; measured on ROCm 7.2 the aux streams
-// land on queues {2,3,4,4,3,2,1,4} and the null stream on 3, so the three kinds that run
-// side by side (one wave kind, block, tall block) get streams 0, 2 and 6: three distinct queues
-// that also avoid the caller's.
-constexpr int kKindStream[sb::kNumKinds] = {0, 0, 0, 2, 6, 1};
+
+// plan.cpp stages the class tables without HIP, as sb::ClassRecord; the kernels read them as sb::ClassDesc
+static_assert(sizeof(sb::ClassRecord) == sizeof(sb::ClassDesc) && offsetof(sb::ClassRecord, block_begin) == offsetof(sb::ClassDesc, block_begin) &&
+                 offsetof(sb::ClassRecord, n) == offsetof(sb::ClassDesc, n) && offsetof(sb::ClassRecord, loci_off) == offsetof(sb::ClassDesc, loci_off) &&
+                 offsetof(sb::ClassRecord, shape) == offsetof(sb::ClassDesc, shape),
+              "plan.h's ClassRecord and em_device.h's ClassDesc are one layout");
 
 } // namespace
 
@@ -364,17 +366,10 @@ void ctx_boot_release(sbgpu_ctx_t *ctx)
 }
 } // namespace sb
 
-struct KindLaunch {
-   int first_class = 0, n_classes = 0; // range in plan->host.classes
-   int n_blocks = 0;
-   int block_threads = 0;
-   sb::ClassDesc *d_table = nullptr;   // points into plan->d_tables
-};
-
 struct sbgpu_plan {
    sbgpu_ctx *ctx = nullptr;
    sb::HostPlan host;
-   KindLaunch launches[sb::kNumKinds];
+   sb::KindLaunch launches[sb::kNumKinds]; // (a kind's table: d_tables + its first_class)
    char *d_arena = nullptr;            // one allocation (sb::dev_take), one upload: the arrays below point into it
    size_t arena_cap = 0;
    int64_t *d_row_off = nullptr, *d_iso_off = nullptr, *d_f_off = nullptr;
@@ -395,19 +390,11 @@ struct sbgpu_plan {
    sb::ClassDesc *d_tables = nullptr;  // one descriptor per class
    std::vector<int64_t> loci_off;      // per class: offset into d_loci_all
    uint8_t *d_row_keep = nullptr;      // streaming path: init() row flags
-   // SBGPU_GRAPH=1: the launches of sbgpu_em_run_device captured once per (plan, argument pointers, stream) and replayed
-   // (an experiment: DESIGN.md section 8)
-   mutable hipGraphExec_t graph_exec = nullptr;
-   mutable const void *graph_key[6] = {};
    double *d_locus_sum = nullptr;      // abundance epilogue: kept-FPKM sum per workgroup of 256 loci
    unsigned *d_epi_ticket = nullptr;   // abundance epilogue: finished workgroups (the last one sums; it leaves 0 behind)
    size_t stream_lds_bytes = 0;
-   // wide loci (kStream class) served by the cooperative multi-workgroup kernel, in launches ("rounds")
-   struct WideRound {
-      int first_desc = 0, n_desc = 0, n_blocks = 0;
-      size_t lds_bytes = 0;
-   };
-   std::vector<WideRound> wide_rounds;
+   // wide loci (kStream class) served by the cooperative multi-workgroup kernel, in launches ("rounds": sb::pack_wide_rounds)
+   std::vector<sb::WideRound> wide_rounds;
    sb::WideDesc *d_wide_table = nullptr; // all rounds' descriptors
    double *d_wide_bufs = nullptr;
    mutable unsigned wide_epoch = 0;    // bumped by every run: the tag space of its exchange granules
@@ -723,20 +710,13 @@ int sbgpu_plan_destroy(sbgpu_plan_t *p)
    // every device array of the plan lives in this one allocation; it goes back to the pool (dev_give waits for the device,
    // as hipFree did: a run on the caller's stream may still be reading it)
    sb::dev_give(p->d_arena, p->arena_cap);
-   if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
    delete p;
    return SBGPU_OK;
 }
 
-int sbgpu_plan_create(sbgpu_ctx_t *c, int64_t n_loci, const int64_t *row_off, const int64_t *iso_off,
-                      const int64_t *f_off, sbgpu_plan_t **plan_out)
+// the plan's experiment switches (the shipped library reads none: sb::exp_env)
+static sb::PlanTuning plan_tuning_from_env()
 {
-   if (!c || !plan_out) return fail(SBGPU_EINVAL, "sbgpu_plan_create: null argument");
-   *plan_out = nullptr;
-   sbgpu_plan *p = new (std::nothrow) sbgpu_plan();
-   if (!p) return fail(SBGPU_ENOMEM, "sbgpu_plan_create: out of host memory");
-   p->ctx = c;
-   const char *err = "";
    sb::PlanTuning tune;
    if (const char *e = sb::exp_env("SBGPU_WAVE_RMULT")) tune.wave_rmult = std::atoi(e);
    if (const char *e = sb::exp_env("SBGPU_MAX_WAVES")) tune.max_waves = std::atoll(e);
@@ -762,6 +742,17 @@ int sbgpu_plan_create(sbgpu_ctx_t *c, int64_t n_loci, const int64_t *row_off, co
    // a lane weight "t" makes the phase re-pack its survivors into their phase-0 layouts instead ("tile" phases)
    if (const char *e = sb::exp_env("SBGPU_PHASE_LAMBDA"))
       parse_list(e, [](const std::string &t) { return (!t.empty() && (t[0] == 't' || t[0] == 'T')) ? -1.0 : std::atof(t.c_str()); }, &tune.phase_lambda);
+   return tune;
+}
+
+int sbgpu_plan_create(sbgpu_ctx_t *c, int64_t n_loci, const int64_t *row_off, const int64_t *iso_off,
+                      const int64_t *f_off, sbgpu_plan_t **plan_out)
+{
+   if (!c || !plan_out) return fail(SBGPU_EINVAL, "sbgpu_plan_create: null argument");
+   *plan_out = nullptr;
+   sbgpu_plan *p = new (std::nothrow) sbgpu_plan();
+   if (!p) return fail(SBGPU_ENOMEM, "sbgpu_plan_create: out of host memory");
+   p->ctx = c;
    const bool timing = std::getenv("SBGPU_HOST_TIMING") != nullptr; // diagnostic: stage times on stderr
    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
    double t_stage = now();
@@ -772,7 +763,8 @@ int sbgpu_plan_create(sbgpu_ctx_t *c, int64_t n_loci, const int64_t *row_off, co
          t_stage = t;
       }
    };
-   int rc = sb::build_host_plan(n_loci, row_off, iso_off, f_off, c->n_cu, tune, &p->host, &err);
+   const char *err = "";
+   const int rc = sb::build_host_plan(n_loci, row_off, iso_off, f_off, c->n_cu, plan_tuning_from_env(), &p->host, &err);
    stage("size classes");
    if (rc != SBGPU_OK) {
       delete p;
@@ -786,212 +778,51 @@ int sbgpu_plan_create(sbgpu_ctx_t *c, int64_t n_loci, const int64_t *row_off, co
    };
    hipError_t e = hipSetDevice(c->device);
    if (e != hipSuccess) return bail(e, "hipSetDevice");
-   const size_t nb = (size_t)(n_loci + 1) * sizeof(int64_t);
-   // ---- wide loci: the streaming class is served by the multi-workgroup kernel wherever a locus' rows fit
-   // into n_cu workgroups; such loci move to the front of the class list, the rest keeps the streaming kernel
-   std::vector<sb::WideDesc> wide_table;
-   size_t wide_buf_doubles = 0;
-   for (sb::SizeClass &sc : p->host.classes) {
-      if (sc.kind != sb::kStream) continue;
-      // (workgroups, locus): a round's time is its slowest locus', and an iteration costs the more the more
-      // workgroups exchange partials, so loci of like workgroup counts share rounds: largest first
-      std::vector<std::pair<int, int32_t>> wide;
-      std::vector<int32_t> rest;
-      // a locus' layout is the one that serves it with the fewest workgroups (em_wide.h: 16 / 32 / 64 column lanes x
-      // 4-8 columns; rows per workgroup = register rows + LDS rows); the rows are then dealt evenly
-      auto groups_of = [&](int32_t l, int &layout) -> int64_t {
-         const int64_t nrow = row_off[l + 1] - row_off[l], niso = iso_off[l + 1] - iso_off[l];
-         layout = sb::wide_layout_for(niso, nrow);
-         if (layout < 0) return -1;
-         const int64_t rpb = sb::wide_rows_per_block(layout);
-         return std::max<int64_t>(1, (nrow + rpb - 1) / rpb);
-      };
-      // (read per plan, not cached: a test that sets it after an earlier plan must get the streaming kernel)
-      const bool no_wide = std::getenv("SBGPU_NO_WIDE") != nullptr;
-      for (int32_t l : sc.loci) {
-         int layout;
-         const int64_t G = groups_of(l, layout);
-         if (G > 0 && G <= c->n_cu && row_off[l + 1] > row_off[l] && !no_wide) wide.emplace_back((int)G, l);
-         else rest.push_back(l);
-      }
-      std::stable_sort(wide.begin(), wide.end(), [](const std::pair<int, int32_t> &x, const std::pair<int, int32_t> &y) { return x.first > y.first; });
-      sc.loci.clear();
-      // Rounds: every launch holds at most n_cu workgroups, all resident.  First fit, most workgroups first: a locus goes
-      // to the first round that has room (a round is as long as its slowest locus, and a locus of fewer workgroups is never
-      // slower than one of more: filling the gaps of the early rounds with small loci costs nothing and can save the last,
-      // mostly empty launch).  A round's descriptors are consecutive in the table, ordered by their first workgroup.
-      std::vector<std::vector<std::pair<int, int32_t>>> members;
-      std::vector<int> used;
-      for (const auto &gl : wide) {
-         size_t r = 0;
-         while (r < used.size() && used[r] + gl.first > c->n_cu) ++r;
-         if (r == used.size()) {
-            used.push_back(0);
-            members.emplace_back();
-         }
-         used[r] += gl.first;
-         members[r].push_back(gl);
-      }
-      for (size_t r = 0; r < members.size(); ++r) {
-         sbgpu_plan::WideRound round;
-         round.first_desc = (int)wide_table.size();
-         for (const auto &gl : members[r]) {
-            const int32_t l = gl.second;
-            const int G = gl.first;
-            const int64_t nrow = row_off[l + 1] - row_off[l];
-            int layout;
-            (void)groups_of(l, layout);
-            sb::WideDesc d;
-            d.locus = l;
-            d.first_block = round.n_blocks;
-            d.n_blocks = G;
-            d.rows_per_block = (int32_t)std::max<int64_t>(1, (nrow + G - 1) / G);
-            d.npad = sb::wide_cols(layout);
-            d.buf_off = (int64_t)wide_buf_doubles;
-            d.layout = layout;
-            d.lb_slice = sb::wide_lb_slice(d.npad, G);
-            d.pad_ = 0;
-            wide_buf_doubles += (size_t)4 * G * d.npad + (size_t)4 * d.npad; // two buffers of G x npad 16-byte granules (partials) + two of npad (totals)
-            round.n_blocks += G;
-            round.n_desc += 1;
-            round.lds_bytes = std::max(round.lds_bytes, sb::wide_lds_bytes(layout));
-            wide_table.push_back(d);
-            sc.loci.push_back(l);
-         }
-         p->wide_rounds.push_back(round);
-      }
-      p->n_wide_loci = (int32_t)sc.loci.size();
-      sc.loci.insert(sc.loci.end(), rest.begin(), rest.end());
-      sc.n_blocks = (int)rest.size(); // what is left for the streaming kernel
-   }
-   p->n_wide_desc = (int32_t)wide_table.size();
-   const size_t ncls = p->host.classes.size();
-   const size_t ncls_alloc = ncls + 1;
-   const size_t nlat = p->host.lat.size();
-   int64_t n_phased = 0; // loci of the phased wave kind = capacity of every later phase's lists
-   if (nlat)
-      for (int32_t cap : p->host.lat[0].capacity) n_phased += cap;
-   // ---- one device arena; its head (offsets, class lists, tables, class sizes) is staged on the host
-   // and uploaded with a single copy, the rest is workspace
-   auto up = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
-   size_t at = 0;
-   const size_t o_row = at; at += up(nb);
-   const size_t o_iso = at; at += up(nb);
-   const size_t o_f = at; at += up(nb);
-   const size_t o_loci = at; at += up((size_t)(n_loci + 1) * sizeof(int32_t));
-   const size_t o_tab = at; at += up(ncls_alloc * sizeof(sb::ClassDesc));
-   const size_t o_cn = at; at += up(ncls_alloc * sizeof(int32_t));
-   const size_t o_wtab = at; at += up((wide_table.size() + 1) * sizeof(sb::WideDesc));
-   std::vector<size_t> o_ltab(nlat), o_lroute(nlat), o_lcnt(nlat), o_ltot(nlat), o_llist(nlat);
-   for (size_t i = 0; i < nlat; ++i) {
-      o_ltab[i] = at; at += up((p->host.lat[i].classes.size() + 1) * sizeof(sb::ClassDesc));
-      o_lroute[i] = at; at += up((size_t)(n_loci + 1) * sizeof(int32_t));
-   }
-   const size_t o_tick = at; at += up(sizeof(unsigned)); // (zero: it goes up with the staged head)
-   const size_t staged = at;
-   // zeroed before every run: every later phase's survivor counts and batch total
-   const size_t o_cur = at;
-   for (size_t i = 0; i < nlat; ++i) {
-      o_lcnt[i] = at; at += up((p->host.lat[i].classes.size() + 1) * sizeof(int32_t));
-      o_ltot[i] = at; at += up(sizeof(int32_t));
-   }
-   p->zero_bytes = at - o_cur;
-   for (size_t i = 0; i < nlat; ++i) {
-      o_llist[i] = at; at += up((size_t)(n_phased + 1) * sizeof(int32_t));
-   }
-   const size_t o_keep = at; at += up((size_t)p->host.n_rows + 1);
-   const size_t o_sum = at; at += up((size_t)(n_loci + 1) * sizeof(double));
-   const size_t o_wbuf = at; at += up((wide_buf_doubles + 1) * sizeof(double));
-   if ((e = sb::dev_take(at, &p->d_arena, &p->arena_cap)) != hipSuccess) return bail(e, "hipMalloc(plan arena)");
+   // the wide loci's rounds (read per plan, not cached: a test that sets it after an earlier plan must get the streaming kernel)
+   const bool no_wide = std::getenv("SBGPU_NO_WIDE") != nullptr;
+   sb::WidePacking wide = sb::pack_wide_rounds(&p->host, row_off, iso_off, c->n_cu, no_wide);
+   // one device arena; its head is staged on the host and uploaded with a single copy, the rest is workspace
+   const sb::PlanLayout L = sb::plan_arena_layout(p->host, wide.table.size(), wide.buf_doubles);
+   if ((e = sb::dev_take(L.bytes, &p->d_arena, &p->arena_cap)) != hipSuccess) return bail(e, "hipMalloc(plan arena)");
    stage("hipMalloc");
-   p->d_row_off = (int64_t *)(p->d_arena + o_row);
-   p->d_iso_off = (int64_t *)(p->d_arena + o_iso);
-   p->d_f_off = (int64_t *)(p->d_arena + o_f);
-   p->d_loci_all = (int32_t *)(p->d_arena + o_loci);
-   p->d_tables = (sb::ClassDesc *)(p->d_arena + o_tab);
-   p->d_class_n = (int32_t *)(p->d_arena + o_cn);
-   p->d_zero = p->d_arena + o_cur;
-   p->lat.resize(nlat);
-   for (size_t i = 0; i < nlat; ++i) {
-      sbgpu_plan::LatDev &ld = p->lat[i];
+   std::vector<char> head(L.staged, 0);
+   sb::PlanHead staged = sb::stage_plan_head(p->host, L, row_off, iso_off, f_off, wide.table, head.data());
+   stage("staging");
+   if ((e = hipMemcpy(p->d_arena, head.data(), L.staged, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(plan)");
+   // the wide kernel's exchange granules carry a per-run tag: start from a state no tag matches
+   if (wide.buf_doubles && (e = hipMemset(p->d_arena + L.wide_bufs, 0, wide.buf_doubles * sizeof(double))) != hipSuccess) return bail(e, "hipMemset(plan)");
+   stage("upload");
+   char *const A = p->d_arena;
+   p->d_row_off = (int64_t *)(A + L.row_off), p->d_iso_off = (int64_t *)(A + L.iso_off), p->d_f_off = (int64_t *)(A + L.f_off);
+   p->d_loci_all = (int32_t *)(A + L.loci);
+   p->d_tables = (sb::ClassDesc *)(A + L.tables);
+   p->d_class_n = (int32_t *)(A + L.class_n);
+   p->d_wide_table = (sb::WideDesc *)(A + L.wide_table);
+   p->d_epi_ticket = (unsigned *)(A + L.epi_ticket);
+   p->d_zero = A + L.zero, p->zero_bytes = L.zero_bytes;
+   p->d_row_keep = (uint8_t *)(A + L.row_keep);
+   p->d_locus_sum = (double *)(A + L.locus_sum);
+   p->d_wide_bufs = (double *)(A + L.wide_bufs);
+   for (size_t i = 0; i < p->host.lat.size(); ++i) {
       const sb::LatPhase &lp = p->host.lat[i];
-      ld.d_table = (sb::ClassDesc *)(p->d_arena + o_ltab[i]);
-      ld.d_route = (int32_t *)(p->d_arena + o_lroute[i]);
-      ld.d_counts = (int32_t *)(p->d_arena + o_lcnt[i]);
-      ld.d_total = (int32_t *)(p->d_arena + o_ltot[i]);
-      ld.d_lists = (int32_t *)(p->d_arena + o_llist[i]);
-      ld.n_classes = (int)lp.classes.size();
-      ld.it_limit = lp.it_limit;
-      ld.repack = lp.repack;
+      const sb::PlanLatLayout &ll = L.lat[i];
+      sbgpu_plan::LatDev ld;
+      ld.d_table = (sb::ClassDesc *)(A + ll.table);
+      ld.d_route = (int32_t *)(A + ll.route), ld.d_counts = (int32_t *)(A + ll.counts);
+      ld.d_total = (int32_t *)(A + ll.total), ld.d_lists = (int32_t *)(A + ll.lists);
+      ld.n_classes = (int)lp.classes.size(), ld.it_limit = lp.it_limit, ld.repack = lp.repack;
       // every batch gets a wave of its own up to 32768 waves; beyond that the waves stride over the batches
       ld.grid = (int)std::min<int64_t>(std::max<int64_t>(lp.max_blocks, 1), 32768);
+      p->lat.push_back(ld);
    }
-   p->d_row_keep = (uint8_t *)(p->d_arena + o_keep);
-   p->d_locus_sum = (double *)(p->d_arena + o_sum);
-   p->d_epi_ticket = (unsigned *)(p->d_arena + o_tick);
-   p->d_wide_table = (sb::WideDesc *)(p->d_arena + o_wtab);
-   p->d_wide_bufs = (double *)(p->d_arena + o_wbuf);
-   std::vector<char> stage_buf(staged, 0);
-   if (n_loci > 0) {
-      std::memcpy(stage_buf.data() + o_row, row_off, nb);
-      std::memcpy(stage_buf.data() + o_iso, iso_off, nb);
-      std::memcpy(stage_buf.data() + o_f, f_off, nb);
-   }
-   int32_t *h_loci = (int32_t *)(stage_buf.data() + o_loci);
-   sb::ClassDesc *table = (sb::ClassDesc *)(stage_buf.data() + o_tab);
-   int32_t *h_cn = (int32_t *)(stage_buf.data() + o_cn);
-   if (!wide_table.empty()) std::memcpy(stage_buf.data() + o_wtab, wide_table.data(), wide_table.size() * sizeof(sb::WideDesc));
-   for (size_t i = 0; i < nlat; ++i) {
-      const sb::LatPhase &lp = p->host.lat[i];
-      sb::ClassDesc *lt = (sb::ClassDesc *)(stage_buf.data() + o_ltab[i]);
-      int32_t loff = 0;
-      for (size_t ci = 0; ci < lp.classes.size(); ++ci) {
-         const sb::SizeClass &sc = lp.classes[ci];
-         lt[ci].block_begin = 0; // phase_prepare_kernel fills it from the survivor counts
-         lt[ci].n = lp.capacity[ci];
-         lt[ci].loci_off = loff;
-         lt[ci].shape = sc.layout | (sc.rmult << 8) | (sc.lbG << 16);
-         loff += lp.capacity[ci];
-      }
-      std::memcpy(stage_buf.data() + o_lroute[i], lp.route.data(), lp.route.size() * sizeof(int32_t));
-   }
-   size_t off = 0;
-   size_t max_stream_iso = 0;
-   for (int k = 0; k < sb::kNumKinds; ++k) p->launches[k] = KindLaunch();
-   for (size_t ci = 0; ci < ncls; ++ci) {
-      const sb::SizeClass &sc = p->host.classes[ci];
-      KindLaunch &kl = p->launches[sc.kind];
-      if (kl.n_classes == 0) {
-         kl.first_class = (int)ci;
-         kl.d_table = p->d_tables + ci;
-         kl.block_threads = sc.block_threads;
-      }
-      table[ci].block_begin = kl.n_blocks;
-      table[ci].n = (int32_t)sc.loci.size();
-      table[ci].loci_off = (int32_t)off;
-      table[ci].shape = sc.layout | (sc.rmult << 8) | (sc.lbG << 16);
-      h_cn[ci] = table[ci].n;
-      kl.n_blocks += sc.n_blocks;
-      kl.n_classes += 1;
-      std::memcpy(h_loci + off, sc.loci.data(), sc.loci.size() * sizeof(int32_t));
-      p->loci_off.push_back((int64_t)off);
-      off += sc.loci.size();
-      if (sc.kind == sb::kStream) {
-         for (int32_t l : sc.loci) {
-            size_t k = (size_t)(iso_off[l + 1] - iso_off[l]);
-            if (k > max_stream_iso) max_stream_iso = k;
-         }
-      }
-   }
-   stage("staging");
-   if ((e = hipMemcpy(p->d_arena, stage_buf.data(), staged, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(plan)");
-   // the wide kernel's exchange granules carry a per-run tag: start from a state no tag matches
-   if (wide_buf_doubles && (e = hipMemset(p->d_wide_bufs, 0, wide_buf_doubles * sizeof(double))) != hipSuccess) return bail(e, "hipMemset(plan)");
-   stage("upload");
+   for (int k = 0; k < sb::kNumKinds; ++k) p->launches[k] = staged.launches[k];
+   p->loci_off = std::move(staged.loci_off);
+   p->wide_rounds = std::move(wide.rounds);
+   p->n_wide_desc = (int32_t)wide.table.size(), p->n_wide_loci = wide.n_wide_loci;
    // streaming kernel LDS: (3 + NWAVE) * npad doubles, npad <= pow2ceil-padded niso
    size_t npad = 1;
-   while (npad < max_stream_iso && npad < 64) npad <<= 1;
-   if (max_stream_iso > 64) npad = 64 * ((max_stream_iso + 63) / 64);
+   while (npad < staged.max_stream_iso && npad < 64) npad <<= 1;
+   if (staged.max_stream_iso > 64) npad = 64 * ((staged.max_stream_iso + 63) / 64);
    p->stream_lds_bytes = (3 + sb::kStreamThreads / 64) * npad * sizeof(double);
    *plan_out = p;
    return SBGPU_OK;
@@ -1029,7 +860,6 @@ int sbgpu_plan_classes(const sbgpu_plan_t *p, int64_t *out, int cap)
 
 } // extern "C"
 
-// fp64 (the product path) and fp32 (BASELINE config 5's tolerance sweep) share the launch structure
 // A side stream whose kernels run BESIDE those of the three streams the kinds use (0, 2, 6): four 200 us holds, one per stream,
 // take ~200 us together when the candidate has a hardware queue of its own and ~400 when it shares one (HIP folds a process'
 // streams onto 4 queues by creation order; which one a stream got cannot be asked).  0: none found.
@@ -1050,6 +880,52 @@ static int find_wave_alt(sbgpu_ctx_t *c)
    return 0;
 }
 
+// fp64 (the product path) and fp32 (BASELINE config 5's tolerance sweep) share the launch structure
+template <class T>
+static sb::EmArgsT<T> em_args(const sbgpu_plan_t *p, const int32_t *d_count, const void *d_F, void *d_theta, int32_t *d_status, int32_t *d_iters,
+                              const void *d_row_bias, const void *d_iso_bias)
+{
+   sb::EmArgsT<T> a;
+   a.row_off = p->d_row_off, a.iso_off = p->d_iso_off, a.f_off = p->d_f_off;
+   a.count = d_count, a.F = (const T *)d_F, a.theta = (T *)d_theta, a.status = d_status, a.iters = d_iters;
+   a.row_bias = (const T *)d_row_bias, a.iso_bias = (const T *)d_iso_bias;
+   return a;
+}
+
+// What the launch of one phase of a kind needs besides the batch.  i < 0: phase 0 (the host's tables and batch counts);
+// else later phase i (tables and counts made on the device).  `to`: the phase its survivors continue in, null: it runs them out.
+static sb::PhaseArgs phase_args(const sbgpu_plan_t *p, const sb::KindLaunch &kl, int i, const sbgpu_plan::LatDev *to, int it_limit)
+{
+   const sbgpu_plan::LatDev *ld = i < 0 ? nullptr : &p->lat[(size_t)i];
+   sb::PhaseArgs ph;
+   ph.table = ld ? ld->d_table : p->d_tables + kl.first_class;
+   ph.n_classes = ld ? ld->n_classes : kl.n_classes;
+   ph.lists_in = ld ? ld->d_lists : p->d_loci_all;
+   ph.n_in = ld ? ld->d_counts : p->d_class_n + kl.first_class;
+   ph.n_batches = ld ? 0 : kl.n_blocks;
+   ph.total_blocks = ld ? ld->d_total : nullptr;
+   ph.lists_out = to ? to->d_lists : nullptr;
+   ph.n_out = to ? to->d_counts : nullptr;
+   ph.route = to ? to->d_route : nullptr;
+   ph.next_table = to ? to->d_table : nullptr;
+   ph.it_limit = it_limit;
+   ph.resume = ld ? 1 : 0;
+   return ph;
+}
+
+static hipError_t launch_fused(int kind, const sb::FusedLaunch &l, hipStream_t s)
+{
+   switch (kind) {
+   case sb::kWaveH: return sb::launch_fused_wave_h(l, s);
+   case sb::kWave1: return sb::launch_fused_wave_1(l, s);
+   case sb::kWave2: return sb::launch_fused_wave_2(l, s);
+   case sb::kBlock: return sb::launch_fused_block(l, s);
+   case sb::kBlockTall: return sb::launch_fused_block_tall(l, s);
+   default: return hipErrorInvalidValue;
+   }
+}
+
+// Validate, schedule (em_schedule.h: every decision about streams, order, holds and waits), issue.
 static int em_run_impl(sbgpu_ctx_t *c, const sbgpu_plan_t *p, const int32_t *d_count, const void *d_F_any, void *d_theta_any,
                        int32_t *d_status, int32_t *d_iters, void *stream, const bool f32, const void *d_row_bias = nullptr,
                        const void *d_iso_bias = nullptr, void *join_stream = nullptr)
@@ -1063,108 +939,68 @@ static int em_run_impl(sbgpu_ctx_t *c, const sbgpu_plan_t *p, const int32_t *d_c
    if ((d_row_bias != nullptr) != (d_iso_bias != nullptr)) return fail(SBGPU_EINVAL, "sbgpu_em_run_device_bias: both bias arrays or none");
    // the bias factors are applied where a kernel loads its tile: the tile kernels and, round 5, the multi-workgroup kernel
    // of the wide loci; the streaming fallback (more than n_cu workgroups, or no rows) and the later phases do not
-   bool stream_fallback = false;
-   if (p->launches[sb::kStream].n_classes > 0)
-      stream_fallback = (int32_t)p->host.classes[p->launches[sb::kStream].first_class].loci.size() > p->n_wide_loci;
-   if (d_row_bias && (stream_fallback || !p->lat.empty()))
+   const sb::KindLaunch &stream_kind = p->launches[sb::kStream];
+   const int32_t n_streamed = stream_kind.n_classes > 0 ? (int32_t)p->host.classes[stream_kind.first_class].loci.size() - p->n_wide_loci : 0;
+   if (d_row_bias && (n_streamed > 0 || !p->lat.empty()))
       return fail(SBGPU_EUNSUPPORTED, "sbgpu_em_run_device_bias: the bias factors are applied at tile load (tile kernels and the wide-locus kernel: "
                                       "no locus on the streaming fallback, no phases)");
-   hipStream_t main = (hipStream_t)stream;
-   sb::EmArgs a;
-   a.row_bias = f32 ? nullptr : (const double *)d_row_bias;
-   a.iso_bias = f32 ? nullptr : (const double *)d_iso_bias;
-   a.row_off = p->d_row_off;
-   a.iso_off = p->d_iso_off;
-   a.f_off = p->d_f_off;
-   a.count = d_count;
-   a.F = (const double *)d_F_any;
-   a.theta = (double *)d_theta_any;
-   a.status = d_status;
-   a.iters = d_iters;
-   sb::EmArgsT<float> a32;
-   a32.row_off = a.row_off, a32.iso_off = a.iso_off, a32.f_off = a.f_off, a32.count = a.count;
-   a32.F = (const float *)d_F_any, a32.theta = (float *)d_theta_any, a32.status = d_status, a32.iters = d_iters;
-   a32.row_bias = f32 ? (const float *)d_row_bias : nullptr, a32.iso_bias = f32 ? (const float *)d_iso_bias : nullptr;
-   // Batches are dealt to the workgroups statically: nothing to reset between runs but the later phases' survivor
-   // counts (only when the plan has phases)
-   // (split runs: a plan with per-run state of its own -- the phases' survivor counts, the wide loci's barrier words -- must
-   // not start while the previous run's kernels still use it: such a plan's runs wait for each other as the unsplit ones do)
-   if (join_stream && (p->zero_bytes || p->n_wide_desc))
-      for (int k = 0; k < sb::kNumKinds; ++k)
-         if (p->launches[k].n_classes > 0) HIP_TRY(hipStreamWaitEvent(main, c->join[k], 0));
-   if (p->zero_bytes) HIP_TRY(hipMemsetAsync(p->d_zero, 0, p->zero_bytes, main));
-   // a locus the kernels never reach (a wide-locus barrier that timed out) must not look solved: with wide loci in
-   // the plan, status starts at -1 = SBGPU_EM_UNSOLVED (0xFF bytes); every other kernel writes all its loci
-   if (p->n_wide_desc) HIP_TRY(hipMemsetAsync(d_status, 0xFF, (size_t)p->host.n_loci * sizeof(int32_t), main));
-   // one launch per kind (wave / block / stream); a single kind runs on the
-   // caller's stream, several fork onto the aux streams and join back
-   int kinds = 0;
-   for (int k = 0; k < sb::kNumKinds; ++k) kinds += p->launches[k].n_classes > 0;
-   const bool fork = kinds > 1;
-   // SBGPU_WAVE_ON_MAIN=1: the wave kinds (stream slot 0: the kinds that end last) run on the caller's stream itself, so
-   // that neither their start nor the epilogue behind them waits for an event to cross hardware queues; the other
-   // kinds fork off and join as before
-   static const bool wave_on_main = sb::exp_env("SBGPU_WAVE_ON_MAIN") && std::atoi(sb::exp_env("SBGPU_WAVE_ON_MAIN")) != 0;
-   // Split runs alternate the wave kinds (the kinds that end last) between two streams on two hardware queues: the next run's
-   // wave kernel -- its longest loci first -- starts while this run's last workgroups still work through theirs, instead of
-   // behind them (C3: 0.76 -> 0.72 ms per step; a second stream that shares a hardware queue with the first one or with the
-   // block kinds': 0.79).  Which stream that is depends on how the runtime folded the process' streams onto its hardware queues:
-   // it is looked for once (find_wave_alt), and without one the runs do not alternate.
+
+   // ---- the schedule
+   sb::EmScheduleIn in;
+   for (int k = 0; k < sb::kNumKinds; ++k) in.present[k] = p->launches[k].n_classes > 0;
+   in.per_run_state = p->zero_bytes || p->n_wide_desc;
+   in.wide_rounds = p->n_wide_desc > 0;
+   in.split = join_stream != nullptr;
+   // Which side stream a split run's wave kinds alternate with depends on how the runtime folded the process' streams onto its
+   // hardware queues: it is looked for once (find_wave_alt), and without one the runs do not alternate.
    // SBGPU_WAVE_ALT (experiments): 0 = no alternation, 1..7 = that side stream, unset = the probe's choice (tests pin each schedule)
-   if (join_stream && fork && c->wave_alt < 0) {
+   if (in.split && sb::em_forks(in.present) && c->wave_alt < 0) {
       const char *forced = sb::exp_env("SBGPU_WAVE_ALT");
       c->wave_alt = forced ? std::max(0, std::min(7, std::atoi(forced))) : find_wave_alt(c);
       if (std::getenv("SBGPU_HOST_TIMING"))
          std::fprintf(stderr, "[sbgpu] split runs: the wave kinds' second stream = %d (0: none)%s\n", c->wave_alt, forced ? " (SBGPU_WAVE_ALT)" : "");
    }
-   const int wave_slot = (join_stream && fork && c->wave_alt > 0 && !p->zero_bytes && !p->n_wide_desc && (c->split_runs++ & 1)) ? c->wave_alt : 0;
-   auto stream_of = [&](int k) -> hipStream_t {
-      if (!fork || (wave_on_main && kKindStream[k] == 0)) return main;
-      return c->aux[kKindStream[k] == 0 ? wave_slot : kKindStream[k]];
-   };
-   if (fork) {
+   in.wave_alt = c->wave_alt;
+   in.split_runs = c->split_runs;
+   const sb::EmSchedule sched = sb::em_schedule(in);
+   c->split_runs = sched.split_runs;
+
+   // ---- issue it
+   hipStream_t main = (hipStream_t)stream;
+   hipStream_t on[sb::kNumKinds] = {}; // a present kind's stream
+   for (int i = 0; i < sched.n_steps; ++i) on[sched.steps[i].kind] = sched.steps[i].slot < 0 ? main : c->aux[sched.steps[i].slot];
+   const sb::EmArgs a = em_args<double>(p, d_count, d_F_any, d_theta_any, d_status, d_iters, f32 ? nullptr : d_row_bias, f32 ? nullptr : d_iso_bias);
+   const sb::EmArgsT<float> a32 = em_args<float>(p, d_count, d_F_any, d_theta_any, d_status, d_iters, f32 ? d_row_bias : nullptr, f32 ? d_iso_bias : nullptr);
+   if (sched.wait_previous_run)
+      for (int k = 0; k < sb::kNumKinds; ++k)
+         if (in.present[k]) HIP_TRY(hipStreamWaitEvent(main, c->join[k], 0));
+   // Batches are dealt to the workgroups statically: nothing to reset between runs but the later phases' survivor
+   // counts (only when the plan has phases)
+   if (p->zero_bytes) HIP_TRY(hipMemsetAsync(p->d_zero, 0, p->zero_bytes, main));
+   // a locus the kernels never reach (a wide-locus barrier that timed out) must not look solved: with wide loci in
+   // the plan, status starts at -1 = SBGPU_EM_UNSOLVED (0xFF bytes); every other kernel writes all its loci
+   if (p->n_wide_desc) HIP_TRY(hipMemsetAsync(d_status, 0xFF, (size_t)p->host.n_loci * sizeof(int32_t), main));
+   if (sched.fork) {
       HIP_TRY(hipEventRecord(c->fork, main));
       for (int k = 0; k < sb::kNumKinds; ++k)
-         if (p->launches[k].n_classes > 0 && stream_of(k) != main) HIP_TRY(hipStreamWaitEvent(stream_of(k), c->fork, 0));
+         if (in.present[k] && on[k] != main) HIP_TRY(hipStreamWaitEvent(on[k], c->fork, 0));
    }
    for (int k = 0; k < sb::kNumKinds; ++k) c->timed[k] = false;
    c->n_phase_timed = 0;
    const bool timing = c->timing;
-   // longest iterations first: stream, block, wave
-   // The wide-locus rounds are cooperative launches that want the chip to themselves (one 512-lane workgroup with all
-   // of a CU's registers and up to 94 KB of its LDS per CU): beside the tile kinds' workgroups their residency is not
-   // assured and the rounds take twice as long (measured: C3-T 44 -> 79 ms).  They run when the tile kinds are done.
-   const bool wide_last = fork && p->n_wide_desc > 0;
-   for (int pass = 0; pass < 2; ++pass)
-   for (int k = sb::kNumKinds - 1; k >= 0; --k) {
-      const KindLaunch &kl = p->launches[k];
-      if (kl.n_classes == 0) continue;
-      if ((pass == 1) != (wide_last && k == sb::kStream)) continue; // pass 0: everything but a deferred stream kind
-      if (pass == 1) {
+   for (int i = 0; i < sched.n_steps; ++i) {
+      const sb::EmStep &st = sched.steps[i];
+      const int k = st.kind;
+      const sb::KindLaunch &kl = p->launches[k];
+      hipStream_t s = on[k];
+      if (st.after_others)
          for (int o = 0; o < sb::kNumKinds; ++o) {
-            if (o == k || p->launches[o].n_classes == 0) continue;
-            HIP_TRY(hipEventRecord(c->join[o], stream_of(o)));
-            HIP_TRY(hipStreamWaitEvent(stream_of(k), c->join[o], 0));
+            if (o == k || !in.present[o]) continue;
+            HIP_TRY(hipEventRecord(c->join[o], on[o]));
+            HIP_TRY(hipStreamWaitEvent(s, c->join[o], 0));
          }
-      }
-      hipStream_t s = stream_of(k);
-      // Start order.  A tall-tile workgroup needs a whole CU's registers, a block-kind one half of them: once the
-      // workgroups of a lighter kind have spread over the chip, a heavier one waits for a CU to drain -- the 9
-      // tall workgroups of C3 then finish at 1.48 ms instead of 0.65 ms, behind everything else (they start within a
-      // few microseconds of the block kind, in either order).  So every kind is held back a few microseconds behind
-      // the next heavier one: tall, block (+SBGPU_BLOCK_DELAY_US), wave (+SBGPU_WAVE_DELAY_US more); 0 = off.
-      // C3: 1.49 -> 1.45 ms per step with the wave delay at 5 (no better at 10-40).
-      static const int wave_delay_us = sb::exp_env("SBGPU_WAVE_DELAY_US") ? std::atoi(sb::exp_env("SBGPU_WAVE_DELAY_US")) : 5;
-      static const int block_delay_us = sb::exp_env("SBGPU_BLOCK_DELAY_US") ? std::atoi(sb::exp_env("SBGPU_BLOCK_DELAY_US")) : 5;
-      const bool tall_runs = p->launches[sb::kBlockTall].n_classes > 0;
-      int hold_us = 0;
-      if (fork && k == sb::kBlock && tall_runs) hold_us = block_delay_us;
-      if (fork && kKindStream[k] == 0) hold_us = wave_delay_us + ((tall_runs && p->launches[sb::kBlock].n_classes > 0) ? block_delay_us : 0);
-      // (split runs: a kind's kernels follow each other on its stream, run after run, and the kinds drift apart by themselves --
-      // the hold would only sit on the path of the kind that ends last)
-      if (join_stream && !(p->zero_bytes || p->n_wide_desc)) hold_us = 0;
-      if (hold_us > 0) {
-         hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(64), 0, s, (unsigned long long)hold_us * 100ull);
+      if (st.hold_us > 0) {
+         hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(64), 0, s, (unsigned long long)st.hold_us * 100ull);
          HIP_TRY(hipGetLastError());
       }
       if (timing) HIP_TRY(hipEventRecord(c->t0[k], s));
@@ -1178,7 +1014,7 @@ static int em_run_impl(sbgpu_ctx_t *c, const sbgpu_plan_t *p, const int32_t *d_c
             // registers), its loci run the same number of exchanges give or take, and a cooperative launch is only
             // promised residency on an otherwise free device -- two rounds in flight could both end up half resident
             // and spin in their exchanges until the timeout.
-            for (const sbgpu_plan::WideRound &r : p->wide_rounds) {
+            for (const sb::WideRound &r : p->wide_rounds) {
                sb::WideArgs wa;
                wa.a = a;
                wa.table = p->d_wide_table + r.first_desc;
@@ -1189,74 +1025,30 @@ static int em_run_impl(sbgpu_ctx_t *c, const sbgpu_plan_t *p, const int32_t *d_c
                HIP_TRY(sb::launch_wide(wa, r.n_blocks, r.lds_bytes, s));
             }
          }
-         const int32_t n_all = (int32_t)p->host.classes[kl.first_class].loci.size();
-         if (n_all > p->n_wide_loci) { // the rest: one workgroup per locus, F streamed from L2
+         if (n_streamed > 0) { // the rest: one workgroup per locus, F streamed from L2
             sb::ClassArgs ca = {};
             ca.loci = p->d_loci_all + p->loci_off[kl.first_class] + p->n_wide_loci;
-            ca.n = n_all - p->n_wide_loci;
+            ca.n = n_streamed;
             ca.batch = 0;
             HIP_TRY(sb::launch_stream(a, ca, p->d_row_keep, ca.n, p->stream_lds_bytes, s));
          }
       } else {
          const bool wave_kind = k == sb::kWaveH || k == sb::kWave1 || k == sb::kWave2;
-         const bool phased = wave_kind && !p->lat.empty() && !f32;
-         sb::FusedLaunch fl;
-         fl.a = a;
-         fl.ph.table = kl.d_table;
-         fl.ph.n_classes = kl.n_classes;
-         fl.ph.lists_in = p->d_loci_all;
-         fl.ph.n_in = p->d_class_n + kl.first_class;
-         fl.ph.n_batches = kl.n_blocks;
-         fl.ph.total_blocks = nullptr;
-         fl.ph.lists_out = phased ? p->lat[0].d_lists : nullptr;
-         fl.ph.n_out = phased ? p->lat[0].d_counts : nullptr;
-         fl.ph.route = phased ? p->lat[0].d_route : nullptr;
-         fl.ph.next_table = phased ? p->lat[0].d_table : nullptr;
-         fl.ph.it_limit = phased ? p->host.first_limit : SBGPU_EM_MAX_ITER;
-         fl.ph.resume = 0;
-         fl.n_blocks = std::max(1, (int)(kl.n_blocks * p->host.grid_scale + 0.5));
-         hipError_t e = hipErrorInvalidValue;
-         if (f32) {
-            sb::FusedLaunchF32 f;
-            f.a = a32, f.ph = fl.ph, f.n_blocks = fl.n_blocks;
-            e = sb::launch_fused_f32(k, f, s);
-         } else if (k == sb::kWaveH) e = sb::launch_fused_wave_h(fl, s);
-         else if (k == sb::kWave1) e = sb::launch_fused_wave_1(fl, s);
-         else if (k == sb::kWave2) e = sb::launch_fused_wave_2(fl, s);
-         else if (k == sb::kBlock) e = sb::launch_fused_block(fl, s);
-         else if (k == sb::kBlockTall) e = sb::launch_fused_block_tall(fl, s);
-         HIP_TRY(e);
+         const size_t n_later = (wave_kind && !f32) ? p->lat.size() : 0; // later phases: the wave kind's, fp64 only
+         const sb::PhaseArgs ph0 = phase_args(p, kl, -1, n_later ? &p->lat[0] : nullptr, n_later ? p->host.first_limit : SBGPU_EM_MAX_ITER);
+         const int n_blocks = std::max(1, (int)(kl.n_blocks * p->host.grid_scale + 0.5));
+         HIP_TRY(f32 ? sb::launch_fused_f32(k, sb::FusedLaunchF32{a32, ph0, n_blocks}, s) : launch_fused(k, sb::FusedLaunch{a, ph0, n_blocks}, s));
          // later phases: the loci still running continue in lane-rich layouts; a one-workgroup kernel turns the
          // survivor counts into the next launch's block table in between
-         for (size_t i = 0; phased && i < p->lat.size(); ++i) {
-            const sbgpu_plan::LatDev &ld = p->lat[i];
-            const bool last = i + 1 == p->lat.size();
-            if (timing && i < (size_t)kMaxPhaseEvents) HIP_TRY(hipEventRecord(c->tp[i], s));
+         for (size_t j = 0; j < n_later; ++j) {
+            const sbgpu_plan::LatDev &ld = p->lat[j];
+            if (timing && j < (size_t)kMaxPhaseEvents) HIP_TRY(hipEventRecord(c->tp[j], s));
             HIP_TRY(sb::launch_phase_prepare(ld.d_table, ld.d_counts, ld.n_classes, ld.d_total, s));
-            sb::FusedLaunch ll;
-            ll.a = a;
-            ll.ph.table = ld.d_table;
-            ll.ph.n_classes = ld.n_classes;
-            ll.ph.lists_in = ld.d_lists;
-            ll.ph.n_in = ld.d_counts;
-            ll.ph.n_batches = 0;
-            ll.ph.total_blocks = ld.d_total;
-            ll.ph.lists_out = last ? nullptr : p->lat[i + 1].d_lists;
-            ll.ph.n_out = last ? nullptr : p->lat[i + 1].d_counts;
-            ll.ph.route = last ? nullptr : p->lat[i + 1].d_route;
-            ll.ph.next_table = last ? nullptr : p->lat[i + 1].d_table;
-            ll.ph.it_limit = ld.it_limit;
-            ll.ph.resume = 1;
-            ll.n_blocks = ld.grid;
-            hipError_t el = hipErrorInvalidValue;
-            if (!ld.repack) el = sb::launch_lat(ll, s);
-            else if (k == sb::kWaveH) el = sb::launch_fused_wave_h(ll, s);
-            else if (k == sb::kWave1) el = sb::launch_fused_wave_1(ll, s);
-            else el = sb::launch_fused_wave_2(ll, s);
-            HIP_TRY(el);
-            if (timing) c->n_phase_timed = (int)std::min<size_t>(i + 1, kMaxPhaseEvents);
+            const sb::FusedLaunch later{a, phase_args(p, kl, (int)j, j + 1 < n_later ? &p->lat[j + 1] : nullptr, ld.it_limit), ld.grid};
+            HIP_TRY(ld.repack ? launch_fused(k, later, s) : sb::launch_lat(later, s));
+            if (timing) c->n_phase_timed = (int)std::min<size_t>(j + 1, kMaxPhaseEvents);
          }
-         if (timing && phased && p->lat.size() <= (size_t)kMaxPhaseEvents) HIP_TRY(hipEventRecord(c->tp[p->lat.size()], s));
+         if (timing && n_later && n_later <= (size_t)kMaxPhaseEvents) HIP_TRY(hipEventRecord(c->tp[n_later], s));
       }
       if (timing) {
          HIP_TRY(hipEventRecord(c->t1[k], s));
@@ -1264,13 +1056,13 @@ static int em_run_impl(sbgpu_ctx_t *c, const sbgpu_plan_t *p, const int32_t *d_c
       }
    }
    // the kinds' streams join the caller's -- or, sbgpu_em_run_device_split, ANOTHER stream of the caller's (the one its epilogue
-   // runs on), so that the stream the next run forks from does not wait for this one's kernels
+   // runs on), so that the stream the next run forks from does not wait for this one's kernels.  (Stream handles are compared,
+   // not slots: the caller may pass any stream, one of the context's side streams included.)
    hipStream_t join_to = join_stream ? (hipStream_t)join_stream : main;
-   if (fork) {
+   if (sched.fork) {
       for (int k = 0; k < sb::kNumKinds; ++k) {
-         if (p->launches[k].n_classes == 0) continue;
-         if (stream_of(k) == join_to) continue;
-         HIP_TRY(hipEventRecord(c->join[k], stream_of(k)));
+         if (!in.present[k] || on[k] == join_to) continue;
+         HIP_TRY(hipEventRecord(c->join[k], on[k]));
          HIP_TRY(hipStreamWaitEvent(join_to, c->join[k], 0));
       }
    } else if (join_to != main) {
@@ -1285,31 +1077,7 @@ extern "C" {
 int sbgpu_em_run_device(sbgpu_ctx_t *c, const sbgpu_plan_t *p, const int32_t *d_count, const double *d_F,
                         double *d_theta, int32_t *d_status, int32_t *d_iters, void *stream)
 {
-   static const bool use_graph = sb::exp_env("SBGPU_GRAPH") && std::atoi(sb::exp_env("SBGPU_GRAPH")) != 0;
-   if (!use_graph || !c || !p || c->timing || p->n_wide_desc) // (cooperative launches and timing events stay outside)
-      return em_run_impl(c, p, d_count, d_F, d_theta, d_status, d_iters, stream, false);
-   const void *key[6] = {d_count, d_F, d_theta, d_status, d_iters, stream};
-   if (!p->graph_exec || std::memcmp(key, p->graph_key, sizeof key) != 0) {
-      if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
-      p->graph_exec = nullptr;
-      hipGraph_t g = nullptr;
-      // captured on the context's own stream (the caller's may be the legacy default stream, which cannot capture);
-      // the graph is launched into the caller's
-      HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
-      const int rc = em_run_impl(c, p, d_count, d_F, d_theta, d_status, d_iters, c->stream, false);
-      const hipError_t e = hipStreamEndCapture(c->stream, &g);
-      if (rc != SBGPU_OK) {
-         if (g) (void)hipGraphDestroy(g);
-         return rc;
-      }
-      HIP_TRY(e);
-      const hipError_t ei = hipGraphInstantiate(&p->graph_exec, g, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(g);
-      HIP_TRY(ei);
-      std::memcpy(p->graph_key, key, sizeof key);
-   }
-   HIP_TRY(hipGraphLaunch(p->graph_exec, (hipStream_t)stream));
-   return SBGPU_OK;
+   return em_run_impl(c, p, d_count, d_F, d_theta, d_status, d_iters, stream, false);
 }
 
 int sbgpu_em_run_device_split(sbgpu_ctx_t *c, const sbgpu_plan_t *p, const int32_t *d_count, const double *d_F, double *d_theta,
