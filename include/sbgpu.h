@@ -1642,6 +1642,82 @@ int sbgpu_body_profile_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins, const 
  * bins and [7] the most isoforms of one locus.                                                                              */
 int sbgpu_body_profile_limits(int64_t out[8]);
 
+/* ---- splicing events: exon and junction inclusion (PSI) with intervals --------------------------------------
+ * For one annotated exon or one annotated intron: which share of the transcripts that run across it include it.  The event
+ * table is a function of the annotation alone (built once, on the host); the PSI of every event is a function of the table and
+ * of one abundance row.  The rule (csrc/splice_rules.h, shared by both forms, compiled under -ffp-contract=off).  For locus l
+ * with the isoforms j0 = iso_off[l] .. j1 - 1, isoform j's exons e = exon_off[j] .. exon_off[j+1] - 1, closed [L_e, R_e], ascending:
+ *   - EVENTS  an exon event is a distinct pair [L_e, R_e] among the locus' exons (kind 0); an intron event is a distinct pair
+ *     [R_e + 1, L_{e+1} - 1] between consecutive exons of one isoform (kind 1: the interval junction_mass of the isoform-resolved
+ *     coverage stands for), made only where R_e + 1 <= L_{e+1} - 1 (abutting exons make none).  A locus' events are ordered by
+ *     (left, right, kind) ascending; an exon and an intron of the same coordinates are two events.  Loci in annotation order:
+ *     event_off[n_loci + 1], event_locus[n_events].
+ *   - INCLUSION LIST  of event u, incl_off[u] .. incl_off[u+1] - 1: the isoforms that own that exon or intron, in ascending j;
+ *     incl_iso (int32): the isoform's index inside its locus; incl_exon (int64): the global index of that exon, or of the exon
+ *     upstream of the intron -- the index into exon_bases / junction_mass.  Two identical isoforms are two entries.
+ *   - SPAN  isoform j spans event [a, b] iff it has an exon and L_first(j) <= a and b <= R_last(j): iso_left[j] / iso_right[j]
+ *     hold the two (0xFFFFFFFF / 0 for an isoform without exons, which spans nothing); n_span[u] (int32) counts the spanning
+ *     isoforms whatever keep says.  No span list is kept; inclusion implies span.  n_incl == n_span: constitutive within its span.
+ *   - FLAGS  (uint8) exon events: FIRST / LAST: the exon is the first / last exon of an including isoform; INTERNAL: it is
+ *     neither in some including isoform; SKIPPED: some isoform of the locus has an intron [a', b'] with a' <= L and R <= b'.
+ *     Intron events: RETAINED: some isoform of the locus has an exon [L', R'] with L' <= a and b <= R'.
+ *   - PSI of one abundance row x[n_iso] with keep[n_iso] (NULL: every isoform enters): inc starts at 0.0 and adds x[j] over the
+ *     inclusion list in list order where keep[j] != 0; tot starts at 0.0 and adds x[j] over j = j0 .. j1 - 1 ascending where j
+ *     spans the event and keep[j] != 0; psi = tot > 0.0 ? inc / tot : NaN.  defined_count[u]: the rows with tot > 0.0.  The order
+ *     of the additions is the rule: for non-negative x, tot adds a superset of inc's terms in the same order and rounded addition
+ *     is monotone, so inc <= tot and 0 <= psi <= 1 exactly.  A NaN among the added x gives NaN.
+ *   - SUPPORT of an event from per-exon arrays: support[u] starts at 0.0 and adds v[incl_exon[i]] in list order, v = exon_bases
+ *     for an exon event and junction_mass for an intron event (the posterior mass of the spliced hits over that junction, summed
+ *     over the isoforms that share it); an event whose array is NULL holds 0.0.
+ * The struct is used as a host table and, with device pointers, as the device table (the convention of sbgpu_hits_t).          */
+#define SBGPU_SPLICE_FIRST 1
+#define SBGPU_SPLICE_LAST 2
+#define SBGPU_SPLICE_INTERNAL 4
+#define SBGPU_SPLICE_SKIPPED 8
+#define SBGPU_SPLICE_RETAINED 16
+typedef struct {
+   int64_t n_loci, n_iso, n_exons, n_events, n_incl;
+   int64_t *event_off;      /* [n_loci + 1]                                     */
+   int32_t *event_locus;    /* [n_events]                                       */
+   uint8_t *event_kind;     /* [n_events]: 0 exon, 1 intron                     */
+   uint32_t *event_left;    /* [n_events]                                       */
+   uint32_t *event_right;   /* [n_events]                                       */
+   uint8_t *event_flags;    /* [n_events]: SBGPU_SPLICE_* bits                  */
+   int32_t *n_span;         /* [n_events]                                       */
+   int64_t *incl_off;       /* [n_events + 1]                                   */
+   int32_t *incl_iso;       /* [n_incl]                                         */
+   int64_t *incl_exon;      /* [n_incl]                                         */
+   int64_t *iso_off;        /* [n_loci + 1]: the annotation's                   */
+   uint32_t *iso_left;      /* [n_iso]                                          */
+   uint32_t *iso_right;     /* [n_iso]                                          */
+} sbgpu_splice_events_t;
+/* Host only, no GPU needed (csrc/splice_host.cpp).  shapes: out[0] = n_events, out[1] = n_incl.  build: `out` names arrays the
+ * caller allocated at those sizes and carries the two numbers in n_events / n_incl (anything else: SBGPU_EINVAL); the call sets
+ * n_loci, n_iso and n_exons and fills every array.  SBGPU_EINVAL, with the reason in sbgpu_last_error: a NULL argument or array,
+ * offsets that descend, an isoform whose exons are not ascending and disjoint, more than 2^31 - 1 isoforms in one locus.       */
+int sbgpu_splice_events_shapes_host(const sbgpu_annotation_t *annot, int64_t out[2]);
+int sbgpu_splice_events_build_host(const sbgpu_annotation_t *annot, sbgpu_splice_events_t *out);
+/* Host forms, the plain statement of the rule.  x and keep: [n_rows][n_iso], replicate-major (keep may be NULL); psi:
+ * [n_rows][n_events]; defined_count [n_events] may be NULL.  support [n_events]; exon_bases / junction_mass [n_exons], either
+ * may be NULL.  Both check the table: SBGPU_EINVAL for offsets that descend or do not close, an event_locus outside the loci, an
+ * incl_iso outside its locus, an incl_exon outside the exons.                                                                 */
+int sbgpu_splice_psi_host(const sbgpu_splice_events_t *events, int64_t n_rows, const double *x, const int32_t *keep, double *psi,
+                          int32_t *defined_count);
+int sbgpu_splice_support_host(const sbgpu_splice_events_t *events, const double *exon_bases, const double *junction_mass, double *support);
+/* Device forms (csrc/splice_device.h): d_events is a host struct of device pointers; every array is a device array taken as it
+ * stands -- not checked beyond NULL and the sizes --, one launch, asynchronous on `stream`.  No handle, no retention, no scratch
+ * slot, no collective (a locus lives on one rank).  d_x / d_keep: the d_fpkm / d_keep of sbgpu_quantify_resident's result with
+ * n_rows = 1, or the d_fpkm_rep / d_keep_rep of sbgpu_abundance_bootstrap_device with n_rows = n_rep; the intervals are
+ * sbgpu_replicate_stats_device over d_psi[n_rep][n_events].  The results are the host forms' bits.  SBGPU_ESHAPE: more than
+ * 2^31 - 1 events or rows.                                                                                                   */
+int sbgpu_splice_psi_device(sbgpu_ctx_t *ctx, const sbgpu_splice_events_t *d_events, int64_t n_rows, const double *d_x, const int32_t *d_keep,
+                            double *d_psi, int32_t *d_defined_count, void *stream);
+int sbgpu_splice_support_device(sbgpu_ctx_t *ctx, const sbgpu_splice_events_t *d_events, const double *d_exon_bases,
+                                const double *d_junction_mass, double *d_support, void *stream);
+/* out[0]: an event of a locus of at most this many isoforms keeps its inclusion and span sets as two 64-bit masks (wider loci
+ * test the extents and walk the list, row by row); out[1]: events of one workgroup, one thread each (the grid is not capped). */
+int sbgpu_splice_limits(int64_t out[2]);
+
 #ifdef __cplusplus
 }
 #endif

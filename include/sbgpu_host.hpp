@@ -1188,5 +1188,88 @@ class LocusBootstrap {
    }
 };
 
+/* Splicing events (sbgpu_splice_*, include/sbgpu.h states the rule): the event table of an annotation -- every distinct exon and
+ * intron of every locus, the isoforms that include it and the number that span it.  Owns its vectors; raw names them (a host
+ * table: what sbgpu_splice_psi_host / sbgpu_splice_support_host take).  Built once per annotation, on the host, no GPU needed. */
+class SpliceEvents {
+ public:
+   std::vector<int64_t> event_off, incl_off, incl_exon, iso_off;
+   std::vector<int32_t> event_locus, n_span, incl_iso;
+   std::vector<uint8_t> event_kind, event_flags;
+   std::vector<uint32_t> event_left, event_right, iso_left, iso_right;
+   sbgpu_splice_events_t raw{};
+
+   explicit SpliceEvents(const sbgpu_annotation_t &annot)
+   {
+      int64_t shape[2] = {0, 0};
+      check(sbgpu_splice_events_shapes_host(&annot, shape), "sbgpu_splice_events_shapes_host");
+      const size_t nl = (size_t)annot.n_loci, ni = (size_t)annot.iso_off[annot.n_loci], nu = (size_t)shape[0], nc = (size_t)shape[1];
+      event_off.assign(nl + 1, 0), iso_off.assign(nl + 1, 0), incl_off.assign(nu + 1, 0);
+      event_locus.assign(nu, 0), n_span.assign(nu, 0), event_kind.assign(nu, 0), event_flags.assign(nu, 0), event_left.assign(nu, 0), event_right.assign(nu, 0);
+      incl_iso.assign(nc, 0), incl_exon.assign(nc, 0), iso_left.assign(ni, 0), iso_right.assign(ni, 0);
+      raw.n_events = shape[0], raw.n_incl = shape[1];
+      name();
+      check(sbgpu_splice_events_build_host(&annot, &raw), "sbgpu_splice_events_build_host");
+   }
+   SpliceEvents(const SpliceEvents &o) { *this = o; }
+   SpliceEvents &operator=(const SpliceEvents &o)
+   {
+      event_off = o.event_off, incl_off = o.incl_off, incl_exon = o.incl_exon, iso_off = o.iso_off;
+      event_locus = o.event_locus, n_span = o.n_span, incl_iso = o.incl_iso, event_kind = o.event_kind, event_flags = o.event_flags;
+      event_left = o.event_left, event_right = o.event_right, iso_left = o.iso_left, iso_right = o.iso_right;
+      raw = o.raw;
+      name();
+      return *this;
+   }
+   int64_t n_events() const { return raw.n_events; }
+   int64_t n_incl(int64_t u) const { return incl_off[(size_t)u + 1] - incl_off[(size_t)u]; }
+   bool alternative(int64_t u) const { return n_incl(u) != n_span[(size_t)u]; }
+
+ private:
+   void name()
+   {
+      raw.event_off = event_off.data(), raw.event_locus = event_locus.data(), raw.event_kind = event_kind.data();
+      raw.event_left = event_left.data(), raw.event_right = event_right.data(), raw.event_flags = event_flags.data(), raw.n_span = n_span.data();
+      raw.incl_off = incl_off.data(), raw.incl_iso = incl_iso.data(), raw.incl_exon = incl_exon.data();
+      raw.iso_off = iso_off.data(), raw.iso_left = iso_left.data(), raw.iso_right = iso_right.data();
+   }
+};
+
+/* PSI of every event for n_rows abundance rows (x / keep: [n_rows][n_iso], keep may be nullptr).  host(): psi [n_rows * n_events]
+ * and defined_count [n_events], no GPU.  device(): d_events is a table of DEVICE pointers the caller uploaded (the struct of a
+ * SpliceEvents with every pointer replaced), every other array a device array; one launch, asynchronous on `stream`.
+ * support_host() / support_device(): the events' support from the coverage's exon_bases / junction_mass (either may be nullptr). */
+class SplicePsi {
+ public:
+   int64_t n_rows = 0;
+   std::vector<double> psi;
+   std::vector<int32_t> defined_count;
+
+   static SplicePsi host(const SpliceEvents &events, int64_t n_rows, const double *x, const int32_t *keep = nullptr)
+   {
+      SplicePsi r;
+      r.n_rows = n_rows;
+      r.psi.assign((size_t)(n_rows > 0 ? n_rows : 0) * (size_t)events.n_events(), 0.0), r.defined_count.assign((size_t)events.n_events(), 0);
+      check(sbgpu_splice_psi_host(&events.raw, n_rows, x, keep, r.psi.data(), r.defined_count.data()), "sbgpu_splice_psi_host");
+      return r;
+   }
+   static void device(const Context &ctx, const sbgpu_splice_events_t &d_events, int64_t n_rows, const double *d_x, const int32_t *d_keep, double *d_psi,
+                      int32_t *d_defined_count = nullptr, void *stream = nullptr)
+   {
+      check(sbgpu_splice_psi_device(ctx.get(), &d_events, n_rows, d_x, d_keep, d_psi, d_defined_count, stream), "sbgpu_splice_psi_device");
+   }
+   static std::vector<double> support_host(const SpliceEvents &events, const double *exon_bases, const double *junction_mass)
+   {
+      std::vector<double> s((size_t)events.n_events(), 0.0);
+      check(sbgpu_splice_support_host(&events.raw, exon_bases, junction_mass, s.data()), "sbgpu_splice_support_host");
+      return s;
+   }
+   static void support_device(const Context &ctx, const sbgpu_splice_events_t &d_events, const double *d_exon_bases, const double *d_junction_mass,
+                              double *d_support, void *stream = nullptr)
+   {
+      check(sbgpu_splice_support_device(ctx.get(), &d_events, d_exon_bases, d_junction_mass, d_support, stream), "sbgpu_splice_support_device");
+   }
+};
+
 } // namespace sbgpu
 #endif /* SBGPU_HOST_HPP_ */

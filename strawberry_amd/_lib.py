@@ -52,6 +52,8 @@ SYMBOLS = [
     "sbgpu_em_loo_offsets", "sbgpu_em_loo_shapes_host", "sbgpu_em_loo_expand_host", "sbgpu_em_loo_stat_host", "sbgpu_em_loo_device",
     "sbgpu_model_loo_device", "sbgpu_em_loo_limits",
     "sbgpu_body_profile_host", "sbgpu_body_profile_device", "sbgpu_body_profile_limits",
+    "sbgpu_splice_events_shapes_host", "sbgpu_splice_events_build_host", "sbgpu_splice_psi_host", "sbgpu_splice_support_host",
+    "sbgpu_splice_psi_device", "sbgpu_splice_support_device", "sbgpu_splice_limits",
 ]
 
 
@@ -171,6 +173,13 @@ class sbgpu_isoform_coverage_t(C.Structure):
 class sbgpu_body_profile_t(C.Structure):
     _NAMES = ("body_bases", "body_total", "body_center", "body_cv", "class_profile", "class_n")
     _fields_ = [(n, C.c_void_p) for n in _NAMES] + [("d_" + n, C.c_void_p) for n in _NAMES]
+
+
+class sbgpu_splice_events_t(C.Structure):
+    _COUNTS = ("n_loci", "n_iso", "n_exons", "n_events", "n_incl")
+    _NAMES = ("event_off", "event_locus", "event_kind", "event_left", "event_right", "event_flags", "n_span", "incl_off", "incl_iso", "incl_exon",
+              "iso_off", "iso_left", "iso_right")
+    _fields_ = [(n, C.c_int64) for n in _COUNTS] + [(n, C.c_void_p) for n in _NAMES]
 
 
 class sbgpu_em_fit_t(C.Structure):
@@ -400,6 +409,13 @@ def load():
     L.sbgpu_body_profile_device.argtypes = [vp, vp, C.POINTER(sbgpu_annotation_t), C.POINTER(sbgpu_hits_t), vp, vp, vp, C.c_int32, vp,
                                             C.POINTER(sbgpu_body_profile_t)]
     L.sbgpu_body_profile_limits.argtypes = [C.POINTER(C.c_int64)]
+    L.sbgpu_splice_events_shapes_host.argtypes = [C.POINTER(sbgpu_annotation_t), C.POINTER(C.c_int64)]
+    L.sbgpu_splice_events_build_host.argtypes = [C.POINTER(sbgpu_annotation_t), C.POINTER(sbgpu_splice_events_t)]
+    L.sbgpu_splice_psi_host.argtypes = [C.POINTER(sbgpu_splice_events_t), C.c_int64, vp, vp, vp, vp]
+    L.sbgpu_splice_support_host.argtypes = [C.POINTER(sbgpu_splice_events_t), vp, vp, vp]
+    L.sbgpu_splice_psi_device.argtypes = [vp, C.POINTER(sbgpu_splice_events_t), C.c_int64, vp, vp, vp, vp, vp]
+    L.sbgpu_splice_support_device.argtypes = [vp, C.POINTER(sbgpu_splice_events_t), vp, vp, vp, vp]
+    L.sbgpu_splice_limits.argtypes = [C.POINTER(C.c_int64)]
     L.sbgpu_bootstrap_counts_host.argtypes = [C.c_int64, vp, vp, vp, C.c_uint64, C.c_int32, vp]
     L.sbgpu_bootstrap_counts_device.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp]
     L.sbgpu_em_bootstrap_device.argtypes = [vp, vp, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp, vp, vp, vp, vp, vp]

@@ -86,7 +86,8 @@ def abundance_bootstrap_device(ctx, handle, n_rep, seed, level=0.95, rep_first=0
     ranks: (rank_lo, rank_hi), default interval_ranks(n_rep, level).  locus_id: the loci's global ids where this annotation is
     a shard of a sample; comm: the shards' communicator (one all-reduce of the replicates' FPKM totals).
     -> dict: theta_mean / theta_var / fpkm_mean / fpkm_var / fpkm_lo / fpkm_hi / tpm_mean / tpm_var / tpm_lo / tpm_hi [n_iso],
-    keep_count [n_iso], status_count [n_loci, 4], total_fpkm_rep [n_rep], rank_lo, rank_hi, n_rep; with replicates also
+    keep_count [n_iso], status_count [n_loci, 4], total_fpkm_rep [n_rep], rank_lo, rank_hi, n_rep, device (the device addresses of
+    d_fpkm_rep / d_keep_rep, valid until the context's next bootstrap or quantify call); with replicates also
     fpkm_rep / keep_rep [n_rep, n_iso] (and theta_rep with keep_theta_rep).
     locus=True: sbgpu_locus_bootstrap_device instead -- the same entries, bit for bit, and two more:
     "frac": dict(mean, var, lo, hi [n_iso]; with replicates rep [n_rep, n_iso]): the isoforms' share of their locus;
@@ -131,6 +132,8 @@ def abundance_bootstrap_device(ctx, handle, n_rep, seed, level=0.95, rep_first=0
                    "sbgpu_abundance_bootstrap_device")
     r = {k: res[k][:n_iso] for k in _STATS + ("keep_count",)}
     r.update(status_count=res["status_count"][:nl], total_fpkm_rep=res["total_fpkm_rep"][:B], rank_lo=lo, rank_hi=hi, n_rep=B)
+    # (the replicates' matrices where the call left them: splice.splice_psi reads them before the context's next bootstrap / quantify call)
+    r["device"] = {"fpkm_rep": int(out.d_fpkm_rep or 0), "keep_rep": int(out.d_keep_rep or 0)}
     for k in ("fpkm_rep", "keep_rep", "theta_rep"):
         if k in res:
             r[k] = res[k][:B]

@@ -417,6 +417,22 @@ class ChainQuantifier:
         return support.model_loo_device(self.ctx, self.context_handle, int(self._out.d_keep), keep=self.keep[:self.n_iso], max_bytes=max_bytes,
                                         want=want)
 
+    def splice_psi(self, events=None, bootstrap=None, coverage=None):
+        """The PSI of every annotated exon and intron for the last resident step (splice.SplicePsi), built on the device from the
+        step's own d_fpkm / d_keep.  events: a splice.SpliceEvents or splice.DeviceSpliceEvents (None: built from this object's
+        annotation and uploaded on the first call, then reused: the table is annotation-only).  bootstrap: the dict of
+        abundance_bootstrap() on this step -> mean, var, lo, hi, defined_count over its replicates; coverage: the result of
+        isoform_coverage() on this step -> support.  Valid until the context's next quantify call."""
+        from . import splice
+        if not self.resident or not self._out.d_fpkm:
+            raise _lib.SbgpuError("splice_psi: no resident step has run")
+        if events is None:
+            if getattr(self, "_splice_events", None) is None:
+                self._splice_events = splice.as_device_events(self.ctx, None, self.annot)
+            events = self._splice_events
+        return splice.splice_psi(self.ctx, splice.as_device_events(self.ctx, events, self.annot), int(self._out.d_fpkm), int(self._out.d_keep),
+                                 bootstrap=bootstrap, coverage=coverage)
+
     def locus_abundance(self):
         """Abundances per locus of the last resident step (bootstrap.locus_abundance_device on the device arrays the call left:
         valid until the context's next quantify call) -> dict(fpkm, tpm [n_loci] float64, kept [n_loci] int32) of host arrays."""

@@ -229,7 +229,7 @@ class BinsHandle:
 def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=False, ctx=None, device=0, comm=None,
                       min_isoform_frac=0.0, filter_by_expression=True, effective_len_norm=False, with_context=False, bootstrap=None,
                       keep_bootstrap=False, keep_handle=False, with_assignment=False, with_coverage=False, with_fit=False, with_info=False,
-                      with_support=False, with_body_profile=False, iso_strand=None, n_pos=20):
+                      with_support=False, with_body_profile=False, iso_strand=None, n_pos=20, with_splicing=False):
     """sbgpu_quantify_resident on host hits brought to the device first (torch owns the copies): pass 1 (insert=None: the
     empirical insert-size law, built on the device), bins, weights, EM, FPKM / Frac / keep, the FPKM all-reduce over `comm`
     (dist.AbiComm / dist.HostComm; None: a world of one), TPM.  The hits must come grouped by locus.
@@ -251,6 +251,11 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     (info.model_info_device) -> "isoform_info": an info.IsoformInfo ("info" is the handle's sizes); "bins" as with_context.
     with_support: the bootstrap's retention, and the drop-one isoform support under the call's keep, built on the device
     (support.model_loo_device) -> "isoform_support": a support.IsoformSupport; "bins" as with_context.
+    with_splicing (True, or a splice.SpliceEvents / splice.DeviceSpliceEvents built before: the table is annotation-only): the PSI
+    of every annotated exon and intron from the call's d_fpkm / d_keep, built on the device (splice.splice_psi) -> "splicing": a
+    splice.SplicePsi; with bootstrap=dict(...) also its mean, variance and interval over the bootstrap's replicates at the bootstrap's
+    ranks, defined_count and (unless the bootstrap has replicates=False) the PSI matrix rep [n_rep, n_events], with with_coverage=True
+    also its support.  Nothing more is retained, and no other result changes.
     keep_bootstrap: retention for the bootstrap on, without running it (for a caller that runs it several times).
     keep_handle: the handle is not exported but returned as "handle", a BinsHandle that owns it -- it is destroyed by its close(),
     as a context manager, or when the object is collected; the caller runs bootstrap.abundance_bootstrap_device /
@@ -338,6 +343,12 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
             bins._export(L, annot, handle, hits.n_hits, annot.compat_words, annot.key_words, with_hit_bin=False)   # destroys the handle
     elif not keep_handle:
         L.sbgpu_bins_destroy(handle)
+    splicing = None
+    if with_splicing is not False and with_splicing is not None:
+        # (the call's d_fpkm / d_keep, the bootstrap's replicates and the coverage's arrays all live until the context's next call)
+        from . import splice
+        splicing = splice.splice_psi(ctx, splice.as_device_events(ctx, with_splicing, annot), int(out.d_fpkm or 0), int(out.d_keep or 0),
+                                     bootstrap=boot, coverage=cov, replicates=bool(bootstrap is not None and bootstrap.get("replicates", True)))
     r = {k: (v[:n_iso] if k not in ("status", "iters") else v[:nl]) for k, v in res.items()}
     r.update({"insert": {"mean": used.mean, "sd": used.sd, "use_emp": bool(used.use_emp), "start_offset": used.start_offset,
                          "end_offset": used.end_offset, "total_reads": used.total_reads, "emp_hist": emp},
@@ -359,6 +370,8 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
         r.update(isoform_info=iso_info, bins=bins)
     if with_support:
         r.update(isoform_support=iso_support, bins=bins)
+    if splicing is not None:
+        r["splicing"] = splicing
     if keep_handle:
         r["handle"] = owner
     return r
