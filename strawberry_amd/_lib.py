@@ -428,10 +428,6 @@ def load():
     L.sbgpu_locus_abundance_device.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.sbgpu_locus_bootstrap_device.argtypes = [vp, vp, C.POINTER(sbgpu_bootstrap_params_t), C.c_int32, C.c_int32, C.c_int32, vp, vp,
                                                C.POINTER(sbgpu_abundance_bootstrap_t), C.POINTER(sbgpu_locus_bootstrap_t)]
-    for name in SYMBOLS:
-        f = getattr(L, name)
-        if f.restype is C.c_int and name not in ("sbgpu_device_count", "sbgpu_plan_classes"):
-            pass
     _lib = L
     return L
 

@@ -160,7 +160,7 @@ static inline int api_fail_hip(hipError_t e, const char *what)
    return api_fail(e == hipErrorOutOfMemory ? SBGPU_ENOMEM : SBGPU_EHIP, hip_error_text(what, e));
 }
 // Experiment switches: SBGPU_* variables that select paths DESIGN.md / profiles/EXPERIMENTS_*.md record as measured and NOT adopted
-// (phased execution, launch graphs, tile and schedule variants, A/B forms of the grouping ...).  They exist only in a library built
+// (phased execution, tile and schedule variants ...).  They exist only in a library built
 // with -DSB_EXPERIMENTS (`make experiments` -> libsbgpu_exp.so, never shipped, never timed by bench.py); the shipped library does
 // not read them.  What stays a plain getenv: resources (SBGPU_POOL_GB, SBGPU_HOST_THREADS), diagnostics (SBGPU_HOST_TIMING) and the
 // tests' hooks that force a fallback route the default inputs do not take (SBGPU_PAIR_FORCE_SORT, SBGPU_COLLAPSE_FORCE_SEQ,

@@ -21,20 +21,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace sb {
+#include "bins_schedule.h" // the tables' sizes, the workgroups' and the kBins* flags
 
-// Two table sizes: loci of up to 256 hits (most of them) take 1024 slots -- 18 KB of LDS, so that many
-// workgroups share a CU and hide each other's memory latency -- the others 8192 (140 KB, one per CU).
-constexpr int kBinsSlotsSmall = 1024, kBinsMaxSmall = 256;   // at most one bin per hit
-constexpr int kBinsSlotsMid = 2048, kBinsMaxMid = 1400;      // larger loci first try this one (36 KB: four workgroups per CU);
-                                                             // a locus with more bins than that is redone with the big table
-constexpr int kBinsSlotsBig = 8192, kBinsMaxBig = 5600;      // ~0.7 load
-constexpr int kBinsSmallHits = 256;
-constexpr int kBinsThreads = 256;      // the small table's workgroup
-constexpr int kBinsThreadsMid = 512;   // the two-pass form's
-constexpr int kBinsThreadsAccum = 1024; // the single-pass form's middle table: two workgroups of 16 waves per CU
-constexpr int kBinsThreadsBig = 1024;  // the big table fills a CU's LDS: one workgroup per CU, so it brings 16 waves
-enum : int32_t { kBinsUnsorted = 1, kBinsFractional = 2, kBinsTableFull = 4, kBinsMassOverflow = 8, kBinsRunTooLong = 128 };
+namespace sb {
 
 struct BinsArgs {
    int64_t n_loci;               // loci in `loci`
@@ -611,8 +600,7 @@ struct PairsArgs {
 // locus the middle table could not hold, redone later -- stands for 0).  MODE 1, over the isoforms: the pair and
 // segment counts -> pair_off, pseg_off.  Three small launches: tile sums (4096 entries per workgroup, 16 per lane:
 // one cache line of a lane's own), the scan of the tile sums (one workgroup), the tiles again with their bases.
-// 250 000 isoforms: 61 tiles, ~15 us together -- against a D2H, a host loop and an H2D.
-constexpr int kScanTile = 4096, kScanPerLane = 16;
+// 250 000 isoforms: 61 tiles, ~15 us together -- against a D2H, a host loop and an H2D.  (kScanTile, kScanPerLane: bins_schedule.h)
 
 // Zero fill, 16 bytes per lane and step (`bytes` a multiple of 16, `p` 16-byte aligned): the runtime's
 // hipMemsetAsync kernel reaches 60 GB/s on this -- 0.2 ms for the 12 MB of 1.5 M hits -- this one the memory's rate.

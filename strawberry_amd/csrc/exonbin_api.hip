@@ -90,9 +90,9 @@ int exonbin_device_impl(sbgpu_ctx_t *c, const sbgpu_annotation_t *an, const sbgp
    a.locus_seg_ok = nullptr;
    a.locus_adj = nullptr;
    a.iso_member_hi = a.iso_start_hi = a.locus_adj_hi = nullptr;
-   // the isoforms in the segment basis (exonbin_device.h): loci of up to 64 segments (key_words <= 2 covers them all)
-   static const bool seg_basis = !(sb::exp_env("SBGPU_EXONBIN_SEGBASIS") && std::atoi(sb::exp_env("SBGPU_EXONBIN_SEGBASIS")) == 0);
-   if (seg_basis && key_words >= 1 && compat_words >= 1) {
+   // the isoforms in the segment basis (exonbin_device.h): loci of up to 64 segments (key_words <= 2 covers them all);
+   // the kernel walks the exons for whatever the basis does not cover
+   if (key_words >= 1 && compat_words >= 1) {
       DeviceSegBasis sbz;
       if (seg_pre) {
          sbz = *seg_pre; // made once for a resident annotation
@@ -118,21 +118,11 @@ int exonbin_device_impl(sbgpu_ctx_t *c, const sbgpu_annotation_t *an, const sbgp
    }
    const int64_t blocks_wanted = (hits->n_hits + 255) / 256;
    if (blocks_wanted > 0x7fffffff) return api_fail(SBGPU_ESHAPE, "sbgpu_exonbin_device: more than 2^39 hits in one call");
-   static const bool lane_form = sb::exp_env("SBGPU_EXONBIN_LANE") && std::atoi(sb::exp_env("SBGPU_EXONBIN_LANE")) != 0;
-   if (lane_form) { // per-lane kernel only (A/B measurements)
-      const int64_t cap = (int64_t)sb::ctx_cu_count(c) * 32;
-      hipLaunchKernelGGL(sb::exonbin_lane_kernel, dim3((unsigned)(blocks_wanted < cap ? blocks_wanted : cap)), dim3(256), 0,
-                         (hipStream_t)stream, a);
-      if (d_span)
-         hipLaunchKernelGGL(sb::hit_signature_kernel, dim3((unsigned)(blocks_wanted < cap ? blocks_wanted : cap)), dim3(256), 0,
-                            (hipStream_t)stream, a.n_hits, a.feat_off, a.feat_left, a.feat_right, d_span, d_fhash);
-   } else {
-      hipLaunchKernelGGL(sb::exonbin_kernel, dim3((unsigned)blocks_wanted), dim3(256), 0, (hipStream_t)stream, a);
-      // loci of 65-128 segments or isoforms (form 3 of iso_masks_kernel): their regular hits in the 128-bit segment basis.
-      // Only an annotation with words beyond two can have such a locus; everywhere else the kernel is not launched.
-      if (a.locus_seg_ok && (key_words > 2 || compat_words > 2))
-         hipLaunchKernelGGL(sb::exonbin_seg128_kernel, dim3((unsigned)blocks_wanted), dim3(256), 0, (hipStream_t)stream, a);
-   }
+   hipLaunchKernelGGL(sb::exonbin_kernel, dim3((unsigned)blocks_wanted), dim3(256), 0, (hipStream_t)stream, a);
+   // loci of 65-128 segments or isoforms (form 3 of iso_masks_kernel): their regular hits in the 128-bit segment basis.
+   // Only an annotation with words beyond two can have such a locus; everywhere else the kernel is not launched.
+   if (a.locus_seg_ok && (key_words > 2 || compat_words > 2))
+      hipLaunchKernelGGL(sb::exonbin_seg128_kernel, dim3((unsigned)blocks_wanted), dim3(256), 0, (hipStream_t)stream, a);
    hipError_t e = hipGetLastError();
    if (e != hipSuccess) return api_fail(SBGPU_EHIP, std::string("exonbin_kernel: ") + hipGetErrorString(e));
    return SBGPU_OK;
@@ -312,520 +302,470 @@ void iso_segments(const sbgpu_annotation_t *an, IsoSegments *out)
    }
 }
 
-int bins_create_device_impl(sbgpu_ctx_t *c, const sbgpu_annotation_t *an, const sbgpu_hits_t *dh, const float *d_mass,
-                            const int64_t *locus_hit_off, int32_t compat_words, int32_t key_words, const uint32_t *d_compat,
-                            const uint32_t *d_key, int64_t *d_hit_bin, void *stream, const IsoSegments *iso_pre, sbgpu_bins_t **out,
-                            const uint64_t *d_span, const uint32_t *d_fhash, const GroupingHooks *hooks)
+// ---- sbgpu_bins_create_device: the hits of every locus grouped into bins, the bins packed, the (bin, isoform) pairs made.
+// What the host decides on the way -- order, launches, layouts, fix-ups -- is bins_schedule.h's; the stages below issue it.
+namespace {
+// a HIP call that must succeed (SBGPU_EHIP, "<the call>: <HIP's text>")
+#define SB_TRY(expr)                                                                    \
+   do {                                                                                 \
+      hipError_t e_ = (expr);                                                           \
+      if (e_ != hipSuccess) return api_fail(SBGPU_EHIP, sb::hip_error_text(#expr, e_)); \
+   } while (0)
+
+// one launch record (bins_schedule.h: bins_group_steps) -> the matching instantiation; `cap`: 8 x the CUs
+hipError_t launch_group_step(const BinsStep &st, int64_t cap, hipStream_t s, const BinsArgs &a)
+{
+   const dim3 grid((unsigned)std::min<int64_t>(st.count, cap * st.grid_mult)), block((unsigned)st.threads);
+   auto is = [&](int kernel, int slots, int max_bins, int threads, int cw, bool retry) {
+      return st.kernel == kernel && st.slots == slots && st.max_bins == max_bins && st.threads == threads && st.cw == cw && st.retry == retry;
+   };
+   if (is(kBinsAccum, kBinsSlotsSmall, kBinsMaxSmall, kBinsThreads, 1, false)) hipLaunchKernelGGL((bins_accum_kernel<kBinsSlotsSmall, kBinsMaxSmall, kBinsThreads, 1>), grid, block, 0, s, a);
+   else if (is(kBinsAccum, kBinsSlotsSmall, kBinsMaxSmall, kBinsThreads, 2, false)) hipLaunchKernelGGL((bins_accum_kernel<kBinsSlotsSmall, kBinsMaxSmall, kBinsThreads, 2>), grid, block, 0, s, a);
+   else if (is(kBinsAccum, kBinsSlotsMid, kBinsMaxMid, kBinsThreadsAccum, 1, true)) hipLaunchKernelGGL((bins_accum_kernel<kBinsSlotsMid, kBinsMaxMid, kBinsThreadsAccum, 1, true>), grid, block, 0, s, a);
+   else if (is(kBinsAccum, kBinsSlotsMid, kBinsMaxMid, kBinsThreadsAccum, 2, true)) hipLaunchKernelGGL((bins_accum_kernel<kBinsSlotsMid, kBinsMaxMid, kBinsThreadsAccum, 2, true>), grid, block, 0, s, a);
+   else if (is(kBinsAccum, kBinsSlotsLight, kBinsMaxLight, kBinsThreads, 1, true)) hipLaunchKernelGGL((bins_accum_kernel<kBinsSlotsLight, kBinsMaxLight, kBinsThreads, 1, true>), grid, block, 0, s, a);
+   else if (is(kBinsAccum, kBinsSlotsLight, kBinsMaxLight, kBinsThreads, 2, true)) hipLaunchKernelGGL((bins_accum_kernel<kBinsSlotsLight, kBinsMaxLight, kBinsThreads, 2, true>), grid, block, 0, s, a);
+   else if (is(kBinsLocus, kBinsSlotsSmall, kBinsMaxSmall, kBinsThreads, 0, false)) hipLaunchKernelGGL((bins_locus_kernel<kBinsSlotsSmall, kBinsMaxSmall, kBinsThreads>), grid, block, 0, s, a);
+   else if (is(kBinsLocus, kBinsSlotsMid, kBinsMaxMid, kBinsThreadsMid, 0, true)) hipLaunchKernelGGL((bins_locus_kernel<kBinsSlotsMid, kBinsMaxMid, kBinsThreadsMid, true>), grid, block, 0, s, a);
+   else return hipErrorInvalidValue; // a record no kernel was built for: a missing kernel is an error
+   return hipGetLastError();
+}
+
+// One call's state, stage by stage.  It owns the two pool arenas until the handle has them: every early return ends in the
+// destructor, which waits for the stream (kernels may still use them) and then gives back what is left.
+struct BinsCall {
+   // -- the arguments
+   sbgpu_ctx_t *c;
+   const sbgpu_annotation_t *an;
+   const sbgpu_hits_t *dh;
+   const float *d_mass;
+   const int64_t *locus_hit_off;
+   int32_t cw, kw;
+   const uint32_t *d_compat, *d_key;
+   int64_t *d_hit_bin;
+   hipStream_t s;
+   const IsoSegments *iso_pre;
+   sbgpu_bins_t **out;
+   const uint64_t *d_span;
+   const uint32_t *d_fhash;
+   const GroupingHooks *hooks;
+   // -- shape (validate)
+   int64_t nl = 0, nh = 0, n_iso = 0, n_seg = 0, cap = 0; // cap: 8 x the CUs, the grids' unit
+   const sbgpu_annotation_t *d_an = nullptr;              // the annotation / the segment lists in device memory already (hooks)
+   const DeviceIsoSegments *d_iso = nullptr;
+   bool want_local = false;
+   // -- SBGPU_HOST_TIMING: stage times on stderr; =2: host clock only, no synchronisation
+   bool timing = false, timing_sync = false;
+   double t_stage = 0;
+   // -- memory (take_memory): the context's scratch (d, d3: nothing to free), its pinned words, and the two pool arenas
+   BinsScratchLayout L{};
+   BinsPackedLayout P{};
+   PairsInLayout R{};
+   BinsPinnedLayout H{};
+   char *d = nullptr, *d3 = nullptr, *pin = nullptr;
+   char *d2 = nullptr; // the packed per-bin arrays: the handle takes them over (DeviceBinArrays)
+   size_t d2_cap = 0;
+   DevicePairs dp;     // the pairs' arena: the handle's too
+   IsoSegments own_segments;
+   int32_t *nb = nullptr, *nu = nullptr; // pinned: bins / hits used per locus
+   volatile int32_t *flags_h = nullptr;
+   volatile int64_t *totals_h = nullptr;
+   hipStream_t cs = nullptr;
+   hipEvent_t ev_up = nullptr, ev_rows = nullptr, ev_in = nullptr, ev_acc = nullptr;
+   BinsArgs a{};
+   BinsPackArgs pk{};
+   PairsArgs pa{};
+   // -- decisions and what came back
+   BinsOrder order;
+   BinsGroupSteps steps;
+   bool speculative = false, fixed_up = false, any_wide_locus = false;
+   unsigned lgrid = 1, pgrid = 1;
+   BinsRows rows;
+
+   ~BinsCall()
+   {
+      if (!d2 && !dp.arena) return;
+      (void)hipStreamSynchronize(s);
+      dev_give(dp.arena, dp.capacity);
+      dev_give(d2, d2_cap);
+   }
+   static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+   void stage(const char *name)
+   {
+      if (!timing) return;
+      if (timing_sync) (void)hipStreamSynchronize(s);
+      const double t = now();
+      std::fprintf(stderr, "  bins_create_device: %-16s %.2f ms\n", name, (t - t_stage) * 1e3);
+      t_stage = t;
+   }
+
+   int validate();
+   int take_memory();
+   void fill_args();
+   int upload_and_group();
+   hipError_t fetch_rows();
+   hipError_t launch_middle();
+   hipError_t serve_list(const std::vector<int32_t> &loci);
+   int fix_up();
+   int finish_middle();
+   int fill_pairs();
+   int make_handle();
+};
+
+int BinsCall::validate()
 {
    if (!c || !an || !dh || !locus_hit_off || !out) return api_fail(SBGPU_EINVAL, "sbgpu_bins_create_device: null argument");
    *out = nullptr;
-   const int64_t nl = an->n_loci, nh = dh->n_hits;
-   if (nl < 1 || nh < 0 || compat_words < 1 || key_words < 1) return api_fail(SBGPU_EINVAL, "sbgpu_bins_create_device: bad counts");
+   nl = an->n_loci, nh = dh->n_hits;
+   if (nl < 1 || nh < 0 || cw < 1 || kw < 1) return api_fail(SBGPU_EINVAL, "sbgpu_bins_create_device: bad counts");
    if (nh > 0x7fffffff) return api_fail(SBGPU_ESHAPE, "sbgpu_bins_create_device: more than 2^31 hits in one call");
    if (nh && (!dh->feat_off || !dh->feat_left || !dh->feat_right || !d_mass || !d_compat || !d_key))
       return api_fail(SBGPU_EINVAL, "sbgpu_bins_create_device: null device pointer");
    if (locus_hit_off[0] != 0 || locus_hit_off[nl] != nh) return api_fail(SBGPU_EINVAL, "sbgpu_bins_create_device: locus_hit_off does not span the hits");
    for (int64_t l = 0; l < nl; ++l) {
       if (locus_hit_off[l + 1] < locus_hit_off[l]) return api_fail(SBGPU_EINVAL, "sbgpu_bins_create_device: decreasing locus_hit_off");
-      if (an->iso_off[l + 1] - an->iso_off[l] > 32 * (int64_t)compat_words || an->seg_off[l + 1] - an->seg_off[l] > 32 * (int64_t)key_words)
+      if (an->iso_off[l + 1] - an->iso_off[l] > 32 * (int64_t)cw || an->seg_off[l + 1] - an->seg_off[l] > 32 * (int64_t)kw)
          return api_fail(SBGPU_ESHAPE, "sbgpu_bins_create_device: word counts do not cover a locus");
+      any_wide_locus = any_wide_locus || an->iso_off[l + 1] - an->iso_off[l] > 64;
    }
-   hipStream_t s = (hipStream_t)stream;
+   n_iso = an->iso_off[nl], n_seg = an->seg_off[nl];
+   cap = (int64_t)ctx_cu_count(c) * 8;
+   d_an = hooks ? hooks->d_annot : nullptr;
+   d_iso = hooks ? hooks->d_iso : nullptr;
+   want_local = hooks && hooks->d_hit_bin_local;
    const char *timing_env = std::getenv("SBGPU_HOST_TIMING");
-   const bool timing = timing_env != nullptr, timing_sync = timing && std::atoi(timing_env) != 2; // diagnostic: stage times on stderr; =2: host clock only, no synchronisation
-   auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-   double t_stage = now();
-   auto stage = [&](const char *name) {
-      if (timing) {
-         if (timing_sync) (void)hipStreamSynchronize(s);
-         const double t = now();
-         std::fprintf(stderr, "  bins_create_device: %-16s %.2f ms\n", name, (t - t_stage) * 1e3);
-         t_stage = t;
-      }
-   };
-   // one arena for the scratch: [hit_bin_local | bin_rep | bin_count | bin_compat | n_bins | n_used | flags | offsets x2]
-   const size_t nh1 = (size_t)(nh > 0 ? nh : 1);
-   auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-   size_t off = 0;
-   const size_t o_local = off; off += up(nh1 * 4);
-   const size_t o_rep = off; off += up(nh1 * 4);
-   const size_t o_zero = off; // bin_count + bin_compat are zeroed together
-   const size_t o_cnt = off; off += up(nh1 * 4);
-   const size_t o_cmp = off; off += up(nh1 * 4 * (size_t)compat_words);
-   const size_t zero_bytes = off - o_zero;
-   const size_t o_nb = off; off += up((size_t)nl * 4);
-   const size_t o_nu = off; off += up((size_t)nl * 4);
-   const size_t o_flag = off; off += 256; // [0]: the grouping kernels' flags, [1]: the middle's (pack, pairs)
-   const size_t o_hoff = off; off += up((size_t)(nl + 1) * 8);
-   const size_t o_roff = off; off += up((size_t)(nl + 1) * 8);
-   const size_t o_order = off; off += up((size_t)nl * 4);
-   const size_t o_dup = off; off += up(nh1);
-   const size_t o_span = off; off += d_span ? 0 : up(nh1 * 8);   // spans and hashes: the exon-bin kernel's, or made here
-   const size_t o_fhash = off; off += d_span ? 0 : up(nh1 * 4);
-   // the scratch arenas live with the context (sb::ctx_scratch): nothing to free here (d2 is not scratch: below)
-   char *d = nullptr, *d2 = nullptr;
-   hipError_t e = sb::ctx_scratch(c, 2, off, &d);
-   if (e != hipSuccess) return api_fail(e == hipErrorOutOfMemory ? SBGPU_ENOMEM : SBGPU_EHIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-   auto bail = [&](int code, const std::string &msg) { return api_fail(code, msg); };
-#define SB_TRY(expr)                                                                        \
-   do {                                                                                     \
-      hipError_t e_ = (expr);                                                               \
-      if (e_ != hipSuccess) return bail(SBGPU_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-   } while (0)
-   sb::BinsArgs a;
-   a.n_loci = nl;
-   a.locus_hit_off = (const int64_t *)(d + o_hoff);
-   a.feat_off = dh->feat_off;
-   a.feat_left = dh->feat_left;
-   a.feat_right = dh->feat_right;
-   a.mass = d_mass;
-   a.compat_words = compat_words;
-   a.key_words = key_words;
-   a.compat = d_compat;
-   a.key = d_key;
-   if (!d_span && nh) {
-      const int64_t blocks = (nh + 255) / 256, capb = (int64_t)sb::ctx_cu_count(c) * 32;
-      hipLaunchKernelGGL(sb::hit_signature_kernel, dim3((unsigned)(blocks < capb ? blocks : capb)), dim3(256), 0, s, nh,
-                         dh->feat_off, dh->feat_left, dh->feat_right, (uint64_t *)(d + o_span), (uint32_t *)(d + o_fhash));
+   timing = timing_env != nullptr, timing_sync = timing && std::atoi(timing_env) != 2;
+   t_stage = now();
+   return SBGPU_OK;
+}
+
+// All device memory is sized before anything runs (bins <= hits), so that the kernels follow each other in the stream
+int BinsCall::take_memory()
+{
+   L = bins_scratch_layout(nl, nh, cw, !d_span);
+   hipError_t e = ctx_scratch(c, 2, L.bytes, &d);
+   if (e != hipSuccess) return api_fail_hip(e, "hipMalloc");
+   if (!d_span && nh) { // spans and hashes the exon-bin kernel did not leave
+      const int64_t blocks = (nh + 255) / 256, capb = cap * 4;
+      hipLaunchKernelGGL(hit_signature_kernel, dim3((unsigned)(blocks < capb ? blocks : capb)), dim3(256), 0, s, nh, dh->feat_off, dh->feat_left,
+                         dh->feat_right, (uint64_t *)(d + L.span), (uint32_t *)(d + L.fhash));
       SB_TRY(hipGetLastError());
    }
-   a.span = d_span ? d_span : (const uint64_t *)(d + o_span);
-   a.fhash = d_span ? d_fhash : (const uint32_t *)(d + o_fhash);
-   a.hit_bin_local = (int32_t *)(d + o_local);
-   a.bin_rep = (int32_t *)(d + o_rep);
-   a.bin_count = (int32_t *)(d + o_cnt);
-   a.bin_compat = (uint32_t *)(d + o_cmp);
-   a.dup = (uint8_t *)(d + o_dup);
-   a.n_bins = (int32_t *)(d + o_nb);
-   a.n_used = (int32_t *)(d + o_nu);
-   a.flags = (int32_t *)(d + o_flag);
-   const int64_t cap = (int64_t)sb::ctx_cu_count(c) * 8;
-   const int64_t n_iso = an->iso_off[nl], n_seg = an->seg_off[nl];
-   const sbgpu_annotation_t *d_an = hooks ? hooks->d_annot : nullptr;
-   // ---- the rest of the device memory, all sized before anything runs (bins <= hits), so that the kernels below
-   // follow each other in the stream: the packed per-bin arrays, and what the pairs' kernels read
-   // (an allocation of its own, not context scratch: the handle takes it over, see DeviceBinArrays)
-   size_t off2 = 0;
-   const size_t p_cnt = off2; off2 += up(nh1 * 4);
-   const size_t p_key = off2; off2 += up(nh1 * 4 * (size_t)key_words);
-   const size_t p_cmp = off2; off2 += up(nh1 * 4 * (size_t)compat_words);
-   size_t d2_cap = 0;
-   e = sb::dev_take(off2, &d2, &d2_cap);
-   if (e != hipSuccess) return bail(e == hipErrorOutOfMemory ? SBGPU_ENOMEM : SBGPU_EHIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-   struct ArenaGuard { // given back on every early return; released once the handle owns it
-      char *&p;
-      size_t &cap;
-      hipStream_t s;
-      ~ArenaGuard()
-      {
-         if (p) {
-            (void)hipStreamSynchronize(s);
-            sb::dev_give(p, cap);
-         }
-      }
-   } d2_guard = {d2, d2_cap, s};
-   sb::IsoSegments own_segments;
+   P = bins_packed_layout(nh, cw, kw);
+   if ((e = dev_take(P.bytes, &d2, &d2_cap)) != hipSuccess) return api_fail_hip(e, "hipMalloc");
    if (!iso_pre) { // a caller that knows the annotation earlier makes them while something else runs (chain_api.hip)
-      sb::iso_segments(an, &own_segments);
+      iso_segments(an, &own_segments);
       iso_pre = &own_segments;
    }
-   const std::vector<int64_t> &iso_seg_off = iso_pre->seg_off;
-   const std::vector<int32_t> &iso_seg_idx = iso_pre->seg_idx, &iso_locus = iso_pre->locus, &iso_len = iso_pre->len;
-   const size_t ni1 = (size_t)(n_iso > 0 ? n_iso : 1), nsi1 = iso_seg_idx.empty() ? 1 : iso_seg_idx.size();
-   size_t off3 = 0;
-   const size_t r_isoff = off3; off3 += up((size_t)(nl + 1) * 8);
-   const size_t r_foff = off3; off3 += up((size_t)(nl + 1) * 8);
-   const size_t r_segoff = off3; off3 += up((size_t)(nl + 1) * 8);
-   const size_t r_segl = off3; off3 += up((size_t)(n_seg + 1) * 4);
-   const size_t r_segr = off3; off3 += up((size_t)(n_seg + 1) * 4);
-   const size_t r_isegoff = off3; off3 += up((ni1 + 1) * 8);
-   const size_t r_isegidx = off3; off3 += up(nsi1 * 4);
-   const size_t r_isoloc = off3; off3 += up(ni1 * 4);
-   const size_t r_isolen = off3; off3 += up(ni1 * 4);
-   const size_t r_pcnt = off3; off3 += up(ni1 * 4);
-   const size_t r_scnt = off3; off3 += up(ni1 * 4);
-   const size_t r_poff = off3; off3 += up((ni1 + 1) * 8);
-   const size_t r_soff = off3; off3 += up((ni1 + 1) * 8);
-   const size_t r_tot = off3; off3 += 256; // totals of the two scans: [n_bins, n_elem, n_pairs, n_pair_segs]
-   const int64_t row_tiles = (nl + sb::kScanTile - 1) / sb::kScanTile, iso_tiles = std::max<int64_t>(1, (n_iso + sb::kScanTile - 1) / sb::kScanTile);
-   const size_t r_part = off3; off3 += up((size_t)(2 * std::max(row_tiles, iso_tiles) + 2) * 8); // the scans' tile sums
-   char *d3 = nullptr;
-   e = sb::ctx_scratch(c, 4, off3, &d3);
-   if (e != hipSuccess) return bail(e == hipErrorOutOfMemory ? SBGPU_ENOMEM : SBGPU_EHIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-   // pinned host words for what comes back between the kernels (copies into pageable memory would hold the host
-   // until the stream has reached them): [bins per locus | hits used per locus | flags | totals]
-   const size_t h_nb = 0, h_nu = up((size_t)nl * 4), h_flag = h_nu + up((size_t)nl * 4), h_tot = h_flag + 256;
-   char *pin = nullptr;
-   e = sb::ctx_pinned(c, 0, h_tot + 256, &pin);
-   if (e != hipSuccess) return bail(SBGPU_ENOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-   int32_t *nb = (int32_t *)(pin + h_nb), *nu = (int32_t *)(pin + h_nu);
-   volatile int32_t *flags_h = (volatile int32_t *)(pin + h_flag);
-   volatile int64_t *totals_h = (volatile int64_t *)(pin + h_tot);
-   hipStream_t cs = nullptr;
-   hipEvent_t ev_up = nullptr, ev_rows = nullptr, ev_in = nullptr, ev_acc = nullptr;
-   SB_TRY(sb::ctx_copy_stream(c, &cs));
-   SB_TRY(sb::ctx_event(c, 0, &ev_up));
-   SB_TRY(sb::ctx_event(c, 1, &ev_rows));
-   SB_TRY(sb::ctx_event(c, 2, &ev_in));
-   SB_TRY(sb::ctx_event(c, 4, &ev_acc));
-   // ---- uploads on the copy stream, beside whatever the main stream still runs (the caller's exon-bin kernel): a copy
-   // in the main stream between two kernels costs the hand-over to the DMA engine and back, 0.3 ms each way measured.
-   // First what the grouping kernels read (hit offsets, the loci's order), then the annotation's part of the pairs' inputs.
-   // (Streams share hardware queues -- the copy stream may sit in the main stream's queue and then runs in issue order
-   // with it -- so nothing here counts on the overlap.)
-   SB_TRY(hipMemcpyAsync(d + o_hoff, locus_hit_off, (size_t)(nl + 1) * 8, hipMemcpyHostToDevice, cs));
-   // The bins' counts and compat words are [n_hits]-sized (a locus' bins sit at its hit offset): 1.3 GB for 1.6e8 hits,
-   // 0.18 ms to zero at the memory's rate.  Only bins_locus_kernel's global atomics need the zeros -- the two-pass form
-   // and the big table; the single-pass kernels write every entry they own -- so they are made where those run.
-   auto zero_bins = [&](hipStream_t zs) -> hipError_t {
-      const int64_t n16 = (int64_t)(zero_bytes / 16); // (the arena's parts are 256-byte multiples)
-      hipLaunchKernelGGL(sb::bins_zero_kernel, dim3((unsigned)std::min<int64_t>((n16 + 255) / 256, cap * 4)), dim3(256), 0, zs, (uint4 *)(d + o_zero), n16);
-      return hipGetLastError();
-   };
-   hipLaunchKernelGGL(sb::bins_zero_kernel, dim3(1), dim3(256), 0, cs, (uint4 *)(d + o_flag), (int64_t)16);
-   SB_TRY(hipGetLastError());
-   const int64_t *d_iso_off = d_an ? d_an->iso_off : (const int64_t *)(d3 + r_isoff);
-   // small and big loci in two launches (two LDS table sizes)
-   std::vector<int32_t> order((size_t)nl);
-   int64_t n_small = 0;
-   for (int64_t l = 0; l < nl; ++l)
-      if (locus_hit_off[l + 1] - locus_hit_off[l] <= sb::kBinsSmallHits) order[(size_t)n_small++] = (int32_t)l;
-   int64_t n_big = 0;
-   for (int64_t l = 0; l < nl; ++l)
-      if (locus_hit_off[l + 1] - locus_hit_off[l] > sb::kBinsSmallHits) order[(size_t)(n_small + n_big++)] = (int32_t)l;
-   // the very big ones first, largest to smallest: a locus is one workgroup's work, and a locus of 10^5 hits that starts
-   // last would be the kernel's tail (only those few are sorted: a full sort of 55 000 loci costs 2.6 ms of host time).
-   // They also get a launch of their own with 1024 threads; the loci between -- a few thousand hits, two or three per
-   // thread of such a workgroup -- are bound by the per-locus fixed cost (table set-up, six workgroup barriers, the
-   // ranking), which 256-thread workgroups, several per CU, pay side by side: 2.62 -> 1.83 ms on the chain sample
-   // (SBGPU_BINS_MID_THREADS=1024|512|256, SBGPU_BINS_HEAVY_HITS=n for A/B; 8192 was the best of 2000 ... 100 000).
-   int64_t n_heavy = 0;
-   static const int64_t heavy_env = sb::exp_env("SBGPU_BINS_HEAVY_HITS") ? std::atoll(sb::exp_env("SBGPU_BINS_HEAVY_HITS")) : 0;
-   {
-      const int64_t heavy = heavy_env > 0 ? heavy_env : std::max<int64_t>(8192, 3 * (nh / std::max<int64_t>(nl, 1)));
-      auto hits_of = [&](int32_t l) { return locus_hit_off[l + 1] - locus_hit_off[l]; };
-      auto first_big = order.begin() + n_small, last_big = first_big + n_big;
-      auto mid = std::stable_partition(first_big, last_big, [&](int32_t l) { return hits_of(l) >= heavy; });
-      std::sort(first_big, mid, [&](int32_t x, int32_t y) { return hits_of(x) != hits_of(y) ? hits_of(x) > hits_of(y) : x < y; });
-      n_heavy = mid - first_big;
-   }
-   // the single-pass kernels (bins_device.h) where a bin's compat union fits two words; SBGPU_BINS_TWO_PASS=1: the older form (A/B)
-   static const bool two_pass_env = sb::exp_env("SBGPU_BINS_TWO_PASS") && std::atoi(sb::exp_env("SBGPU_BINS_TWO_PASS")) != 0;
-   const bool single_pass = compat_words <= 2 && key_words <= 2 && !two_pass_env;
-   if (!single_pass) SB_TRY(zero_bins(cs));
-   SB_TRY(hipMemcpyAsync(d + o_order, order.data(), (size_t)nl * 4, hipMemcpyHostToDevice, cs));
-   SB_TRY(hipEventRecord(ev_in, cs));
-   SB_TRY(hipStreamWaitEvent(s, ev_in, 0));
-   sb::ctx_stage_begin(c, single_pass ? "bins_accum_kernel" : "bins_locus_kernel", s);
-   if (n_small) {
-      a.n_loci = n_small;
-      a.loci = (const int32_t *)(d + o_order);
-      const dim3 grid((unsigned)std::min<int64_t>(n_small, cap * 4));
-      if (single_pass && compat_words == 1) hipLaunchKernelGGL((sb::bins_accum_kernel<sb::kBinsSlotsSmall, sb::kBinsMaxSmall, sb::kBinsThreads, 1>), grid, dim3(sb::kBinsThreads), 0, s, a);
-      else if (single_pass) hipLaunchKernelGGL((sb::bins_accum_kernel<sb::kBinsSlotsSmall, sb::kBinsMaxSmall, sb::kBinsThreads, 2>), grid, dim3(sb::kBinsThreads), 0, s, a);
-      else hipLaunchKernelGGL((sb::bins_locus_kernel<sb::kBinsSlotsSmall, sb::kBinsMaxSmall, sb::kBinsThreads>), grid, dim3(sb::kBinsThreads), 0, s, a);
-      SB_TRY(hipGetLastError());
-   }
-   if (n_big) {
-      // first the middle table; whatever has more bins than it holds is redone below
-      a.n_loci = n_big;
-      a.loci = (const int32_t *)(d + o_order) + n_small;
-      const dim3 grid((unsigned)std::min<int64_t>(n_big, cap * 4));
-      static const int mid_threads = sb::exp_env("SBGPU_BINS_MID_THREADS") ? std::atoi(sb::exp_env("SBGPU_BINS_MID_THREADS")) : 256;
-      if (single_pass && mid_threads != 1024 && n_heavy < n_big) {
-         // the heavy loci on 1024 threads, the others on fewer (more workgroups per CU, cheaper barriers)
-         if (n_heavy) {
-            a.n_loci = n_heavy;
-            const dim3 gh((unsigned)std::min<int64_t>(n_heavy, cap * 4));
-            if (compat_words == 1) hipLaunchKernelGGL((sb::bins_accum_kernel<sb::kBinsSlotsMid, sb::kBinsMaxMid, sb::kBinsThreadsAccum, 1, true>), gh, dim3(sb::kBinsThreadsAccum), 0, s, a);
-            else hipLaunchKernelGGL((sb::bins_accum_kernel<sb::kBinsSlotsMid, sb::kBinsMaxMid, sb::kBinsThreadsAccum, 2, true>), gh, dim3(sb::kBinsThreadsAccum), 0, s, a);
-         }
-         a.n_loci = n_big - n_heavy;
-         a.loci = (const int32_t *)(d + o_order) + n_small + n_heavy;
-         const dim3 gm((unsigned)std::min<int64_t>(a.n_loci, cap * 8));
-         // ... and on a table of 1024 slots / 512 bins (24 KB of LDS: six workgroups per CU instead of three; a locus of
-         // more bins is redone with the big table like any other overflow): 1.83 -> 1.41 ms (SBGPU_BINS_MID_SLOTS=2048 for A/B)
-         static const int mid_slots = sb::exp_env("SBGPU_BINS_MID_SLOTS") ? std::atoi(sb::exp_env("SBGPU_BINS_MID_SLOTS")) : 1024;
-         if (mid_threads == 256 && mid_slots == 1024 && compat_words == 1) hipLaunchKernelGGL((sb::bins_accum_kernel<1024, 512, 256, 1, true>), gm, dim3(256), 0, s, a);
-         else if (mid_threads == 256 && mid_slots == 1024) hipLaunchKernelGGL((sb::bins_accum_kernel<1024, 512, 256, 2, true>), gm, dim3(256), 0, s, a);
-         else if (mid_threads == 256 && compat_words == 1) hipLaunchKernelGGL((sb::bins_accum_kernel<sb::kBinsSlotsMid, sb::kBinsMaxMid, 256, 1, true>), gm, dim3(256), 0, s, a);
-         else if (mid_threads == 256) hipLaunchKernelGGL((sb::bins_accum_kernel<sb::kBinsSlotsMid, sb::kBinsMaxMid, 256, 2, true>), gm, dim3(256), 0, s, a);
-         else if (compat_words == 1) hipLaunchKernelGGL((sb::bins_accum_kernel<sb::kBinsSlotsMid, sb::kBinsMaxMid, 512, 1, true>), gm, dim3(512), 0, s, a);
-         else hipLaunchKernelGGL((sb::bins_accum_kernel<sb::kBinsSlotsMid, sb::kBinsMaxMid, 512, 2, true>), gm, dim3(512), 0, s, a);
-      } else
-      if (single_pass && compat_words == 1) hipLaunchKernelGGL((sb::bins_accum_kernel<sb::kBinsSlotsMid, sb::kBinsMaxMid, sb::kBinsThreadsAccum, 1, true>), grid, dim3(sb::kBinsThreadsAccum), 0, s, a);
-      else if (single_pass) hipLaunchKernelGGL((sb::bins_accum_kernel<sb::kBinsSlotsMid, sb::kBinsMaxMid, sb::kBinsThreadsAccum, 2, true>), grid, dim3(sb::kBinsThreadsAccum), 0, s, a);
-      else hipLaunchKernelGGL((sb::bins_locus_kernel<sb::kBinsSlotsMid, sb::kBinsMaxMid, sb::kBinsThreadsMid, true>), grid, dim3(sb::kBinsThreadsMid), 0, s, a);
-   }
-   SB_TRY(hipGetLastError());
-   sb::ctx_stage_end(c, s);
-   // bins / hits used per locus and the grouping kernels' flags, to the pinned words -- on the copy stream, behind an
-   // event of the main one, which goes straight on to the middle (a copy in the main stream holds the next kernel back
-   // by the hand-over to the DMA engine: 0.25 ms measured here)
-   auto fetch_rows = [&]() -> hipError_t {
-      hipError_t x = hipEventRecord(ev_acc, s);
-      if (x == hipSuccess) x = hipStreamWaitEvent(cs, ev_acc, 0);
-      if (x == hipSuccess) x = hipMemcpyAsync(nb, d + o_nb, (size_t)nl * 4, hipMemcpyDeviceToHost, cs);
-      if (x == hipSuccess) x = hipMemcpyAsync(nu, d + o_nu, (size_t)nl * 4, hipMemcpyDeviceToHost, cs);
-      if (x == hipSuccess) x = hipMemcpyAsync((void *)flags_h, d + o_flag, 8, hipMemcpyDeviceToHost, cs);
-      if (x == hipSuccess) x = hipEventRecord(ev_rows, cs);
-      return x;
-   };
-   // (the annotation's part goes up while the grouping kernels run)
-   if (!d_an) {
-      SB_TRY(hipMemcpyAsync(d3 + r_isoff, an->iso_off, (size_t)(nl + 1) * 8, hipMemcpyHostToDevice, cs));
-      SB_TRY(hipMemcpyAsync(d3 + r_segoff, an->seg_off, (size_t)(nl + 1) * 8, hipMemcpyHostToDevice, cs));
-      if (n_seg) {
-         SB_TRY(hipMemcpyAsync(d3 + r_segl, an->seg_left, (size_t)n_seg * 4, hipMemcpyHostToDevice, cs));
-         SB_TRY(hipMemcpyAsync(d3 + r_segr, an->seg_right, (size_t)n_seg * 4, hipMemcpyHostToDevice, cs));
-      }
-   }
-   const sb::DeviceIsoSegments *d_iso = hooks ? hooks->d_iso : nullptr;
-   if (!d_iso) {
-      SB_TRY(hipMemcpyAsync(d3 + r_isegoff, iso_seg_off.data(), (size_t)(n_iso + 1) * 8, hipMemcpyHostToDevice, cs));
-      if (!iso_seg_idx.empty()) SB_TRY(hipMemcpyAsync(d3 + r_isegidx, iso_seg_idx.data(), iso_seg_idx.size() * 4, hipMemcpyHostToDevice, cs));
-      if (n_iso) {
-         SB_TRY(hipMemcpyAsync(d3 + r_isoloc, iso_locus.data(), (size_t)n_iso * 4, hipMemcpyHostToDevice, cs));
-         SB_TRY(hipMemcpyAsync(d3 + r_isolen, iso_len.data(), (size_t)n_iso * 4, hipMemcpyHostToDevice, cs));
-      }
-   }
-   SB_TRY(hipEventRecord(ev_up, cs));
-   SB_TRY(fetch_rows());
-   // ---- the middle: rows scanned, bins packed, pairs counted and scanned -- behind the grouping kernels without a
-   // host round trip.  Its flags are a word of their own (o_flag + 4), cleared per launch: the middle may run a second
-   // time (below).
-   sb::BinsPackArgs pk;
+   R = pairs_in_layout(nl, n_iso, n_seg, iso_pre->seg_idx.size());
+   if ((e = ctx_scratch(c, 4, R.bytes, &d3)) != hipSuccess) return api_fail_hip(e, "hipMalloc");
+   // pinned host words for what comes back between the kernels (copies into pageable memory would hold the host until the
+   // stream has reached them)
+   H = bins_pinned_layout(nl);
+   if ((e = ctx_pinned(c, 0, H.bytes, &pin)) != hipSuccess) return api_fail(SBGPU_ENOMEM, hip_error_text("hipHostMalloc", e));
+   nb = (int32_t *)(pin + H.nb), nu = (int32_t *)(pin + H.nu);
+   flags_h = (volatile int32_t *)(pin + H.flag);
+   totals_h = (volatile int64_t *)(pin + H.tot);
+   SB_TRY(ctx_copy_stream(c, &cs));
+   SB_TRY(ctx_event(c, 0, &ev_up));
+   SB_TRY(ctx_event(c, 1, &ev_rows));
+   SB_TRY(ctx_event(c, 2, &ev_in));
+   SB_TRY(ctx_event(c, 4, &ev_acc));
+   return SBGPU_OK;
+}
+
+// the three kernel families' arguments from the layouts (a.n_loci / a.loci: per launch)
+void BinsCall::fill_args()
+{
+   a.n_loci = nl;
+   a.locus_hit_off = (const int64_t *)(d + L.hoff);
+   a.feat_off = dh->feat_off, a.feat_left = dh->feat_left, a.feat_right = dh->feat_right;
+   a.mass = d_mass;
+   a.compat_words = cw, a.key_words = kw;
+   a.compat = d_compat, a.key = d_key;
+   a.span = d_span ? d_span : (const uint64_t *)(d + L.span);
+   a.fhash = d_span ? d_fhash : (const uint32_t *)(d + L.fhash);
+   a.hit_bin_local = (int32_t *)(d + L.local);
+   a.bin_rep = (int32_t *)(d + L.rep);
+   a.bin_count = (int32_t *)(d + L.cnt);
+   a.bin_compat = (uint32_t *)(d + L.cmp);
+   a.dup = (uint8_t *)(d + L.dup);
+   a.n_bins = (int32_t *)(d + L.nb), a.n_used = (int32_t *)(d + L.nu);
+   a.flags = (int32_t *)(d + L.flag);
+
    pk.n_loci = nl;
    pk.locus_hit_off = a.locus_hit_off;
-   pk.row_off = (const int64_t *)(d + o_roff);
-   pk.compat_words = compat_words;
-   pk.key_words = key_words;
+   pk.row_off = (const int64_t *)(d + L.roff);
+   pk.compat_words = cw, pk.key_words = kw;
    pk.key = d_key;
-   pk.hit_bin_local = a.hit_bin_local;
-   pk.bin_rep = a.bin_rep;
-   pk.bin_count_in = a.bin_count;
-   pk.bin_compat_in = a.bin_compat;
-   pk.count = (int32_t *)(d2 + p_cnt);
-   pk.bin_key = (uint32_t *)(d2 + p_key);
-   pk.bin_compat = (uint32_t *)(d2 + p_cmp);
+   pk.hit_bin_local = a.hit_bin_local, pk.bin_rep = a.bin_rep, pk.bin_count_in = a.bin_count, pk.bin_compat_in = a.bin_compat;
+   pk.count = (int32_t *)(d2 + P.cnt);
+   pk.bin_key = (uint32_t *)(d2 + P.key);
+   pk.bin_compat = (uint32_t *)(d2 + P.cmp);
    pk.hit_bin = d_hit_bin;
-   pk.flags = a.flags + 1;
-   sb::PairsArgs pa;
+   pk.flags = a.flags + 1; // the middle's flags are a word of their own, cleared per launch: the middle may run twice
+
    pa.n_iso = n_iso;
-   pa.iso_locus = d_iso ? d_iso->locus : (const int32_t *)(d3 + r_isoloc);
-   pa.iso_off = d_iso_off;
+   pa.iso_locus = d_iso ? d_iso->locus : (const int32_t *)(d3 + R.isoloc);
+   pa.iso_off = d_an ? d_an->iso_off : (const int64_t *)(d3 + R.isoff);
    pa.row_off = pk.row_off;
-   pa.f_off = (const int64_t *)(d3 + r_foff);
-   pa.seg_off = d_an ? d_an->seg_off : (const int64_t *)(d3 + r_segoff);
-   pa.seg_left = d_an ? d_an->seg_left : (const uint32_t *)(d3 + r_segl);
-   pa.seg_right = d_an ? d_an->seg_right : (const uint32_t *)(d3 + r_segr);
-   pa.iso_seg_off = d_iso ? d_iso->seg_off : (const int64_t *)(d3 + r_isegoff);
-   pa.iso_seg_idx = d_iso ? d_iso->seg_idx : (const int32_t *)(d3 + r_isegidx);
-   pa.iso_len = d_iso ? d_iso->len : (const int32_t *)(d3 + r_isolen);
-   pa.compat_words = compat_words;
-   pa.key_words = key_words;
-   pa.bin_key = pk.bin_key;
-   pa.bin_compat = pk.bin_compat;
-   pa.pair_cnt = (int32_t *)(d3 + r_pcnt);
-   pa.seg_cnt = (int32_t *)(d3 + r_scnt);
-   pa.pair_off = (const int64_t *)(d3 + r_poff);
-   pa.pseg_off = (const int64_t *)(d3 + r_soff);
-   pa.pair_seg_off = nullptr;
+   pa.f_off = (const int64_t *)(d3 + R.foff);
+   pa.seg_off = d_an ? d_an->seg_off : (const int64_t *)(d3 + R.segoff);
+   pa.seg_left = d_an ? d_an->seg_left : (const uint32_t *)(d3 + R.segl);
+   pa.seg_right = d_an ? d_an->seg_right : (const uint32_t *)(d3 + R.segr);
+   pa.iso_seg_off = d_iso ? d_iso->seg_off : (const int64_t *)(d3 + R.isegoff);
+   pa.iso_seg_idx = d_iso ? d_iso->seg_idx : (const int32_t *)(d3 + R.isegidx);
+   pa.iso_len = d_iso ? d_iso->len : (const int32_t *)(d3 + R.isolen);
+   pa.compat_words = cw, pa.key_words = kw;
+   pa.bin_key = pk.bin_key, pa.bin_compat = pk.bin_compat;
+   pa.pair_cnt = (int32_t *)(d3 + R.pcnt), pa.seg_cnt = (int32_t *)(d3 + R.scnt);
+   pa.pair_off = (const int64_t *)(d3 + R.poff), pa.pseg_off = (const int64_t *)(d3 + R.soff);
+   pa.pair_seg_off = nullptr; // the pairs' arena: fill_pairs
    pa.pair_seg_lens = pa.pair_mask = nullptr;
    pa.pair_iso_len = nullptr;
    pa.pair_out_index = nullptr;
    pa.flags = a.flags + 1;
-   // one wave per locus (bins_pairs_locus_kernel) for loci of up to 64 isoforms, the thread-per-isoform kernel for the
-   // others; SBGPU_PAIRS_BY_ISOFORM=1: the latter everywhere (A/B)
-   static const bool pairs_by_iso = sb::exp_env("SBGPU_PAIRS_BY_ISOFORM") && std::atoi(sb::exp_env("SBGPU_PAIRS_BY_ISOFORM")) != 0;
-   bool any_wide_locus = false;
-   for (int64_t l = 0; l < nl && !any_wide_locus; ++l) any_wide_locus = an->iso_off[l + 1] - an->iso_off[l] > 64;
-   pa.only_wide_loci = pairs_by_iso ? 0 : 1;
-   const unsigned lgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nl + 3) / 4, cap * 8));
-   const unsigned pgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_iso + 255) / 256, cap * 4));
-   auto launch_middle = [&]() -> hipError_t {
-      hipError_t x = hipMemsetAsync(d + o_flag + 4, 0, 4, s);
-      if (x == hipSuccess) x = hipStreamWaitEvent(s, ev_up, 0);
-      if (x != hipSuccess) return x;
-      sb::ctx_stage_begin(c, "bins_scan_*_kernel<rows> + bins_pack_kernel", s);
-      int64_t *part_a = (int64_t *)(d3 + r_part), *part_b = part_a + std::max(row_tiles, iso_tiles) + 1;
-      sb::ScanArgs sr = {nl, a.n_bins, nullptr, d_iso_off, (int64_t *)(d + o_roff), (int64_t *)(d3 + r_foff), part_a, part_b, (int64_t *)(d3 + r_tot)};
-      hipLaunchKernelGGL(sb::bins_scan_tiles_kernel<0>, dim3((unsigned)row_tiles), dim3(256), 0, s, sr);
-      hipLaunchKernelGGL(sb::bins_scan_parts_kernel, dim3(1), dim3(256), 0, s, sr, row_tiles);
-      hipLaunchKernelGGL(sb::bins_scan_apply_kernel<0>, dim3((unsigned)row_tiles), dim3(256), 0, s, sr);
-      hipLaunchKernelGGL(sb::bins_pack_kernel, dim3((unsigned)(nl < cap ? nl : cap)), dim3(256), 0, s, pk);
-      sb::ctx_stage_end(c, s);
-      sb::ctx_stage_begin(c, "bins_pairs_kernel<count> + bins_scan_*_kernel<pairs>", s);
-      if (pairs_by_iso || any_wide_locus) hipLaunchKernelGGL(sb::bins_pairs_kernel<false>, dim3(pgrid), dim3(256), 0, s, pa);
-      if (!pairs_by_iso) hipLaunchKernelGGL(sb::bins_pairs_locus_kernel<false>, dim3(lgrid), dim3(256), 0, s, pa, nl);
-      sb::ScanArgs sp = {n_iso, pa.pair_cnt, pa.seg_cnt, nullptr, (int64_t *)(d3 + r_poff), (int64_t *)(d3 + r_soff), part_a, part_b, (int64_t *)(d3 + r_tot) + 2};
-      hipLaunchKernelGGL(sb::bins_scan_tiles_kernel<1>, dim3((unsigned)iso_tiles), dim3(256), 0, s, sp);
-      hipLaunchKernelGGL(sb::bins_scan_parts_kernel, dim3(1), dim3(256), 0, s, sp, n_iso ? iso_tiles : 0);
-      hipLaunchKernelGGL(sb::bins_scan_apply_kernel<1>, dim3((unsigned)iso_tiles), dim3(256), 0, s, sp);
-      sb::ctx_stage_end(c, s);
-      if ((x = hipGetLastError()) != hipSuccess) return x;
-      x = hipMemcpyAsync((void *)totals_h, d3 + r_tot, 32, hipMemcpyDeviceToHost, s);
-      if (x == hipSuccess) x = hipMemcpyAsync((void *)flags_h, d + o_flag, 8, hipMemcpyDeviceToHost, s);
-      return x;
-   };
-   // Where nothing on the host has to come between (the usual case: single-pass kernels, hit -> bin not asked for), the
-   // middle is launched before the bin counts are back; should the counts then call for a fix-up -- a locus for the big
-   // table, fractional masses -- the fix-up runs and the middle is launched again over its result.
-   const bool speculative = single_pass && !d_hit_bin;
+   // one wave per locus (bins_pairs_locus_kernel) for loci of up to 64 isoforms, the thread-per-isoform kernel for the others
+   pa.only_wide_loci = 1;
+   lgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nl + 3) / 4, cap * 8));
+   pgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_iso + 255) / 256, cap * 4));
+}
+
+// Uploads on the copy stream, beside whatever the main stream still runs (the caller's exon-bin kernel): a copy in the main
+// stream between two kernels costs the hand-over to the DMA engine and back, 0.3 ms each way measured.  First what the grouping
+// kernels read (hit offsets, the loci's order), then the annotation's part of the pairs' inputs.  (Streams share hardware
+// queues -- the copy stream may sit in the main stream's queue and then runs in issue order with it -- so nothing here counts on
+// the overlap.)
+int BinsCall::upload_and_group()
+{
+   SB_TRY(hipMemcpyAsync(d + L.hoff, locus_hit_off, (size_t)(nl + 1) * 8, hipMemcpyHostToDevice, cs));
+   hipLaunchKernelGGL(bins_zero_kernel, dim3(1), dim3(256), 0, cs, (uint4 *)(d + L.flag), (int64_t)16);
+   SB_TRY(hipGetLastError());
+   order = bins_locus_order(nl, locus_hit_off, nh);
+   steps = bins_group_steps(order.n_small, order.n_heavy, order.n_mid, cw, kw);
+   // The bins' counts and compat words are [n_hits]-sized (a locus' bins sit at its hit offset): 1.3 GB for 1.6e8 hits,
+   // 0.18 ms to zero at the memory's rate.  Only bins_locus_kernel's global atomics need the zeros -- the two-pass form
+   // and the big table; the single-pass kernels write every entry they own -- so they are made where those run.
+   if (steps.zero_first) {
+      const int64_t n16 = (int64_t)(L.zero_bytes / 16); // (the arena's parts are 256-byte multiples)
+      hipLaunchKernelGGL(bins_zero_kernel, dim3((unsigned)std::min<int64_t>((n16 + 255) / 256, cap * 4)), dim3(256), 0, cs, (uint4 *)(d + L.cnt), n16);
+      SB_TRY(hipGetLastError());
+   }
+   SB_TRY(hipMemcpyAsync(d + L.order, order.order.data(), (size_t)nl * 4, hipMemcpyHostToDevice, cs));
+   SB_TRY(hipEventRecord(ev_in, cs));
+   SB_TRY(hipStreamWaitEvent(s, ev_in, 0));
+   ctx_stage_begin(c, steps.single_pass ? "bins_accum_kernel" : "bins_locus_kernel", s);
+   for (int i = 0; i < steps.n_steps; ++i) {
+      a.n_loci = steps.steps[i].count;
+      a.loci = (const int32_t *)(d + L.order) + steps.steps[i].first;
+      SB_TRY(launch_group_step(steps.steps[i], cap, s, a));
+   }
+   ctx_stage_end(c, s);
+   // (the annotation's part goes up while the grouping kernels run)
+   if (!d_an) {
+      SB_TRY(hipMemcpyAsync(d3 + R.isoff, an->iso_off, (size_t)(nl + 1) * 8, hipMemcpyHostToDevice, cs));
+      SB_TRY(hipMemcpyAsync(d3 + R.segoff, an->seg_off, (size_t)(nl + 1) * 8, hipMemcpyHostToDevice, cs));
+      if (n_seg) {
+         SB_TRY(hipMemcpyAsync(d3 + R.segl, an->seg_left, (size_t)n_seg * 4, hipMemcpyHostToDevice, cs));
+         SB_TRY(hipMemcpyAsync(d3 + R.segr, an->seg_right, (size_t)n_seg * 4, hipMemcpyHostToDevice, cs));
+      }
+   }
+   if (!d_iso) {
+      SB_TRY(hipMemcpyAsync(d3 + R.isegoff, iso_pre->seg_off.data(), (size_t)(n_iso + 1) * 8, hipMemcpyHostToDevice, cs));
+      if (!iso_pre->seg_idx.empty()) SB_TRY(hipMemcpyAsync(d3 + R.isegidx, iso_pre->seg_idx.data(), iso_pre->seg_idx.size() * 4, hipMemcpyHostToDevice, cs));
+      if (n_iso) {
+         SB_TRY(hipMemcpyAsync(d3 + R.isoloc, iso_pre->locus.data(), (size_t)n_iso * 4, hipMemcpyHostToDevice, cs));
+         SB_TRY(hipMemcpyAsync(d3 + R.isolen, iso_pre->len.data(), (size_t)n_iso * 4, hipMemcpyHostToDevice, cs));
+      }
+   }
+   SB_TRY(hipEventRecord(ev_up, cs));
+   SB_TRY(fetch_rows());
+   return SBGPU_OK;
+}
+
+// Bins / hits used per locus and the grouping kernels' flags, to the pinned words -- on the copy stream, behind an event of
+// the main one, which goes straight on to the middle (a copy in the main stream holds the next kernel back by the hand-over
+// to the DMA engine: 0.25 ms measured here)
+hipError_t BinsCall::fetch_rows()
+{
+   hipError_t x = hipEventRecord(ev_acc, s);
+   if (x == hipSuccess) x = hipStreamWaitEvent(cs, ev_acc, 0);
+   if (x == hipSuccess) x = hipMemcpyAsync(nb, d + L.nb, (size_t)nl * 4, hipMemcpyDeviceToHost, cs);
+   if (x == hipSuccess) x = hipMemcpyAsync(nu, d + L.nu, (size_t)nl * 4, hipMemcpyDeviceToHost, cs);
+   if (x == hipSuccess) x = hipMemcpyAsync((void *)flags_h, d + L.flag, 8, hipMemcpyDeviceToHost, cs);
+   if (x == hipSuccess) x = hipEventRecord(ev_rows, cs);
+   return x;
+}
+
+// The middle: rows scanned, bins packed, pairs counted and scanned -- behind the grouping kernels without a host round trip
+hipError_t BinsCall::launch_middle()
+{
+   hipError_t x = hipMemsetAsync(d + L.flag + 4, 0, 4, s);
+   if (x == hipSuccess) x = hipStreamWaitEvent(s, ev_up, 0);
+   if (x != hipSuccess) return x;
+   ctx_stage_begin(c, "bins_scan_*_kernel<rows> + bins_pack_kernel", s);
+   int64_t *part_a = (int64_t *)(d3 + R.part), *part_b = part_a + std::max(R.row_tiles, R.iso_tiles) + 1, *tot = (int64_t *)(d3 + R.tot);
+   ScanArgs sr = {nl, a.n_bins, nullptr, pa.iso_off, (int64_t *)(d + L.roff), (int64_t *)(d3 + R.foff), part_a, part_b, tot};
+   hipLaunchKernelGGL(bins_scan_tiles_kernel<0>, dim3((unsigned)R.row_tiles), dim3(256), 0, s, sr);
+   hipLaunchKernelGGL(bins_scan_parts_kernel, dim3(1), dim3(256), 0, s, sr, R.row_tiles);
+   hipLaunchKernelGGL(bins_scan_apply_kernel<0>, dim3((unsigned)R.row_tiles), dim3(256), 0, s, sr);
+   hipLaunchKernelGGL(bins_pack_kernel, dim3((unsigned)(nl < cap ? nl : cap)), dim3(256), 0, s, pk);
+   ctx_stage_end(c, s);
+   ctx_stage_begin(c, "bins_pairs_kernel<count> + bins_scan_*_kernel<pairs>", s);
+   if (any_wide_locus) hipLaunchKernelGGL(bins_pairs_kernel<false>, dim3(pgrid), dim3(256), 0, s, pa);
+   hipLaunchKernelGGL(bins_pairs_locus_kernel<false>, dim3(lgrid), dim3(256), 0, s, pa, nl);
+   ScanArgs sp = {n_iso, pa.pair_cnt, pa.seg_cnt, nullptr, (int64_t *)(d3 + R.poff), (int64_t *)(d3 + R.soff), part_a, part_b, tot + 2};
+   hipLaunchKernelGGL(bins_scan_tiles_kernel<1>, dim3((unsigned)R.iso_tiles), dim3(256), 0, s, sp);
+   hipLaunchKernelGGL(bins_scan_parts_kernel, dim3(1), dim3(256), 0, s, sp, n_iso ? R.iso_tiles : 0);
+   hipLaunchKernelGGL(bins_scan_apply_kernel<1>, dim3((unsigned)R.iso_tiles), dim3(256), 0, s, sp);
+   ctx_stage_end(c, s);
+   if ((x = hipGetLastError()) != hipSuccess) return x;
+   x = hipMemcpyAsync((void *)totals_h, d3 + R.tot, 32, hipMemcpyDeviceToHost, s);
+   if (x == hipSuccess) x = hipMemcpyAsync((void *)flags_h, d + L.flag, 8, hipMemcpyDeviceToHost, s);
+   return x;
+}
+
+// a list of loci for a fix-up kernel, once the stream is through with the list before it (the caller keeps `loci` alive
+// until the stream has read it)
+hipError_t BinsCall::serve_list(const std::vector<int32_t> &loci)
+{
+   hipError_t x = hipStreamSynchronize(s);
+   if (x == hipSuccess) x = hipMemcpyAsync(d + L.order, loci.data(), loci.size() * 4, hipMemcpyHostToDevice, s);
+   a.n_loci = (int64_t)loci.size();
+   a.loci = (const int32_t *)(d + L.order);
+   return x;
+}
+
+// The counts come back; what they call for (bins_schedule.h) runs, or the device form declines
+int BinsCall::fix_up()
+{
+   speculative = bins_speculative(steps.single_pass, d_hit_bin != nullptr);
    if (speculative) SB_TRY(launch_middle());
    SB_TRY(hipEventSynchronize(ev_rows));
    int32_t flags = flags_h[0];
-   bool fixed_up = false;
-   {
-      // loci the middle table could not hold: again, with the big one
-      std::vector<int32_t> redo;
-      for (int64_t l = 0; l < nl; ++l)
-         if (nb[(size_t)l] < 0) redo.push_back((int32_t)l);
-      if (!redo.empty()) {
-         fixed_up = true;
-         SB_TRY(hipStreamSynchronize(s));
-         SB_TRY(hipMemcpyAsync(d + o_order, redo.data(), redo.size() * 4, hipMemcpyHostToDevice, s));
-         a.n_loci = (int64_t)redo.size();
-         a.loci = (const int32_t *)(d + o_order);
-         if (single_pass) { // these loci's entries were never zeroed (the other loci's stand as they are)
-            hipLaunchKernelGGL(sb::bins_zero_loci_kernel, dim3((unsigned)std::min<int64_t>((int64_t)redo.size(), cap)), dim3(256), 0, s, a);
-            SB_TRY(hipGetLastError());
-         }
-         hipLaunchKernelGGL((sb::bins_locus_kernel<sb::kBinsSlotsBig, sb::kBinsMaxBig, sb::kBinsThreadsBig>),
-                            dim3((unsigned)std::min<int64_t>((int64_t)redo.size(), cap)), dim3(sb::kBinsThreadsBig), 0, s, a);
+   const std::vector<int32_t> redo = bins_redo_list(nb, nl);
+   if (!redo.empty()) {
+      fixed_up = true;
+      SB_TRY(serve_list(redo));
+      const dim3 grid((unsigned)std::min<int64_t>((int64_t)redo.size(), cap));
+      if (steps.single_pass) { // these loci's entries were never zeroed (the other loci's stand as they are)
+         hipLaunchKernelGGL(bins_zero_loci_kernel, grid, dim3(256), 0, s, a);
          SB_TRY(hipGetLastError());
-         SB_TRY(fetch_rows());
-         SB_TRY(hipEventSynchronize(ev_rows));
-         flags = flags_h[0];
       }
+      hipLaunchKernelGGL((bins_locus_kernel<kBinsSlotsBig, kBinsMaxBig, kBinsThreadsBig>), grid, dim3(kBinsThreadsBig), 0, s, a);
+      SB_TRY(hipGetLastError());
+      SB_TRY(fetch_rows());
+      SB_TRY(hipEventSynchronize(ev_rows));
+      flags = flags_h[0];
    }
-   // hit -> bin: the single-pass kernels leave it out; it is made where somebody reads it (the caller's hit_bin, the
-   // ordered masses below).  Loci the big table served have theirs already.
-   const bool want_local = hooks && hooks->d_hit_bin_local;
-   if (single_pass && (d_hit_bin || want_local || flags == sb::kBinsFractional) && nh) {
-      std::vector<int32_t> todo;
-      for (int64_t l = 0; l < nl; ++l)
-         if (nb[(size_t)l] <= sb::kBinsMaxMid) todo.push_back((int32_t)l);
+   if (bins_assign_wanted(steps.single_pass, d_hit_bin != nullptr, want_local, flags, nh)) {
+      const std::vector<int32_t> todo = bins_assign_list(nb, nl);
       if (!todo.empty()) {
-         SB_TRY(hipStreamSynchronize(s));
-         SB_TRY(hipMemcpyAsync(d + o_order, todo.data(), todo.size() * 4, hipMemcpyHostToDevice, s));
-         a.n_loci = (int64_t)todo.size();
-         a.loci = (const int32_t *)(d + o_order);
-         hipLaunchKernelGGL((sb::bins_assign_kernel<sb::kBinsSlotsMid, sb::kBinsThreadsMid>),
-                            dim3((unsigned)std::min<int64_t>((int64_t)todo.size(), cap * 4)), dim3(sb::kBinsThreadsMid), 0, s, a);
+         SB_TRY(serve_list(todo));
+         hipLaunchKernelGGL((bins_assign_kernel<kBinsSlotsMid, kBinsThreadsMid>), dim3((unsigned)std::min<int64_t>((int64_t)todo.size(), cap * 4)),
+                            dim3(kBinsThreadsMid), 0, s, a);
          SB_TRY(hipGetLastError());
          SB_TRY(hipStreamSynchronize(s)); // (`todo` leaves scope)
       }
    }
-   if (flags == sb::kBinsFractional) {
+   if (flags == kBinsFractional) {
       // fractional masses (multi-mapped reads): the bins stand, their masses are summed again in float, in the
       // order of the reference's std::set (bins_device.h)
       fixed_up = true;
-      std::vector<int32_t> all((size_t)nl);
-      for (int64_t l = 0; l < nl; ++l) all[(size_t)l] = (int32_t)l;
-      SB_TRY(hipStreamSynchronize(s));
-      SB_TRY(hipMemcpyAsync(d + o_order, all.data(), (size_t)nl * 4, hipMemcpyHostToDevice, s));
-      SB_TRY(hipMemsetAsync(d + o_flag, 0, 4, s));
-      a.n_loci = nl;
-      a.loci = (const int32_t *)(d + o_order);
-      hipLaunchKernelGGL(sb::bins_ordered_mass_kernel, dim3((unsigned)std::min<int64_t>(nl, cap * 4)), dim3(256), 0, s, a);
+      const std::vector<int32_t> all = bins_loci_where(nb, nl, [](int32_t) { return true; });
+      SB_TRY(serve_list(all));
+      SB_TRY(hipMemsetAsync(d + L.flag, 0, 4, s));
+      hipLaunchKernelGGL(bins_ordered_mass_kernel, dim3((unsigned)std::min<int64_t>(nl, cap * 4)), dim3(256), 0, s, a);
       SB_TRY(hipGetLastError());
-      SB_TRY(hipMemcpyAsync((void *)flags_h, d + o_flag, 8, hipMemcpyDeviceToHost, s));
+      SB_TRY(hipMemcpyAsync((void *)flags_h, d + L.flag, 8, hipMemcpyDeviceToHost, s));
       SB_TRY(hipStreamSynchronize(s));
       flags = flags_h[0];
    }
-   if (flags) {
-      (void)hipStreamSynchronize(s);
-      std::string why = "sbgpu_bins_create_device: not covered by the device form:";
-      if (flags & sb::kBinsUnsorted) why += " hits of a locus are not sorted by (left, right);";
-      if (flags & sb::kBinsFractional) why += " fractional hit masses next to another obstacle;";
-      if (flags & sb::kBinsTableFull) why += " a locus has more bins than the LDS table holds;";
-      if (flags & sb::kBinsRunTooLong) why += " fractional masses and more than 48 fragments of one bin starting at one position;";
-      return bail(SBGPU_EUNSUPPORTED, why + " use sbgpu_bins_create");
-   }
+   if (flags) return api_fail(SBGPU_EUNSUPPORTED, bins_decline_reason(flags));
    stage("group kernel");
-   // ---- host: the same prefix sums (the handle, the caller's plan), while the middle runs
-   std::vector<int64_t> row_off((size_t)nl + 1, 0), f_off((size_t)nl + 1, 0);
-   int64_t used = 0;
-   for (int64_t l = 0; l < nl; ++l) {
-      row_off[(size_t)l + 1] = row_off[(size_t)l] + nb[(size_t)l];
-      f_off[(size_t)l + 1] = f_off[(size_t)l] + (int64_t)nb[(size_t)l] * (an->iso_off[l + 1] - an->iso_off[l]);
-      used += nu[(size_t)l];
-   }
-   const int64_t n_bins = row_off[(size_t)nl];
-   if (hooks && hooks->rows_known) hooks->rows_known(row_off.data(), f_off.data());
-   // the pairs' arena, allocated by the size of the last call's while the middle runs (none yet, or too small: below)
-   sb::DevicePairs dp;
-   size_t dp_bytes = sb::ctx_pairs_hint(c);
-   if (dp_bytes && sb::dev_take(dp_bytes, &dp.arena, &dp.capacity) != hipSuccess) dp.arena = nullptr, dp.capacity = 0;
-   dp_bytes = dp.capacity;
-   auto bail3 = [&](int code, const std::string &msg) {
-      (void)hipStreamSynchronize(s);
-      sb::dev_give(dp.arena, dp.capacity);
-      return bail(code, msg);
-   };
-#define SB_TRY3(expr)                                                                          \
-   do {                                                                                        \
-      hipError_t e_ = (expr);                                                                  \
-      if (e_ != hipSuccess) return bail3(SBGPU_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-   } while (0)
-   if (!speculative || fixed_up) SB_TRY3(launch_middle());
-   SB_TRY3(hipStreamSynchronize(s));
-   flags = flags_h[1];
-   if (totals_h[0] != n_bins || totals_h[1] != f_off[(size_t)nl]) return bail3(SBGPU_EHIP, "sbgpu_bins_create_device: device and host prefix sums differ");
-   if (flags & sb::kBinsMassOverflow) return bail3(SBGPU_EUNSUPPORTED, "sbgpu_bins_create_device: a bin's mass reaches 2^24; use sbgpu_bins_create");
-   if (flags & (sb::kPairsNotUnder | sb::kPairsForeignSegment))
-      return bail3(SBGPU_EUNSUPPORTED, "sbgpu_bins_create_device: a bin does not sit under an isoform it is compatible with; sbgpu_bins_create reports the details");
+   return SBGPU_OK;
+}
+
+// The host's prefix sums while the middle runs, the caller's hook, the pairs' arena by the last call's size; then the
+// middle's totals and flags
+int BinsCall::finish_middle()
+{
+   rows = bins_rows(nb, nu, an->iso_off, nl);
+   if (hooks && hooks->rows_known) hooks->rows_known(rows.row_off.data(), rows.f_off.data());
+   const size_t hint = ctx_pairs_hint(c); // (none yet, or too small: fill_pairs)
+   if (hint && dev_take(hint, &dp.arena, &dp.capacity) != hipSuccess) dp.arena = nullptr, dp.capacity = 0;
+   if (!speculative || fixed_up) SB_TRY(launch_middle());
+   SB_TRY(hipStreamSynchronize(s));
+   const int32_t flags = flags_h[1];
+   if (totals_h[0] != rows.row_off[(size_t)nl] || totals_h[1] != rows.f_off[(size_t)nl])
+      return api_fail(SBGPU_EHIP, "sbgpu_bins_create_device: device and host prefix sums differ");
+   if (flags & kBinsMassOverflow) return api_fail(SBGPU_EUNSUPPORTED, "sbgpu_bins_create_device: a bin's mass reaches 2^24; use sbgpu_bins_create");
+   if (flags & (kPairsNotUnder | kPairsForeignSegment))
+      return api_fail(SBGPU_EUNSUPPORTED, "sbgpu_bins_create_device: a bin does not sit under an isoform it is compatible with; sbgpu_bins_create reports the details");
    stage("pack + pairs count");
-   dp.any_wide = (flags & sb::kPairsWide) != 0;
+   dp.any_wide = (flags & kPairsWide) != 0;
    dp.n_pairs = totals_h[2];
    dp.n_pair_segs = totals_h[3];
-   size_t off4 = 0;
-   dp.o_seg_off = off4; off4 += up(((size_t)dp.n_pairs + 1) * 8);
-   dp.o_out_index = off4; off4 += up(((size_t)dp.n_pairs + 1) * 8);
-   dp.o_seg_lens = off4; off4 += up(((size_t)dp.n_pair_segs + 1) * 4);
-   dp.o_mask = off4; off4 += up(((size_t)dp.n_pairs + 1) * 4);
-   dp.o_iso_len = off4; off4 += up(((size_t)dp.n_pairs + 1) * 4);
-   if (off4 > dp_bytes) {
-      sb::dev_give(dp.arena, dp.capacity);
-      dp.arena = nullptr;
-      e = sb::dev_take(off4, &dp.arena, &dp.capacity);
-      if (e != hipSuccess) return bail3(e == hipErrorOutOfMemory ? SBGPU_ENOMEM : SBGPU_EHIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+   return SBGPU_OK;
+}
+
+int BinsCall::fill_pairs()
+{
+   const PairsLayout Q = pairs_layout(dp.n_pairs, dp.n_pair_segs);
+   dp.o_seg_off = Q.seg_off, dp.o_out_index = Q.out_index, dp.o_seg_lens = Q.seg_lens, dp.o_mask = Q.mask, dp.o_iso_len = Q.iso_len;
+   if (Q.bytes > dp.capacity) {
+      dev_give(dp.arena, dp.capacity);
+      dp.arena = nullptr, dp.capacity = 0;
+      const hipError_t e = dev_take(Q.bytes, &dp.arena, &dp.capacity);
+      if (e != hipSuccess) return api_fail_hip(e, "hipMalloc");
    }
-   sb::ctx_set_pairs_hint(c, off4);
+   ctx_set_pairs_hint(c, Q.bytes);
    pa.pair_seg_off = (int64_t *)(dp.arena + dp.o_seg_off);
    pa.pair_seg_lens = (uint32_t *)(dp.arena + dp.o_seg_lens);
    pa.pair_mask = (uint32_t *)(dp.arena + dp.o_mask);
    pa.pair_iso_len = (int32_t *)(dp.arena + dp.o_iso_len);
    pa.pair_out_index = (int64_t *)(dp.arena + dp.o_out_index);
-   sb::ctx_stage_begin(c, "bins_pairs_kernel<fill>", s);
-   if (pairs_by_iso || any_wide_locus) hipLaunchKernelGGL(sb::bins_pairs_kernel<true>, dim3(pgrid), dim3(256), 0, s, pa);
-   if (!pairs_by_iso) hipLaunchKernelGGL(sb::bins_pairs_locus_kernel<true>, dim3(lgrid), dim3(256), 0, s, pa, nl);
-   sb::ctx_stage_end(c, s);
-   SB_TRY3(hipGetLastError());
+   ctx_stage_begin(c, "bins_pairs_kernel<fill>", s);
+   if (any_wide_locus) hipLaunchKernelGGL(bins_pairs_kernel<true>, dim3(pgrid), dim3(256), 0, s, pa);
+   hipLaunchKernelGGL(bins_pairs_locus_kernel<true>, dim3(lgrid), dim3(256), 0, s, pa, nl);
+   ctx_stage_end(c, s);
+   SB_TRY(hipGetLastError());
    stage("pairs fill launch");
+   return SBGPU_OK;
+}
+
+// the caller's kernels behind the grouping (bin weights, EM) go into the stream, then the handle takes the two arenas over
+int BinsCall::make_handle()
+{
    if (want_local) *hooks->d_hit_bin_local = a.hit_bin_local;
-   // the caller's kernels behind the grouping (bin weights, EM) go into the stream now
    if (hooks && hooks->after_pairs) {
-      const sb::DeviceGrouping g = {row_off.data(), f_off.data(), n_bins, f_off[(size_t)nl], (const int32_t *)(d2 + p_cnt), &dp};
+      const DeviceGrouping g = {rows.row_off.data(), rows.f_off.data(), rows.row_off[(size_t)nl], rows.f_off[(size_t)nl], (const int32_t *)(d2 + P.cnt), &dp};
       const int rc_after = hooks->after_pairs(g);
-      if (rc_after != SBGPU_OK) {
-         (void)hipStreamSynchronize(s);
-         sb::dev_give(dp.arena, dp.capacity);
-         return rc_after;
-      }
+      if (rc_after != SBGPU_OK) return rc_after;
    }
-#undef SB_TRY3
-#undef SB_TRY
-   const sb::DeviceBinArrays dba = {d2, d2_cap, p_cnt, p_key, p_cmp};
-   const int rc = sb::bins_from_groups(an, compat_words, key_words, row_off.data(), dba, used, &dp, &iso_pre->len, out);
-   if (rc != SBGPU_OK) {
-      (void)hipStreamSynchronize(s);
-      sb::dev_give(dp.arena, dp.capacity);
-   } else {
-      d2 = nullptr; // the handle's now (d2_guard lets go)
-   }
+   const DeviceBinArrays dba = {d2, d2_cap, P.cnt, P.key, P.cmp};
+   const int rc = bins_from_groups(an, cw, kw, rows.row_off.data(), dba, rows.used, &dp, &iso_pre->len, out);
+   if (rc == SBGPU_OK) d2 = nullptr, dp.arena = nullptr; // the handle's now
    stage("handle");
+   return rc;
+}
+#undef SB_TRY
+} // namespace
+
+int bins_create_device_impl(sbgpu_ctx_t *c, const sbgpu_annotation_t *an, const sbgpu_hits_t *dh, const float *d_mass,
+                            const int64_t *locus_hit_off, int32_t compat_words, int32_t key_words, const uint32_t *d_compat,
+                            const uint32_t *d_key, int64_t *d_hit_bin, void *stream, const IsoSegments *iso_pre, sbgpu_bins_t **out,
+                            const uint64_t *d_span, const uint32_t *d_fhash, const GroupingHooks *hooks)
+{
+   BinsCall call = {c, an, dh, d_mass, locus_hit_off, compat_words, key_words, d_compat, d_key, d_hit_bin, (hipStream_t)stream, iso_pre, out, d_span, d_fhash, hooks};
+   int rc = call.validate();
+   if (rc == SBGPU_OK) rc = call.take_memory();
+   if (rc == SBGPU_OK) call.fill_args();
+   if (rc == SBGPU_OK) rc = call.upload_and_group();
+   if (rc == SBGPU_OK) rc = call.fix_up();
+   if (rc == SBGPU_OK) rc = call.finish_middle();
+   if (rc == SBGPU_OK) rc = call.fill_pairs();
+   if (rc == SBGPU_OK) rc = call.make_handle();
    return rc;
 }
 } // namespace sb

@@ -179,35 +179,9 @@ __device__ __forceinline__ void exonbin_hit(const ExonBinArgs &a, int64_t hidx, 
    }
 }
 
-// ------------------------------------------------------------------ per-lane form
-// Every lane walks the tables of its own hit's locus: divergent loops, vector loads.  The wave
-// form below falls back to it for hits it does not cover; it is also a kernel of its own
-// (SBGPU_EXONBIN_LANE=1, A/B measurements).
-__global__ __launch_bounds__(256) void exonbin_lane_kernel(ExonBinArgs a)
-{
-   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-   for (int64_t hidx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; hidx < a.n_hits; hidx += stride) {
-      const int64_t f0 = a.feat_off[hidx];
-      const int nf = (int)(a.feat_off[hidx + 1] - f0);
-      if (nf <= kExonBinRegFeats) {
-         RegHit h;
-         h.nf = nf;
-#pragma unroll
-         for (int i = 0; i < kExonBinRegFeats; ++i) {
-            const bool in = i < nf;
-            h.c[i] = in ? a.feat_code[f0 + i] : (uint8_t)2;
-            h.l[i] = in ? a.feat_left[f0 + i] : 0u;
-            h.r[i] = in ? a.feat_right[f0 + i] : 0u;
-         }
-         exonbin_hit(a, hidx, h);
-      } else {
-         MemHit h = {a.feat_code + f0, a.feat_left + f0, a.feat_right + f0, nf};
-         exonbin_hit(a, hidx, h);
-      }
-   }
-}
-
 // ------------------------------------------------------------------ wave form
+// (exonbin_hit above is the per-lane form -- every lane walks the tables of its own hit's locus: divergent loops, vector
+// loads -- which the wave form falls back to for the hits it does not cover)
 // Hits arrive sorted by locus and position, so the 64 hits of a wave nearly always share one
 // locus and a short stretch of it.  The wave then walks the locus' tables ONCE, uniformly:
 // exon and segment coordinates come through the scalar cache into SGPRs (constant address

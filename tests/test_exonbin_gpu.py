@@ -290,8 +290,9 @@ def test_device_pairs_for_narrow_and_wide_loci_in_one_call(ctx):
         np.testing.assert_array_equal(x, y)
 
 
-def group_both_ways(ctx, annot, hits, compat, key):
-    """(device bins or None, host bins) for arbitrary word arrays (they need not come from the kernel)."""
+def group_both_ways(ctx, annot, hits, compat, key, want_hit_bin=True, host=None):
+    """(device bins or None, host bins) for arbitrary word arrays (they need not come from the kernel).
+    want_hit_bin=False: the device form is not asked for hit -> bin (its hit_bin stays None); host: bins made earlier."""
     import ctypes as C
     import torch
     from strawberry_amd import exonbin as eb
@@ -305,10 +306,11 @@ def group_both_ways(ctx, annot, hits, compat, key):
     ht = _lib.sbgpu_hits_t(hits.n_hits, d["hit_locus"].data_ptr(), d["feat_off"].data_ptr(), d["feat_code"].data_ptr(),
                            d["feat_left"].data_ptr(), d["feat_right"].data_ptr())
     bd = eb.LocusBins.on_device(ctx, annot, hits, ht, d_mass.data_ptr(), compat.shape[1], key.shape[1], d_compat.data_ptr(),
-                                d_key.data_ptr(), d_hit_bin.data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if bd is not None:
+                                d_key.data_ptr(), d_hit_bin.data_ptr() if want_hit_bin else None,
+                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if bd is not None and want_hit_bin:
         bd.hit_bin = d_hit_bin.cpu().numpy()
-    return bd, eb.LocusBins(annot, hits, compat, key)
+    return bd, host if host is not None else eb.LocusBins(annot, hits, compat, key)
 
 
 def test_device_grouping_multiword_keys_and_table_limit(ctx):
@@ -396,6 +398,48 @@ def test_device_grouping_single_pass_with_a_locus_for_the_big_table(ctx):
 
 def bins_arrays_no_pairs(b):
     return [b.row_off, b.f_off, b.count, b.bin_key, b.bin_compat, np.asarray(b.hit_bin)]
+
+
+def test_device_grouping_heavy_launch_and_light_table_overflow(ctx):
+    """One call whose loci take every launch of the single-pass form (csrc/bins_schedule.h: bins_group_steps): a heavy locus
+    (>= 8192 hits and >= 3 x the mean) on the 1024-thread kernel, whose 513-1400 bins only its table holds; a middle locus
+    with more bins than the light table's 512, redone by the big table; a middle locus that fits; loci of exactly 256 hits
+    (small) and 257 (middle); two small ones and an empty one.  With hit -> bin asked for (the middle kernels wait for the
+    counts, bins_assign_kernel runs) and without (they are launched before the counts are back and again after the redo)."""
+    from strawberry_amd import exonbin as eb
+    rng = np.random.default_rng(79)
+    shapes = [(600, 9000), (700, 2000), (200, 1500), (150, 256), (150, 257), (30, 40), (60, 100), (10, 0)]   # (keys, hits)
+    loci = [[[(1000 * (l + 1) * 200 + 100 * k, 1000 * (l + 1) * 200 + 100 * k + 49) for k in range(40)]] * 20 for l in range(len(shapes))]
+    annot = eb.Annotation(loci)
+    assert annot.compat_words == 1 and annot.key_words == 2
+    loc, feats, masses, compat, key = [], [], [], [], []
+    for l, (n_keys, n_hits) in enumerate(shapes):
+        base = 1000 * (l + 1) * 200
+        keys = rng.integers(1, 2 ** 32, (n_keys, 2), dtype=np.uint64).astype(np.uint32)
+        keys[:, 1] &= 255                   # 40 segments
+        comps = rng.integers(1, 2 ** 20, (n_keys, 1), dtype=np.uint64).astype(np.uint32)   # 20 isoforms
+        pick = np.sort(rng.integers(0, n_keys, n_hits))
+        lefts = np.sort(rng.choice(np.arange(base, base + 12000), n_hits, replace=False))   # distinct fragments
+        for q in range(n_hits):
+            loc.append(l)
+            feats.append(([0], [int(lefts[q])], [int(lefts[q]) + 74]))
+            masses.append(float(rng.integers(1, 4)))
+            key.append(keys[pick[q]])
+            compat.append(comps[pick[q]])
+    hits, compat, key = eb.Hits(loc, feats, mass=masses), np.array(compat, np.uint32), np.array(key, np.uint32)
+    per_locus = np.bincount(hits.hit_locus, minlength=len(shapes))
+    assert per_locus[0] >= 8192 and per_locus[0] >= 3 * (hits.n_hits // len(shapes))
+    assert per_locus[3] == 256 and per_locus[4] == 257 and per_locus[7] == 0
+    bd, bh = group_both_ways(ctx, annot, hits, compat, key)
+    nb = np.diff(bh.row_off)
+    assert 513 <= nb[0] <= 1400 and 513 <= nb[1] <= 1400 and nb[7] == 0
+    assert bd is not None
+    for x, y in zip(bins_arrays_no_pairs(bd), bins_arrays_no_pairs(bh)):
+        np.testing.assert_array_equal(x, y)
+    bd, _ = group_both_ways(ctx, annot, hits, compat, key, want_hit_bin=False, host=bh)
+    assert bd is not None and bd.hit_bin is None
+    for x, y in zip(bins_arrays_no_pairs(bd)[:-1], bins_arrays_no_pairs(bh)[:-1]):
+        np.testing.assert_array_equal(x, y)
 
 
 def test_device_grouping_declines_what_it_cannot_do_exactly(ctx):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""exonbin on BIG loci (65-128 segments): the 128-bit segment basis (exonbin_seg128_kernel) against the exon walk
-(SBGPU_EXONBIN_SEGBASIS=0 in the environment selects the walk everywhere).  usage: bench_exonbin_big.py [n_loci=1500] [hits_per_locus=3000]"""
+"""exonbin on BIG loci (65-128 segments): the 128-bit segment basis (exonbin_seg128_kernel).
+usage: bench_exonbin_big.py [n_loci=1500] [hits_per_locus=3000]"""
 import json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,5 +37,5 @@ for _ in range(6):
     compat, key = eb.compat_and_keys(annot, hits, ctx)
     torch.cuda.synchronize(); ts.append(time.time() - t)
 print(json.dumps({"loci": n_loci, "hits": hits.n_hits, "segments_per_locus": float(np.diff(annot.seg_off).mean()), "key_words": annot.key_words,
-                  "segbasis": os.environ.get("SBGPU_EXONBIN_SEGBASIS", "1"), "call_ms_min": min(ts[1:]) * 1e3,
+                  "call_ms_min": min(ts[1:]) * 1e3,
                   "compatible_frac": float((compat != 0).any(1).mean()), "note": "whole sbgpu_exonbin_host call incl. uploads and downloads"}))
