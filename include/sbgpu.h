@@ -1337,6 +1337,147 @@ int sbgpu_model_loo_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins, const int
  * a launch's grid is capped at; [5] the default scratch budget in bytes; [6] the most bins and [7] the most isoforms of a locus. */
 int sbgpu_em_loo_limits(int64_t out[8]);
 
+/* ---- differential isoform usage: two samples, a pooled-solve likelihood ratio ------------------------------
+ * Did isoform usage at a locus change between two samples?  Solve each sample, solve both under ONE shared theta, compare the
+ * likelihoods: the question the drop-one support asks of an isoform, asked of a pair of samples.  Two bootstrap intervals cost
+ * 2 B solves and have no joint null; a Wald test from two information matrices is one-sided at theta_j near 0.  The rule
+ * (csrc/diff_rules.h, shared by both forms, compiled under -ffp-contract=off).  Two batches A and B over the same annotation:
+ * the same n_loci and identical iso_off (anything else is SBGPU_EINVAL); each has its own row_off, f_off, count and F; keep_a
+ * and keep_b are [n_iso] or NULL.  Every sum starts from 0.0 and adds in ascending index.
+ *    1. kept(j) = kept in A OR kept in B (loo_kept's bit on each side; a NULL side keeps everything); K = the kept isoforms of
+ *       the locus.  diff_status[l] before the solves: SBGPU_DIFF_EMPTY when K = 0; SBGPU_DIFF_SOLE when K = 1: no solve, lr_stat
+ *       0.0 exactly, dof 0, usage 1.0 for the kept isoform in every sample that placed a fragment (a count > 0 in one of the
+ *       sample's bins of the locus), 0.0 otherwise; SBGPU_DIFF_TOO_WIDE when K > SBGPU_DIFF_MAX_KEPT (the EM plan's own limit);
+ *       SBGPU_DIFF_TOO_DEEP when nb_A + nb_B > SBGPU_DIFF_MAX_POOLED_BINS (the fit's bin limit, for the pooled problem);
+ *       SBGPU_DIFF_OK otherwise, tested in this order.  TOO_WIDE and TOO_DEEP are statuses, not refusals of the call: the
+ *       neighbours are untouched.  A single sample's locus beyond the fit's limits (5632 bins, 4096 isoforms) refuses the call
+ *       with SBGPU_ESHAPE, as the fit does.
+ *    2. An OK locus gets three sub-problems, in this order, numbered consecutively over the call (a sub-batch): A -- A's bins and
+ *       counts, the kept columns compacted row-major; B -- likewise; POOLED -- A's rows then B's rows, nb_A + nb_B of them, the
+ *       counts as they are and the weights SCALED by rule 3.
+ *    3. A row of sample s is LIVE when asg_row_live holds on its KEPT weights (what the EM will decide on the compacted
+ *       sub-problem).  c^s_j = the sum of kept column j over the live rows of s, in ascending row order.
+ *       alpha^s_j = 0.5 * ((c^A_j + c^B_j) / c^s_j) where c^s_j != 0, and 1.0 otherwise: the sum first, then the quotient, then
+ *       the product.  A pooled weight is F[b][j] * alpha^s_j.
+ *       Why: EmSolver::run renormalises every column over the live rows, so the EM's model for a stacked matrix is
+ *       p((s, b) | j) = F~_bj / sum F~_.j.  Stacked raw, isoform j's mass would split between the samples as c^A_j : c^B_j, a
+ *       ratio that differs from isoform to isoform (c^s_j depends on which bins sample s observed): a shared theta would NOT be
+ *       the joint maximum-likelihood theta.  With alpha every column puts half of its mass in each sample, the responsibilities
+ *       are those of the two samples' own column-normalised models, the M-step sums both samples' fragments, and the stacked
+ *       solve is the joint MLE under one theta.  When c^A_j ~ c^B_j, alpha ~ 1: the weights keep their raw magnitude and the
+ *       1e-5 row threshold keeps its meaning.
+ *    4. Each sub-problem is solved as sbgpu_em_run_device solves any locus; the bases are ALWAYS solved inside the call (a locus
+ *       solved again alone does not always return a batch's theta bits).  Two fits run with nothing erased (keep NULL): the OWN
+ *       fit -- every sub-problem at its own theta and status; the CROSS fit -- sub-problems A and B at the POOLED theta, under
+ *       the pooled solve's status.  The fit's loglik is invariant to theta's scale: the pooled theta sums to N_A + N_B and is
+ *       used as it is.
+ *    5. lr_stat[l] = 2.0 * ((ll_A(theta_A) - ll_A(theta_P)) + (ll_B(theta_B) - ll_B(theta_P))): two subtractions, one sum, one
+ *       product -- what each sample's own likelihood loses when both must share theta_P.  It carries no constants and does not
+ *       depend on how the pooled matrix was scaled.  dof[l] = K - 1.  All solves stop at SBGPU_EM_THETA_CHANGE_LIMIT, not at
+ *       the optimum: small negative values are real and are reported raw.
+ *    6. Integers, exact: n_a, n_b = n_live - n_impossible of each base's own fit.  With lost = n_dropped + n_impossible,
+ *       lost_shift[l] = lost(POOLED) - lost(A) - lost(B) + (lost(A cross) - lost(A)) + (lost(B cross) - lost(B)).  Non-zero: the
+ *       scaling, or the shared theta, moved fragments across the row threshold or made them impossible; lr_stat is still
+ *       reported raw, but does not compare like with like.
+ *    7. After the solves an OK locus becomes SBGPU_DIFF_ONE_SAMPLE when n_a or n_b is 0 or a base ended SBGPU_EM_INIT_EMPTY;
+ *       else SBGPU_DIFF_UNSOLVED when any of the three solves ended SBGPU_EM_DENOM_ZERO.  For a status other than OK or SOLE
+ *       every double of the locus and of its isoforms is 0.0, n_a, n_b, lost_shift and dof are 0, and the one index, top_iso,
+ *       is -1.  status_a / _b / _pooled and iters_a / _b / _pooled are STILL REPORTED, as the solves left them, for every locus
+ *       that had sub-problems -- ONE_SAMPLE and UNSOLVED included: they say why -- and are -1 where it had none (EMPTY, SOLE,
+ *       TOO_WIDE, TOO_DEEP).
+ *    8. Per isoform: theta_a, theta_b, theta_pooled scattered back, 0.0 where the isoform is not kept or the locus is not OK;
+ *       usage_x[j] = theta_x[j] / (the ascending sum of the locus' kept theta_x), 0.0 where that sum is 0;
+ *       delta_usage[j] = usage_b[j] - usage_a[j].
+ *    9. Per locus: the four log-likelihoods (loglik_a, loglik_b own; loglik_a_pooled, loglik_b_pooled cross), the three statuses
+ *       and iteration counts, and top_iso: the locus-local index of the kept isoform of largest |delta_usage| under strict > in
+ *       ascending order from -1.0 (a NaN never wins), -1 when there is none.  At K = 2 the usages of each sample sum to 1, so
+ *       the two |delta_usage| are equal up to a rounding and top_iso is whichever the roundings favour: read delta_usage there.
+ * p-values are the caller's (chi-squared with dof degrees of freedom; strawberry_amd/diff.py has one).
+ * CAVEAT.  theta in the reference's model is a share among the bins a sample OBSERVED: the column scale runs over live bins
+ * only.  Two samples of very different depth observe different bin sets, and part of a usage difference is then that difference
+ * of conditioning; the resident path keeps only observed bins, so two retained samples' bin tables were not built to match.  A
+ * caller who builds both batches on one shared bin table, zero-count rows included, gets the clean test: the rule allows zero
+ * counts.  Out of this rule: merging two bin tables by key, more than two samples, replicates and dispersion, multiple-testing
+ * corrections, warm starts, multi-rank wiring, columns in the parity writers.
+ * The struct: host arrays to fill (any may be NULL) and, on return -- device forms only -- the device arrays of all of them:
+ * the (first) context's memory, in a scratch slot of their own, valid until that context's next sbgpu_quantify_* or diff call. */
+#define SBGPU_DIFF_MAX_KEPT 512
+#define SBGPU_DIFF_MAX_POOLED_BINS 5632
+#define SBGPU_DIFF_OK 0
+#define SBGPU_DIFF_EMPTY 1
+#define SBGPU_DIFF_SOLE 2
+#define SBGPU_DIFF_TOO_WIDE 3
+#define SBGPU_DIFF_TOO_DEEP 4
+#define SBGPU_DIFF_ONE_SAMPLE 5
+#define SBGPU_DIFF_UNSOLVED 6
+#define SBGPU_DIFF_KIND_A 0
+#define SBGPU_DIFF_KIND_B 1
+#define SBGPU_DIFF_KIND_POOLED 2
+typedef struct {
+   double *theta_a, *theta_b, *theta_pooled, *usage_a, *usage_b, *usage_pooled, *delta_usage;   /* in: [n_iso]  */
+   double *lr_stat, *loglik_a, *loglik_b, *loglik_a_pooled, *loglik_b_pooled;                    /* in: [n_loci] */
+   int64_t *n_a, *n_b, *lost_shift;                                                              /* in: [n_loci] */
+   int32_t *dof, *diff_status, *top_iso, *status_a, *status_b, *status_pooled, *iters_a, *iters_b, *iters_pooled; /* in: [n_loci] */
+   const double *d_theta_a, *d_theta_b, *d_theta_pooled, *d_usage_a, *d_usage_b, *d_usage_pooled, *d_delta_usage; /* out: device forms only */
+   const double *d_lr_stat, *d_loglik_a, *d_loglik_b, *d_loglik_a_pooled, *d_loglik_b_pooled;
+   const int64_t *d_n_a, *d_n_b, *d_lost_shift;
+   const int32_t *d_dof, *d_diff_status, *d_top_iso, *d_status_a, *d_status_b, *d_status_pooled, *d_iters_a, *d_iters_b, *d_iters_pooled;
+   int32_t *sub_count;                          /* in, device forms only: [sizes[1]] and [sizes[3]] of the shapes call, or NULL: the */
+   double *sub_F;                               /* expanded sub-batch, for a caller that checks it */
+} sbgpu_em_diff_t;
+typedef struct {
+   int64_t max_bytes; /* device scratch one chunk of sub-problems may take; 0: 1 GiB.  Any positive value is legal: consecutive
+                         whole loci form a chunk, and a locus above the budget is a chunk alone */
+   int64_t reserved;  /* 0 */
+} sbgpu_diff_params_t;
+/* Host form (csrc/diff_host.cpp; no GPU needed, free of HIP) in three calls, because the library has no CPU EM: the caller solves
+ * the sub-batch between the second and the third, and fits it twice (sbgpu_em_fit_host: own and cross, rule 4).
+ * Shapes (rules 1, 2): sizes[4] = the sub-problems, their bins, isoforms and weights together -- always filled; every other
+ * output may be NULL (sizes first, then fill): diff_status [n_loci] (before the solves); sub_locus, sub_kind [sizes[0]]: the
+ * parent locus and SBGPU_DIFF_KIND_*; sub_row_off, sub_iso_off, sub_f_off [sizes[0] + 1].  SBGPU_EINVAL: NULL offsets,
+ * n_loci < 0, offsets that do not begin at 0 or do not ascend; SBGPU_ESHAPE: rule 1.                                         */
+int sbgpu_em_diff_shapes_host(int64_t n_loci, const int64_t *row_off_a, const int64_t *row_off_b, const int64_t *iso_off, const int32_t *keep_a,
+                              const int32_t *keep_b, int64_t sizes[4], int32_t *diff_status, int32_t *sub_locus, int32_t *sub_kind,
+                              int64_t *sub_row_off, int64_t *sub_iso_off, int64_t *sub_f_off);
+/* Expansion (rules 2, 3): the sub-batch's counts [sizes[1]] and weights [sizes[3]].  Refusals as sbgpu_em_fit_host's for each
+ * batch; SBGPU_EINVAL also where the two batches' n_loci or iso_off differ.                                                */
+int sbgpu_em_diff_expand_host(const sbgpu_batch_t *batch_a, const sbgpu_batch_t *batch_b, const int32_t *keep_a, const int32_t *keep_b,
+                              int32_t *sub_count, double *sub_F);
+/* Statistics (rules 5-9) from the sub-batch's solve -- sub_theta [sizes[2]], sub_status, sub_iters [sizes[0]] --, its own fit --
+ * own_loglik, own_n_live, own_n_dropped, own_n_impossible [sizes[0]] -- and its cross fit -- cross_loglik, cross_n_dropped,
+ * cross_n_impossible [sizes[0]]; the POOLED entries of the cross arrays are not read.  Of the batches the offsets and the
+ * counts are read (F may be NULL).  SBGPU_EINVAL: a NULL input, malformed or differing offsets.                              */
+int sbgpu_em_diff_stat_host(const sbgpu_batch_t *batch_a, const sbgpu_batch_t *batch_b, const int32_t *keep_a, const int32_t *keep_b,
+                            const double *sub_theta, const int32_t *sub_status, const int32_t *sub_iters, const double *own_loglik,
+                            const int64_t *own_n_live, const int64_t *own_n_dropped, const int64_t *own_n_impossible, const double *cross_loglik,
+                            const int64_t *cross_n_dropped, const int64_t *cross_n_impossible, sbgpu_em_diff_t *out);
+/* Device form (csrc/diff_device.h) for two batches sbgpu_em_run_device solves, both on ctx's device: each plan, d_count and d_F
+ * as given to it; d_keep_a, d_keep_b: device [n_iso] arrays or NULL; params: NULL for the defaults.  The keeps are read back once
+ * (the shapes are made on the host, by the function the host form calls); then per chunk of loci: a plan for the chunk's
+ * sub-batch, diff_colscale_kernel (rule 3's live rows, c and alpha, the column sums in ascending row order), diff_expand_kernel
+ * (a workgroup per row tile; own copies are stores of loaded values, a pooled weight is one product: bitwise the host
+ * expansion), the EM through sbgpu_em_run_device, diff_cross_kernel, the fit's three launches twice in this stage's scratch (an
+ * earlier fit result of the caller stays valid), diff_stat_kernel.  No atomics.  Every integer, every status and -- given the
+ * same solves and fits -- every double are the host form's.  Only the arrays the caller gave pointers for cross PCIe.
+ * Synchronises on `stream` (NULL: the context's own).  SBGPU_ESHAPE: rule 1; SBGPU_EINVAL: a NULL argument, plans that differ in
+ * n_loci or iso_off, counts or weights that are not on the device, a negative max_bytes.                                    */
+int sbgpu_em_diff_device(sbgpu_ctx_t *ctx, const sbgpu_plan_t *plan_a, const int32_t *d_count_a, const double *d_F_a, const sbgpu_plan_t *plan_b,
+                         const int32_t *d_count_b, const double *d_F_b, const int32_t *d_keep_a, const int32_t *d_keep_b,
+                         const sbgpu_diff_params_t *params, void *stream, sbgpu_em_diff_t *out);
+/* The same from what two contexts' resident calls (or sbgpu_front_stream_end) kept with sbgpu_bootstrap_keep on: sample A is
+ * ctx_a's record, sample B ctx_b's; each handle is checked against its context's record as sbgpu_model_loo_device checks one.
+ * The two contexts must be on the same device (SBGPU_EINVAL otherwise); ctx_b's own stream is synchronised before its arrays
+ * are read; the work, the sub-batch's plan and the scratch are ctx_a's.  Neither record changes: both calls' seven results are
+ * the same bits with and without it, and every other stage still answers on both contexts, in any order.                    */
+int sbgpu_model_diff_device(sbgpu_ctx_t *ctx_a, const sbgpu_bins_t *bins_a, sbgpu_ctx_t *ctx_b, const sbgpu_bins_t *bins_b, const int32_t *d_keep_a,
+                            const int32_t *d_keep_b, const sbgpu_diff_params_t *params, void *stream, sbgpu_em_diff_t *out);
+/* The thresholds (csrc/diff_rules.h, csrc/diff_device.h; reasoned from LDS sizes, not tuned): out[0] the most kept isoforms of
+ * a tested locus; [1] the most pooled bins; [2] weights of one row tile of the expand kernel, [3] the most rows of one tile: a
+ * locus of K kept isoforms is cut into tiles of max(1, min(out[3], out[2] / K)) rows; [4] kept isoforms up to which the
+ * column-scale kernel serves a locus with a group of lanes (several loci to a workgroup), a whole workgroup beyond; [5] threads
+ * of a workgroup; [6] workgroups per CU a launch's grid is capped at; [7] the default scratch budget in bytes.              */
+int sbgpu_em_diff_limits(int64_t out[8]);
+
 /* ---- the EM bootstrap: how far theta can be trusted -------------------------
  * The reference prints theta with no statement of its spread.  The bootstrap resamples every locus' fragments over its
  * bins, solves again, and reports mean and variance of theta over the replicates.

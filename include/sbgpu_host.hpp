@@ -1052,6 +1052,79 @@ class IsoformSupport {
    }
 };
 
+/* Differential isoform usage of two samples (sbgpu_em_diff_device / sbgpu_model_diff_device, include/sbgpu.h): per
+ * locus the likelihood-ratio statistic of "one shared theta" against "a theta per sample" with its degrees of freedom, per
+ * isoform the three thetas, usages and the usage difference.  device(): for two batches (plans) of one annotation, or right
+ * after two resident calls on two contexts of one device (bins).  p-values (chi-squared with dof degrees of freedom, NaN where
+ * lost_shift != 0) are the caller's.                                                                                       */
+class DifferentialUsage {
+ public:
+   std::vector<double> theta_a, theta_b, theta_pooled, usage_a, usage_b, usage_pooled, delta_usage;   /* [n_iso]  */
+   std::vector<double> lr_stat, loglik_a, loglik_b, loglik_a_pooled, loglik_b_pooled;                  /* [n_loci] */
+   std::vector<int64_t> n_a, n_b, lost_shift;                                                          /* [n_loci] */
+   std::vector<int32_t> dof, diff_status, top_iso, status_a, status_b, status_pooled, iters_a, iters_b, iters_pooled; /* [n_loci] */
+   sbgpu_em_diff_t raw{}; /* the device arrays -- the (first) context's, valid until its next quantify or diff call; its host
+                             pointers are null after the call */
+
+   static DifferentialUsage device(const Context &ctx, const sbgpu_plan_t *plan_a, const int32_t *d_count_a, const double *d_F_a,
+                                   const sbgpu_plan_t *plan_b, const int32_t *d_count_b, const double *d_F_b, const int32_t *d_keep_a = nullptr,
+                                   const int32_t *d_keep_b = nullptr, int64_t max_bytes = 0, void *stream = nullptr)
+   {
+      int64_t info[8];
+      check(sbgpu_plan_info(plan_a, info), "sbgpu_plan_info");
+      DifferentialUsage t;
+      t.prepare(info[0], info[2]);
+      const sbgpu_diff_params_t par{max_bytes, 0};
+      check(sbgpu_em_diff_device(ctx.get(), plan_a, d_count_a, d_F_a, plan_b, d_count_b, d_F_b, d_keep_a, d_keep_b, &par, stream, &t.raw),
+            "sbgpu_em_diff_device");
+      t.done();
+      return t;
+   }
+   static DifferentialUsage device(const Context &ctx_a, const sbgpu_bins_t *bins_a, const Context &ctx_b, const sbgpu_bins_t *bins_b,
+                                   const int32_t *d_keep_a = nullptr, const int32_t *d_keep_b = nullptr, int64_t max_bytes = 0, void *stream = nullptr)
+   {
+      int64_t info[8];
+      check(sbgpu_bins_info(bins_a, info), "sbgpu_bins_info");
+      DifferentialUsage t;
+      t.prepare(info[0], info[1]);
+      const sbgpu_diff_params_t par{max_bytes, 0};
+      check(sbgpu_model_diff_device(ctx_a.get(), bins_a, ctx_b.get(), bins_b, d_keep_a, d_keep_b, &par, stream, &t.raw), "sbgpu_model_diff_device");
+      t.done();
+      return t;
+   }
+
+   /* (public for a caller that fills raw through the host form's three calls) */
+   void prepare(int64_t n_loci, int64_t n_iso)
+   {
+      const size_t nl = (size_t)n_loci + 1, ni = (size_t)n_iso + 1; /* (one spare entry: data() of an empty vector may be null) */
+      for (std::vector<double> *v : {&theta_a, &theta_b, &theta_pooled, &usage_a, &usage_b, &usage_pooled, &delta_usage}) v->assign(ni, 0.0);
+      for (std::vector<double> *v : {&lr_stat, &loglik_a, &loglik_b, &loglik_a_pooled, &loglik_b_pooled}) v->assign(nl, 0.0);
+      for (std::vector<int64_t> *v : {&n_a, &n_b, &lost_shift}) v->assign(nl, 0);
+      for (std::vector<int32_t> *v : {&dof, &diff_status, &top_iso, &status_a, &status_b, &status_pooled, &iters_a, &iters_b, &iters_pooled}) v->assign(nl, 0);
+      raw = sbgpu_em_diff_t{};
+      raw.theta_a = theta_a.data(), raw.theta_b = theta_b.data(), raw.theta_pooled = theta_pooled.data();
+      raw.usage_a = usage_a.data(), raw.usage_b = usage_b.data(), raw.usage_pooled = usage_pooled.data(), raw.delta_usage = delta_usage.data();
+      raw.lr_stat = lr_stat.data(), raw.loglik_a = loglik_a.data(), raw.loglik_b = loglik_b.data();
+      raw.loglik_a_pooled = loglik_a_pooled.data(), raw.loglik_b_pooled = loglik_b_pooled.data();
+      raw.n_a = n_a.data(), raw.n_b = n_b.data(), raw.lost_shift = lost_shift.data();
+      raw.dof = dof.data(), raw.diff_status = diff_status.data(), raw.top_iso = top_iso.data();
+      raw.status_a = status_a.data(), raw.status_b = status_b.data(), raw.status_pooled = status_pooled.data();
+      raw.iters_a = iters_a.data(), raw.iters_b = iters_b.data(), raw.iters_pooled = iters_pooled.data();
+   }
+   void done()
+   {
+      raw.theta_a = raw.theta_b = raw.theta_pooled = raw.usage_a = raw.usage_b = raw.usage_pooled = raw.delta_usage = nullptr;
+      raw.lr_stat = raw.loglik_a = raw.loglik_b = raw.loglik_a_pooled = raw.loglik_b_pooled = nullptr;
+      raw.n_a = raw.n_b = raw.lost_shift = nullptr;
+      raw.dof = raw.diff_status = raw.top_iso = raw.status_a = raw.status_b = raw.status_pooled = raw.iters_a = raw.iters_b = raw.iters_pooled = nullptr;
+      for (std::vector<double> *v : {&theta_a, &theta_b, &theta_pooled, &usage_a, &usage_b, &usage_pooled, &delta_usage, &lr_stat, &loglik_a, &loglik_b,
+                                     &loglik_a_pooled, &loglik_b_pooled})
+         v->pop_back();
+      for (std::vector<int64_t> *v : {&n_a, &n_b, &lost_shift}) v->pop_back();
+      for (std::vector<int32_t> *v : {&dof, &diff_status, &top_iso, &status_a, &status_b, &status_pooled, &iters_a, &iters_b, &iters_pooled}) v->pop_back();
+   }
+};
+
 /* The bootstrap of the resident path (sbgpu_bootstrap_keep / sbgpu_abundance_bootstrap_device, include/sbgpu.h): FPKM and TPM
  * mean, variance and percentile interval over resampled bin counts, with the replicates in which the expression filter kept
  * each isoform.  keep(): before the resident call; device(): right after it, on that call's handle.  interval_ranks(): the two

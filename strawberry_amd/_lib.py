@@ -51,6 +51,8 @@ SYMBOLS = [
     "sbgpu_em_info_host", "sbgpu_em_info_device", "sbgpu_model_info_device", "sbgpu_em_info_limits", "sbgpu_em_info_cov_offsets",
     "sbgpu_em_loo_offsets", "sbgpu_em_loo_shapes_host", "sbgpu_em_loo_expand_host", "sbgpu_em_loo_stat_host", "sbgpu_em_loo_device",
     "sbgpu_model_loo_device", "sbgpu_em_loo_limits",
+    "sbgpu_em_diff_shapes_host", "sbgpu_em_diff_expand_host", "sbgpu_em_diff_stat_host", "sbgpu_em_diff_device", "sbgpu_model_diff_device",
+    "sbgpu_em_diff_limits",
     "sbgpu_body_profile_host", "sbgpu_body_profile_device", "sbgpu_body_profile_limits",
     "sbgpu_splice_events_shapes_host", "sbgpu_splice_events_build_host", "sbgpu_splice_psi_host", "sbgpu_splice_support_host",
     "sbgpu_splice_psi_device", "sbgpu_splice_support_device", "sbgpu_splice_limits",
@@ -199,6 +201,17 @@ class sbgpu_em_loo_t(C.Structure):
 
 
 class sbgpu_loo_params_t(C.Structure):
+    _fields_ = [("max_bytes", C.c_int64), ("reserved", C.c_int64)]
+
+
+class sbgpu_em_diff_t(C.Structure):
+    _NAMES = ("theta_a", "theta_b", "theta_pooled", "usage_a", "usage_b", "usage_pooled", "delta_usage", "lr_stat", "loglik_a", "loglik_b",
+              "loglik_a_pooled", "loglik_b_pooled", "n_a", "n_b", "lost_shift", "dof", "diff_status", "top_iso", "status_a", "status_b",
+              "status_pooled", "iters_a", "iters_b", "iters_pooled")
+    _fields_ = [(n, C.c_void_p) for n in _NAMES] + [("d_" + n, C.c_void_p) for n in _NAMES] + [("sub_count", C.c_void_p), ("sub_F", C.c_void_p)]
+
+
+class sbgpu_diff_params_t(C.Structure):
     _fields_ = [("max_bytes", C.c_int64), ("reserved", C.c_int64)]
 
 
@@ -404,6 +417,12 @@ def load():
     L.sbgpu_em_loo_device.argtypes = [vp, vp, vp, vp, vp, C.POINTER(sbgpu_loo_params_t), vp, C.POINTER(sbgpu_em_loo_t)]
     L.sbgpu_model_loo_device.argtypes = [vp, vp, vp, C.POINTER(sbgpu_loo_params_t), vp, C.POINTER(sbgpu_em_loo_t)]
     L.sbgpu_em_loo_limits.argtypes = [C.POINTER(C.c_int64)]
+    L.sbgpu_em_diff_shapes_host.argtypes = [C.c_int64, vp, vp, vp, vp, vp, C.POINTER(C.c_int64), vp, vp, vp, vp, vp, vp]
+    L.sbgpu_em_diff_expand_host.argtypes = [C.POINTER(sbgpu_batch_t), C.POINTER(sbgpu_batch_t), vp, vp, vp, vp]
+    L.sbgpu_em_diff_stat_host.argtypes = [C.POINTER(sbgpu_batch_t), C.POINTER(sbgpu_batch_t)] + [vp] * 12 + [C.POINTER(sbgpu_em_diff_t)]
+    L.sbgpu_em_diff_device.argtypes = [vp] * 9 + [C.POINTER(sbgpu_diff_params_t), vp, C.POINTER(sbgpu_em_diff_t)]
+    L.sbgpu_model_diff_device.argtypes = [vp] * 6 + [C.POINTER(sbgpu_diff_params_t), vp, C.POINTER(sbgpu_em_diff_t)]
+    L.sbgpu_em_diff_limits.argtypes = [C.POINTER(C.c_int64)]
     L.sbgpu_body_profile_host.argtypes = [vp, C.POINTER(sbgpu_annotation_t), C.POINTER(sbgpu_hits_t), vp, C.c_int32, vp, vp, vp, vp, vp, vp,
                                           C.c_int32, C.POINTER(sbgpu_body_profile_t)]
     L.sbgpu_body_profile_device.argtypes = [vp, vp, C.POINTER(sbgpu_annotation_t), C.POINTER(sbgpu_hits_t), vp, vp, vp, C.c_int32, vp,

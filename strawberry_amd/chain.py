@@ -24,12 +24,15 @@ class DeviceSample:
     """Annotation (host arrays, it is small) + hits on the device."""
 
     def __init__(self, torch, dev, n_loci=60000, n_frags=2e8, seed=31, read_len=75, mean=250.0, sd=30.0, noise=0.10,
-                 loci_subset=None):
-        """loci_subset: (rank, world) -- keep only this rank's share of the SAME sample's loci (strong scaling:
+                 loci_subset=None, sample_seed=None):
+        """sample_seed: another SAMPLE of the same annotation -- the expression shares, the per-locus depths and the fragments'
+        generator draw from it, the annotation still comes from `seed` (None: everything from `seed`).
+        loci_subset: (rank, world) -- keep only this rank's share of the SAME sample's loci (strong scaling:
         every rank draws the same annotation and the same per-locus fragment counts, then generates its own loci's
         fragments only)."""
         loci = synth.make_gene_models(n_loci, seed=seed)
-        rng = np.random.Generator(np.random.PCG64(seed ^ 0x5EED))
+        draw = seed if sample_seed is None else sample_seed
+        rng = np.random.Generator(np.random.PCG64(draw ^ 0x5EED))
         # per-locus share of the fragments: log-normal (sigma 1), like C3's law
         w = rng.lognormal(0.0, 1.0, n_loci)
         per_locus = np.maximum(0, np.rint(w / w.sum() * n_frags)).astype(np.int64)
@@ -65,7 +68,7 @@ class DeviceSample:
         share[last] = 1.0
         up = lambda x, dt=None: torch.from_numpy(np.ascontiguousarray(x if dt is None else x.astype(dt))).to(dev)  # noqa: E731
         g = torch.Generator(device=dev)
-        g.manual_seed(seed * 7919 + (0 if loci_subset is None else 1 + loci_subset[0]))
+        g.manual_seed(draw * 7919 + (0 if loci_subset is None else 1 + loci_subset[0]))
         n = int(per_locus.sum())
         d_locus = torch.repeat_interleave(torch.arange(n_loci, device=dev, dtype=torch.int32), up(per_locus))
         # isoform of each fragment: first isoform of the locus whose cumulative share reaches u
@@ -222,7 +225,7 @@ class ChainQuantifier:
     then FPKM / TPM on the host arrays the call returns (the caller's own epilogue, as in the reference)."""
 
     def __init__(self, ctx, n_loci=60000, n_frags=2e8, seed=31, read_len=75, loci_subset=None, pin=True, resident=False,
-                 empirical=False, comm=None, min_isoform_frac=0.0, keep_context=False, keep_bootstrap=False):
+                 empirical=False, comm=None, min_isoform_frac=0.0, keep_context=False, keep_bootstrap=False, sample_seed=None):
         """resident=True: step() is sbgpu_quantify_resident -- the chain with the reference's pass 1 in front (empirical=True: no
         insert-size law is given, the device builds it from the hits; Strawberry's default mode) and the FPKM / Frac / TPM
         epilogue behind it, the collectives over `comm` (dist.AbiComm / dist.HostComm; None: a world of one) inside the call;
@@ -235,11 +238,12 @@ class ChainQuantifier:
         keep_bootstrap=True (resident only): likewise for the bootstrap (sbgpu_bootstrap_keep); abundance_bootstrap() runs it on the
         last step's handle, model_fit() the model fit (fit.model_fit_device) and isoform_information() the isoform information
         (info.model_info_device) and isoform_support() the drop-one support (support.model_loo_device), which work from the same
-        retention."""
+        retention; differential_usage(other) compares this object's last step with another quantifier's (diff.model_diff_device).
+        sample_seed: DeviceSample's -- another sample of the annotation `seed` draws."""
         import torch
         self.torch, self.ctx = torch, ctx
         self.dev = torch.device("cuda", ctx.device)
-        self.sample = DeviceSample(torch, self.dev, n_loci, n_frags, seed, read_len, loci_subset=loci_subset)
+        self.sample = DeviceSample(torch, self.dev, n_loci, n_frags, seed, read_len, loci_subset=loci_subset, sample_seed=sample_seed)
         self.annot, self.hits = self.sample.annot, self.sample
         self.insert = InsertSize(250.0, 30.0)
         self.read_len = read_len
@@ -416,6 +420,19 @@ class ChainQuantifier:
             raise _lib.SbgpuError("isoform_support: no step has run with keep_bootstrap=True")
         return support.model_loo_device(self.ctx, self.context_handle, int(self._out.d_keep), keep=self.keep[:self.n_iso], max_bytes=max_bytes,
                                         want=want)
+
+    def differential_usage(self, other, max_bytes=0, want=None, with_sub_batch=False):
+        """Differential isoform usage between this object's last step (sample A) and `other`'s (sample B), both made with
+        keep_bootstrap=True over the same annotation, on contexts of one device: diff.model_diff_device on the two handles with
+        the two steps' keeps -> a diff.DifferentialUsage.  Neither object's results change.  max_bytes: the scratch budget of one
+        chunk of sub-problems (0: 1 GiB); want: the arrays to bring to the host (None: all); with_sub_batch: diff.em_diff_device's."""
+        from . import diff
+        for q in (self, other):
+            if q.context_handle is None or not q.keep_bootstrap:
+                raise _lib.SbgpuError("differential_usage: no step has run with keep_bootstrap=True")
+        return diff.model_diff_device(self.ctx, self.context_handle, other.ctx, other.context_handle, int(self._out.d_keep), int(other._out.d_keep),
+                                      keep_a=self.keep[:self.n_iso], keep_b=other.keep[:other.n_iso], max_bytes=max_bytes, want=want,
+                                      with_sub_batch=with_sub_batch)
 
     def splice_psi(self, events=None, bootstrap=None, coverage=None):
         """The PSI of every annotated exon and intron for the last resident step (splice.SplicePsi), built on the device from the

@@ -237,6 +237,61 @@ inline LooChunkLayout loo_chunk_layout(int64_t n_tiles, int64_t n_sub, int64_t s
    return L;
 }
 
+// The differential usage: as the isoform support's -- the whole call's results and what the host makes of its
+// shapes, then, behind `chunk`, one chunk's working set.
+struct DiffLayout {
+   size_t lstat, rank, first, koff, kcol, upload_bytes;               // made on the host: statuses, kept ranks and lists
+   size_t th_a, th_b, th_p, us_a, us_b, us_p, delta;                    // per isoform
+   size_t lr, ll_a, ll_b, llx_a, llx_b, n_a, n_b, shift;                // per locus
+   size_t dof, status, top, st_a, st_b, st_p, it_a, it_b, it_p;
+   size_t sum_a, sum_b, sum_p;                                          // per locus: the statistics' first launch's notes for its second
+   size_t chunk, bytes;
+};
+inline DiffLayout diff_layout(int64_t n_loci, int64_t n_iso, int64_t n_kept, size_t chunk_bytes)
+{
+   const size_t nl1 = (size_t)n_loci + 1, ni1 = (size_t)n_iso + 1;
+   Arena a;
+   DiffLayout L;
+   L.lstat = a.take(nl1 * 4), L.rank = a.take(ni1 * 4), L.first = a.take(nl1 * 8), L.koff = a.take(nl1 * 8), L.kcol = a.take(at_least_1(n_kept) * 4);
+   L.upload_bytes = a.size;
+   L.th_a = a.take(ni1 * 8), L.th_b = a.take(ni1 * 8), L.th_p = a.take(ni1 * 8), L.us_a = a.take(ni1 * 8), L.us_b = a.take(ni1 * 8);
+   L.us_p = a.take(ni1 * 8), L.delta = a.take(ni1 * 8);
+   L.lr = a.take(nl1 * 8), L.ll_a = a.take(nl1 * 8), L.ll_b = a.take(nl1 * 8), L.llx_a = a.take(nl1 * 8), L.llx_b = a.take(nl1 * 8);
+   L.n_a = a.take(nl1 * 8), L.n_b = a.take(nl1 * 8), L.shift = a.take(nl1 * 8);
+   L.dof = a.take(nl1 * 4), L.status = a.take(nl1 * 4), L.top = a.take(nl1 * 4), L.st_a = a.take(nl1 * 4), L.st_b = a.take(nl1 * 4);
+   L.st_p = a.take(nl1 * 4), L.it_a = a.take(nl1 * 4), L.it_b = a.take(nl1 * 4), L.it_p = a.take(nl1 * 4);
+   L.sum_a = a.take(nl1 * 8), L.sum_b = a.take(nl1 * 8), L.sum_p = a.take(nl1 * 8);
+   L.chunk = a.take(chunk_bytes);
+   L.bytes = a.size;
+   return L;
+}
+struct DiffTile {
+   int32_t locus, sample, row0, rows; // rows [row0, row0 + rows) of the locus in sample 0 (A) or 1 (B)
+};
+struct DiffScaleItem {
+   int32_t first, n, lanes, rows; // loci list[first .. first + n) share a workgroup, `lanes` lanes each (0: one locus, all threads); rows: the most bins of one sample among them
+};
+struct DiffChunkLayout {
+   size_t tiles, items, list, upload_bytes;
+   size_t alpha, count, F, theta, status, iters, x_theta, x_status, fit, x_fit, bytes;
+};
+inline DiffChunkLayout diff_chunk_layout(int64_t n_tiles, int64_t n_items, int64_t n_list, int64_t n_kept, int64_t n_sub, int64_t sub_rows,
+                                         int64_t sub_iso, int64_t sub_elem, size_t fit_bytes)
+{
+   Arena a;
+   DiffChunkLayout L;
+   L.tiles = a.take(at_least_1(n_tiles) * sizeof(DiffTile)), L.items = a.take(at_least_1(n_items) * sizeof(DiffScaleItem));
+   L.list = a.take(at_least_1(n_list) * 4);
+   L.upload_bytes = a.size;
+   L.alpha = a.take(at_least_1(2 * n_kept) * 8);
+   L.count = a.take(at_least_1(sub_rows) * 4), L.F = a.take(at_least_1(sub_elem) * 8), L.theta = a.take(at_least_1(sub_iso) * 8);
+   L.status = a.take(at_least_1(n_sub) * 4), L.iters = a.take(at_least_1(n_sub) * 4);
+   L.x_theta = a.take(at_least_1(sub_iso) * 8), L.x_status = a.take(at_least_1(n_sub) * 4);
+   L.fit = a.take(fit_bytes), L.x_fit = a.take(fit_bytes);
+   L.bytes = a.size;
+   return L;
+}
+
 // ---- the host forms' shared loops.  Every sum runs in the order the kernels' do: a column's over the live bins, ascending.
 
 // The kept words of one locus into K [(niso + 31) / 32] -> their number.  keep_of_locus null: no filter was given and every
