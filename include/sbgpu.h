@@ -1395,9 +1395,11 @@ int sbgpu_em_loo_limits(int64_t out[8]);
  * p-values are the caller's (chi-squared with dof degrees of freedom; strawberry_amd/diff.py has one).
  * CAVEAT.  theta in the reference's model is a share among the bins a sample OBSERVED: the column scale runs over live bins
  * only.  Two samples of very different depth observe different bin sets, and part of a usage difference is then that difference
- * of conditioning; the resident path keeps only observed bins, so two retained samples' bin tables were not built to match.  A
- * caller who builds both batches on one shared bin table, zero-count rows included, gets the clean test: the rule allows zero
- * counts.  Out of this rule: merging two bin tables by key, more than two samples, replicates and dispersion, multiple-testing
+ * of conditioning; the resident path keeps only observed bins, so two retained samples' bin tables were not built to match.  The
+ * rule allows zero counts: both batches on one shared bin table, zero-count rows included, give the test without that
+ * difference.  sbgpu_bins_merge_* below builds that table from two samples' bins by key, and sbgpu_model_diff_merged_device runs
+ * this rule on it for two retained samples (ChainQuantifier.differential_usage(other, shared_bins=True)); this entry and its
+ * default stay as they are.  Out of this rule: more than two samples, replicates and dispersion, multiple-testing
  * corrections, warm starts, multi-rank wiring, columns in the parity writers.
  * The struct: host arrays to fill (any may be NULL) and, on return -- device forms only -- the device arrays of all of them:
  * the (first) context's memory, in a scratch slot of their own, valid until that context's next sbgpu_quantify_* or diff call. */
@@ -1477,6 +1479,91 @@ int sbgpu_model_diff_device(sbgpu_ctx_t *ctx_a, const sbgpu_bins_t *bins_a, sbgp
  * column-scale kernel serves a locus with a group of lanes (several loci to a workgroup), a whole workgroup beyond; [5] threads
  * of a workgroup; [6] workgroups per CU a launch's grid is capped at; [7] the default scratch budget in bytes.              */
 int sbgpu_em_diff_limits(int64_t out[8]);
+
+/* ---- two samples on ONE bin table: the merge of two bin tables by key ---------------------------------------
+ * The differential usage above conditions each sample on the bins it observed.  The merge gives both samples the union of their
+ * bins, with zero counts where a sample saw nothing, so that the unchanged rule above tests them on one bin set.  The rule
+ * (csrc/merge_rules.h, shared by both forms):
+ *    1. Two samples A and B over the same annotation: the same n_loci, identical iso_off and the same key_words >= 1 (anything
+ *       else is SBGPU_EINVAL); each has row_off [n_loci + 1], key [n_bins * key_words], count [n_bins] and F [n_elem], row-major,
+ *       n_elem = the sum of bins x isoforms over the loci.  Two keys are equal when all key_words words are.  Keys are unique
+ *       inside a sample's locus: a duplicate in either sample is SBGPU_EINVAL and sbgpu_last_error names the (lowest such) locus,
+ *       in both forms.
+ *    2. The union rows of locus l are A's bins in A's order, then the bins of B whose key does not occur among A's, in B's
+ *       order: nb_U = nb_A + #(B-only).  row_a[r] / row_b[r] = the GLOBAL bin of union row r in A / in B, or -1.  row_off_u and
+ *       f_off_u are the union's offsets over the same iso_off; both samples share them.
+ *    3. count_u_s[r] = count_s[row_s[r]], 0 where row_s[r] is -1.  F_u_s[r][j] = F_s[row_s[r]][j] where the sample has the row:
+ *       its own bits.  Otherwise F_u_s[r][j] = X_s[row_other[r]][j], where X_s has the OTHER sample's shape: the other sample's
+ *       bins weighed under THIS sample's insert law.  X NULL: the other sample's own weights are taken -- exact when both samples
+ *       were given one law, and for long reads, where a weight does not depend on the law.
+ *    4. LIMITATION.  Which isoforms a bin is paired with is the union of compatibilities over the hits of the sample that
+ *       observed it.  A bin both samples observed keeps, in each sample, that sample's own pair set; a bin only one sample
+ *       observed hands its pair set to the other.  Uniting the pair sets of shared bins is out of this rule.
+ *    5. A single sample's locus beyond 5632 bins or 4096 isoforms, or a union of more than 5632 rows, refuses the call with
+ *       SBGPU_ESHAPE, naming the locus, as the fit does.  2 * nb_U > SBGPU_DIFF_MAX_POOLED_BINS is NOT a refusal: the
+ *       differential rule reports SBGPU_DIFF_TOO_DEEP for that locus.
+ *    6. The deep form of the device match files keys under h = 0x811C9DC5; per word h = (h ^ word) * 0x01000193 (mod 2^32);
+ *       slot = (h ^ (h >> 15)) mod out[1] of sbgpu_bins_merge_limits; a hash match is confirmed on all words, so the hash is
+ *       no part of the result.
+ * Footprint: the merged arrays of a whole sample pair are held at once -- 2 * n_elem_U * 8 bytes of weights, n_bins_U * 16 of
+ * row maps and counts, roughly twice one sample's F -- beside n_bins_A * 4 + n_bins_B * 4 of match results; there is no chunking. */
+typedef struct {
+   int64_t n_loci;
+   const int64_t *iso_off, *row_off; /* host, [n_loci + 1] in every form */
+   int32_t key_words;
+   int32_t reserved;                 /* 0 */
+   const uint32_t *key;              /* [n_bins * key_words] */
+   const int32_t *count;             /* [n_bins] */
+   const double *F;                  /* [n_elem] */
+   const double *X;                  /* [n_elem of the OTHER sample] or NULL (rule 3) */
+} sbgpu_merge_sample_t;
+typedef struct {
+   int64_t n_bins, n_elem;                                      /* out: the union's rows and weights */
+   int64_t *row_off, *f_off;                                    /* in: host [n_loci + 1] to fill, or NULL */
+   const int32_t *d_row_a, *d_row_b, *d_count_a, *d_count_b;    /* out: device [n_bins] */
+   const double *d_F_a, *d_F_b;                                 /* out: device [n_elem] */
+} sbgpu_bins_merged_t;
+/* Host form (csrc/merge_host.cpp; no GPU needed, free of HIP).  Shapes: sizes[2] = n_bins_U, n_elem_U -- always filled; every
+ * other output may be NULL (sizes first, then fill): row_off_u, f_off_u [n_loci + 1]; row_a, row_b [sizes[0]].  Of the samples
+ * the offsets and the keys are read.  Fill: count_a, count_b [sizes[0]], F_a, F_b [sizes[1]] (each may be NULL).               */
+int sbgpu_bins_merge_shapes_host(const sbgpu_merge_sample_t *a, const sbgpu_merge_sample_t *b, int64_t sizes[2], int64_t *row_off_u,
+                                 int64_t *f_off_u, int32_t *row_a, int32_t *row_b);
+int sbgpu_bins_merge_fill_host(const sbgpu_merge_sample_t *a, const sbgpu_merge_sample_t *b, int32_t *count_a, int32_t *count_b, double *F_a,
+                               double *F_b);
+/* Device form (csrc/merge_device.h): the samples' key, count, F and X are device arrays on ctx's device, the offsets host arrays.
+ * The match (merge_match_small_kernel: a group of lanes of one wave per locus, no LDS; merge_match_deep_kernel: a workgroup
+ * per locus, A's keys in an LDS table of open addressing), one read-back of the per-locus B-only counts (a duplicate key is
+ * reported through them), the offsets on the host by the function the host form calls, the fill (merge_fill_kernel: a
+ * workgroup per tile of union rows, every output element written by exactly one thread; no global atomics), one
+ * synchronisation on `stream` (NULL: the context's own).  Every integer and every double is the host form's.  The device
+ * arrays lie in a scratch slot of their own and are valid until that context's next sbgpu_quantify_* or merge call.          */
+int sbgpu_bins_merge_device(sbgpu_ctx_t *ctx, const sbgpu_merge_sample_t *a, const sbgpu_merge_sample_t *b, void *stream,
+                            sbgpu_bins_merged_t *out);
+/* Copies the arrays the caller names (each may be NULL) of a merge that is still valid to host buffers sized from its n_bins
+ * and n_elem; synchronises on `stream`.                                                                                       */
+int sbgpu_bins_merge_fetch(sbgpu_ctx_t *ctx, const sbgpu_bins_merged_t *merged, int32_t *row_a, int32_t *row_b, int32_t *count_a,
+                           int32_t *count_b, double *F_a, double *F_b, void *stream);
+/* The thresholds (csrc/merge_rules.h, csrc/merge_device.h; from sizes -- a wave, the CU's 160 KB of LDS --, not tuned): out[0]
+ * bins of one sample up to which a locus takes the small form of the match (both samples at or below it; a lane per bin inside
+ * one wave64), the deep form beyond; [1] slots of the deep form's LDS table (the power of two at or above twice [2]: 64 KB, two
+ * workgroups to a CU); [2] the most rows of a union, and bins of one sample's locus; [3] weights of one tile of the fill, [4] the
+ * most rows of one tile: a locus of K isoforms is cut into tiles of max(1, min(out[4], out[3] / K)) rows; [5] threads of a
+ * workgroup; [6] workgroups per CU a launch's grid is capped at; [7] key words a lane of the small form holds in registers.   */
+int sbgpu_bins_merge_limits(int64_t out[8]);
+/* The differential usage of two RETAINED samples on one bin table: what sbgpu_model_diff_device takes, checked as it checks
+ * them (the same refusals).  Needs the handles' bin keys and (bin, isoform) pairs on the device: SBGPU_EUNSUPPORTED for a handle
+ * whose bins were grouped on the host (one from sbgpu_quantify_host is one); SBGPU_ESHAPE for a pair wider than 32 segments
+ * under a law that is not long_read.  Each record holds a host copy of the insert-size law its call weighed its bins under.
+ * The work: each law's table (sbgpu_insert_pdf_table) is built and uploaded; X_A = ALL of B's pairs weighed under A's law into a
+ * zeroed [n_elem_B] array by one sbgpu_binweight_device launch over B's own out_index, X_B likewise (a launch each, about the
+ * cost of a sample's own weight stage, and no pair compaction: the rows the fill does not read are the price); the merge
+ * above; ONE plan over the union's offsets, which serves both samples; sbgpu_em_diff_device on (count_u_A, F_u_A) and
+ * (count_u_B, F_u_B), unchanged.  Neither record changes; the work and the scratch are ctx_a's; ctx_b's stream is synchronised
+ * before its arrays are read.  merged_out (optional): the merge, as sbgpu_bins_merge_device reports it.  out NULL (merged_out
+ * given): the merge alone -- sbgpu_last_stage_ms then lists merge_xweights_a, merge_xweights_b, merge_match, merge_fill.        */
+int sbgpu_model_diff_merged_device(sbgpu_ctx_t *ctx_a, const sbgpu_bins_t *bins_a, sbgpu_ctx_t *ctx_b, const sbgpu_bins_t *bins_b,
+                                   const int32_t *d_keep_a, const int32_t *d_keep_b, const sbgpu_diff_params_t *params, void *stream,
+                                   sbgpu_em_diff_t *out, sbgpu_bins_merged_t *merged_out);
 
 /* ---- the EM bootstrap: how far theta can be trusted -------------------------
  * The reference prints theta with no statement of its spread.  The bootstrap resamples every locus' fragments over its

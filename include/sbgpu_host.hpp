@@ -1092,6 +1092,28 @@ class DifferentialUsage {
       t.done();
       return t;
    }
+   /* The same on ONE bin table for both samples: the union of their bins by key (sbgpu_model_diff_merged_device).
+    * merged, merged_row_off, merged_f_off: the merge -- its sizes, device arrays (ctx_a's, valid until its next quantify or merge
+    * call; sbgpu_bins_merge_fetch copies them) and the union's offsets.                                                        */
+   sbgpu_bins_merged_t merged{};
+   std::vector<int64_t> merged_row_off, merged_f_off; /* [n_loci + 1] */
+   static DifferentialUsage device_merged(const Context &ctx_a, const sbgpu_bins_t *bins_a, const Context &ctx_b, const sbgpu_bins_t *bins_b,
+                                          const int32_t *d_keep_a = nullptr, const int32_t *d_keep_b = nullptr, int64_t max_bytes = 0,
+                                          void *stream = nullptr)
+   {
+      int64_t info[8];
+      check(sbgpu_bins_info(bins_a, info), "sbgpu_bins_info");
+      DifferentialUsage t;
+      t.prepare(info[0], info[1]);
+      t.merged_row_off.assign((size_t)info[0] + 1, 0), t.merged_f_off.assign((size_t)info[0] + 1, 0);
+      t.merged.row_off = t.merged_row_off.data(), t.merged.f_off = t.merged_f_off.data();
+      const sbgpu_diff_params_t par{max_bytes, 0};
+      check(sbgpu_model_diff_merged_device(ctx_a.get(), bins_a, ctx_b.get(), bins_b, d_keep_a, d_keep_b, &par, stream, &t.raw, &t.merged),
+            "sbgpu_model_diff_merged_device");
+      t.merged.row_off = t.merged.f_off = nullptr;
+      t.done();
+      return t;
+   }
 
    /* (public for a caller that fills raw through the host form's three calls) */
    void prepare(int64_t n_loci, int64_t n_iso)

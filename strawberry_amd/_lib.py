@@ -53,6 +53,8 @@ SYMBOLS = [
     "sbgpu_model_loo_device", "sbgpu_em_loo_limits",
     "sbgpu_em_diff_shapes_host", "sbgpu_em_diff_expand_host", "sbgpu_em_diff_stat_host", "sbgpu_em_diff_device", "sbgpu_model_diff_device",
     "sbgpu_em_diff_limits",
+    "sbgpu_bins_merge_shapes_host", "sbgpu_bins_merge_fill_host", "sbgpu_bins_merge_device", "sbgpu_bins_merge_fetch", "sbgpu_bins_merge_limits",
+    "sbgpu_model_diff_merged_device",
     "sbgpu_body_profile_host", "sbgpu_body_profile_device", "sbgpu_body_profile_limits",
     "sbgpu_splice_events_shapes_host", "sbgpu_splice_events_build_host", "sbgpu_splice_psi_host", "sbgpu_splice_support_host",
     "sbgpu_splice_psi_device", "sbgpu_splice_support_device", "sbgpu_splice_limits",
@@ -213,6 +215,16 @@ class sbgpu_em_diff_t(C.Structure):
 
 class sbgpu_diff_params_t(C.Structure):
     _fields_ = [("max_bytes", C.c_int64), ("reserved", C.c_int64)]
+
+
+class sbgpu_merge_sample_t(C.Structure):
+    _fields_ = [("n_loci", C.c_int64), ("iso_off", C.c_void_p), ("row_off", C.c_void_p), ("key_words", C.c_int32), ("reserved", C.c_int32),
+                ("key", C.c_void_p), ("count", C.c_void_p), ("F", C.c_void_p), ("X", C.c_void_p)]
+
+
+class sbgpu_bins_merged_t(C.Structure):
+    _NAMES = ("row_a", "row_b", "count_a", "count_b", "F_a", "F_b")
+    _fields_ = [("n_bins", C.c_int64), ("n_elem", C.c_int64), ("row_off", C.c_void_p), ("f_off", C.c_void_p)] + [("d_" + n, C.c_void_p) for n in _NAMES]
 
 
 class sbgpu_bootstrap_params_t(C.Structure):
@@ -423,6 +435,13 @@ def load():
     L.sbgpu_em_diff_device.argtypes = [vp] * 9 + [C.POINTER(sbgpu_diff_params_t), vp, C.POINTER(sbgpu_em_diff_t)]
     L.sbgpu_model_diff_device.argtypes = [vp] * 6 + [C.POINTER(sbgpu_diff_params_t), vp, C.POINTER(sbgpu_em_diff_t)]
     L.sbgpu_em_diff_limits.argtypes = [C.POINTER(C.c_int64)]
+    ms, mg = C.POINTER(sbgpu_merge_sample_t), C.POINTER(sbgpu_bins_merged_t)
+    L.sbgpu_bins_merge_shapes_host.argtypes = [ms, ms, C.POINTER(C.c_int64), vp, vp, vp, vp]
+    L.sbgpu_bins_merge_fill_host.argtypes = [ms, ms, vp, vp, vp, vp]
+    L.sbgpu_bins_merge_device.argtypes = [vp, ms, ms, vp, mg]
+    L.sbgpu_bins_merge_fetch.argtypes = [vp, mg] + [vp] * 7
+    L.sbgpu_bins_merge_limits.argtypes = [C.POINTER(C.c_int64)]
+    L.sbgpu_model_diff_merged_device.argtypes = [vp] * 6 + [C.POINTER(sbgpu_diff_params_t), vp, C.POINTER(sbgpu_em_diff_t), mg]
     L.sbgpu_body_profile_host.argtypes = [vp, C.POINTER(sbgpu_annotation_t), C.POINTER(sbgpu_hits_t), vp, C.c_int32, vp, vp, vp, vp, vp, vp,
                                           C.c_int32, C.POINTER(sbgpu_body_profile_t)]
     L.sbgpu_body_profile_device.argtypes = [vp, vp, C.POINTER(sbgpu_annotation_t), C.POINTER(sbgpu_hits_t), vp, vp, vp, C.c_int32, vp,

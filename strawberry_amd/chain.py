@@ -421,15 +421,23 @@ class ChainQuantifier:
         return support.model_loo_device(self.ctx, self.context_handle, int(self._out.d_keep), keep=self.keep[:self.n_iso], max_bytes=max_bytes,
                                         want=want)
 
-    def differential_usage(self, other, max_bytes=0, want=None, with_sub_batch=False):
+    def differential_usage(self, other, max_bytes=0, want=None, with_sub_batch=False, shared_bins=False, merged_want=()):
         """Differential isoform usage between this object's last step (sample A) and `other`'s (sample B), both made with
         keep_bootstrap=True over the same annotation, on contexts of one device: diff.model_diff_device on the two handles with
         the two steps' keeps -> a diff.DifferentialUsage.  Neither object's results change.  max_bytes: the scratch budget of one
-        chunk of sub-problems (0: 1 GiB); want: the arrays to bring to the host (None: all); with_sub_batch: diff.em_diff_device's."""
+        chunk of sub-problems (0: 1 GiB); want: the arrays to bring to the host (None: all); with_sub_batch: diff.em_diff_device's.
+        shared_bins=True: both samples are tested on ONE bin table, the union of their bins by key (diff.model_diff_merged_device;
+        DESIGN 3.29); the result then carries the merge.MergedBins as .merged -- its offsets and device addresses, and the arrays
+        merged_want names on the host (None: all)."""
         from . import diff
         for q in (self, other):
             if q.context_handle is None or not q.keep_bootstrap:
                 raise _lib.SbgpuError("differential_usage: no step has run with keep_bootstrap=True")
+        if shared_bins:
+            if with_sub_batch:
+                raise ValueError("differential_usage: with_sub_batch describes the unmerged tables: not with shared_bins=True")
+            return diff.model_diff_merged_device(self.ctx, self.context_handle, other.ctx, other.context_handle, int(self._out.d_keep),
+                                                 int(other._out.d_keep), max_bytes=max_bytes, want=want, merged_want=merged_want)
         return diff.model_diff_device(self.ctx, self.context_handle, other.ctx, other.context_handle, int(self._out.d_keep), int(other._out.d_keep),
                                       keep_a=self.keep[:self.n_iso], keep_b=other.keep[:other.n_iso], max_bytes=max_bytes, want=want,
                                       with_sub_batch=with_sub_batch)

@@ -178,10 +178,10 @@ hipStream_t ctx_stream(const sbgpu_ctx_t *ctx); // the context's own stream
 hipStream_t ctx_aux_stream(const sbgpu_ctx_t *ctx, int i); // one of the context's side streams (0..7; the EM's kinds use 0, 1, 2, 6)
 int ctx_cu_count(const sbgpu_ctx_t *ctx);
 int ctx_device(const sbgpu_ctx_t *ctx);        // the HIP device the context was made on
-// device scratch that lives with the context (slot 0..15; grows on demand, never shrinks): valid until the next request for the
+// device scratch that lives with the context (slot 0..16; grows on demand, never shrinks): valid until the next request for the
 // same slot; one host thread per context.  Slots 0..7 are the chain's; the retained-result stages' have names:
-enum ScratchSlot { kScratchContextTable = 8, kScratchAssign = 9, kScratchCoverage = 10, kScratchFit = 11, kScratchInfo = 12, kScratchLoo = 13, kScratchBody = 14, kScratchDiff = 15 };
-constexpr int kScratchSlots = 16;
+enum ScratchSlot { kScratchContextTable = 8, kScratchAssign = 9, kScratchCoverage = 10, kScratchFit = 11, kScratchInfo = 12, kScratchLoo = 13, kScratchBody = 14, kScratchDiff = 15, kScratchMerge = 16 };
+constexpr int kScratchSlots = 17;
 hipError_t ctx_scratch(sbgpu_ctx_t *ctx, int slot, size_t bytes, char **out);
 // Device allocations that change hands (a handle's arenas, a plan's arena): a hipMalloc / hipFree pair per call costs a
 // few hundred microseconds -- seconds for the tens of GB of a sample-sized call -- and the free waits for the device, so
@@ -305,6 +305,13 @@ struct BootKeep {
    const double *d_F = nullptr;        // [n_elem] the raw bin weights
    const int32_t *d_iso_len = nullptr; // [n_iso] the isoforms' exonic lengths
    sbgpu_abundance_params_t params{};  // as the call's epilogue used them (total_mapped_reads and insert_mean filled in)
+   // the insert-size law the call weighed its bins under, for a stage that weighs ANOTHER sample's bins under it (merge_api.hip):
+   // a host copy, histogram included (insert.emp_hist points into insert_hist); insert_table: the call built a table from it
+   // (false: long reads without a law, whose weights read none); pdf_len: the table's length
+   sbgpu_insert_t insert{};
+   std::vector<double> insert_hist;
+   bool insert_table = false;
+   int32_t pdf_len = 0;
 };
 BootKeep *ctx_boot_keep(sbgpu_ctx_t *ctx);
 // the record's plan and the bootstrap's result block go back (both wait for the device); the record ends

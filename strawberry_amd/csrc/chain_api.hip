@@ -869,6 +869,12 @@ int QuantifyCall::finish_handle(const WorkArena &w)
       boot_rec->d_count = d_count_dev ? d_count_dev : w.count(); // (the handle's arena / the no-hits route's upload)
       boot_rec->d_F = w.F(), boot_rec->d_iso_len = d_iso_len;
       boot_rec->params = epi_params;
+      // the law the weights were made under, as a copy the record owns
+      boot_rec->insert = law.ins, boot_rec->insert_table = a.insert != nullptr || !a.long_read, boot_rec->pdf_len = law.pdf_len;
+      boot_rec->insert_hist.clear();
+      if (law.ins.use_emp && law.ins.emp_hist && law.ins.end_offset >= law.ins.start_offset)
+         boot_rec->insert_hist.assign(law.ins.emp_hist, law.ins.emp_hist + ((int64_t)law.ins.end_offset - law.ins.start_offset + 1));
+      boot_rec->insert.emp_hist = boot_rec->insert_hist.empty() ? nullptr : boot_rec->insert_hist.data();
       sb::bins_set_boot_serial(bins, boot_rec->serial);
    }
    if (retain) {

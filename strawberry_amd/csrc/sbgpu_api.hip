@@ -303,8 +303,8 @@ hipError_t ctx_scratch(sbgpu_ctx_t *ctx, int slot, size_t bytes, char **out)
    if (slot < 0 || slot >= kScratchSlots) return hipErrorInvalidValue;
    // what a resident call kept for sbgpu_context_table_device lies in slots 0..7: whoever asks for one of them (any entry that
    // works in the context's scratch, not only sbgpu_quantify_*) may overwrite or free it, so the record ends here
-   // (8 .. 15 hold what is made FROM the record: the context table, the fragment assignment, the isoform coverage,
-   // the model fit, the isoform information, the isoform support, the body profile, the differential usage)
+   // (8 .. 16 hold what is made FROM the record: the context table, the fragment assignment, the isoform coverage,
+   // the model fit, the isoform information, the isoform support, the body profile, the differential usage, the bin-table merge)
    if (slot < 8) ctx->context_keep.serial = 0, ctx->boot_keep.serial = 0;
    if (bytes < 256) bytes = 256;
    if (ctx->scratch_bytes[slot] < bytes) {

@@ -292,6 +292,47 @@ inline DiffChunkLayout diff_chunk_layout(int64_t n_tiles, int64_t n_items, int64
    return L;
 }
 
+// The bin-table merge.  Its match works in a block of its own (the union's size is only known behind it, and a
+// context's scratch slot loses its contents when it grows); the merged arrays, which outlive the call, are the slot's.
+struct MergeItem {
+   int32_t first, n, lanes, pad; // small form: loci list[first .. first + n) share a workgroup, `lanes` lanes each
+};
+struct MergeTile {
+   int32_t locus, row0, rows, pad; // union rows [row0, row0 + rows) of the locus
+};
+struct MergeMatchLayout {
+   size_t roff_a, roff_b, ioff, foff_a, foff_b, small, items, deep, upload_bytes; // the offsets, the two lists of loci, the small form's items
+   size_t b_of_a, b_only, n_only, bytes;
+};
+inline MergeMatchLayout merge_match_layout(int64_t n_loci, int64_t n_bins_a, int64_t n_bins_b, size_t n_small, size_t n_items, size_t n_deep)
+{
+   const size_t nl1 = (size_t)n_loci + 1;
+   Arena a;
+   MergeMatchLayout L;
+   L.roff_a = a.take(nl1 * 8), L.roff_b = a.take(nl1 * 8), L.ioff = a.take(nl1 * 8), L.foff_a = a.take(nl1 * 8), L.foff_b = a.take(nl1 * 8);
+   L.small = a.take((n_small + 1) * 4), L.items = a.take((n_items + 1) * sizeof(MergeItem)), L.deep = a.take((n_deep + 1) * 4);
+   L.upload_bytes = a.size;
+   L.b_of_a = a.take(at_least_1(n_bins_a) * 4), L.b_only = a.take(at_least_1(n_bins_b) * 4), L.n_only = a.take(nl1 * 4);
+   L.bytes = a.size;
+   return L;
+}
+struct MergeLayout {
+   size_t roff_u, foff_u, tiles, upload_bytes;
+   size_t row_a, row_b, count_a, count_b, F_a, F_b, bytes;
+};
+inline MergeLayout merge_layout(int64_t n_loci, int64_t n_bins_u, int64_t n_elem_u, size_t n_tiles)
+{
+   const size_t nl1 = (size_t)n_loci + 1, nb1 = at_least_1(n_bins_u), ne1 = at_least_1(n_elem_u);
+   Arena a;
+   MergeLayout L;
+   L.roff_u = a.take(nl1 * 8), L.foff_u = a.take(nl1 * 8), L.tiles = a.take((n_tiles + 1) * sizeof(MergeTile));
+   L.upload_bytes = a.size;
+   L.row_a = a.take(nb1 * 4), L.row_b = a.take(nb1 * 4), L.count_a = a.take(nb1 * 4), L.count_b = a.take(nb1 * 4);
+   L.F_a = a.take(ne1 * 8), L.F_b = a.take(ne1 * 8);
+   L.bytes = a.size;
+   return L;
+}
+
 // ---- the host forms' shared loops.  Every sum runs in the order the kernels' do: a column's over the live bins, ascending.
 
 // The kept words of one locus into K [(niso + 31) / 32] -> their number.  keep_of_locus null: no filter was given and every

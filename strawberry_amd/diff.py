@@ -6,8 +6,13 @@ em_diff_host       the three host calls around a solver the caller brings (the l
 em_diff_device     sbgpu_em_diff_device: built in HBM for two batches of one annotation
 model_diff_device  sbgpu_model_diff_device: from what two resident calls kept for the bootstrap on two contexts of one device
                    (ChainQuantifier / FrontQuantifier(keep_bootstrap=True).differential_usage(other))
+model_diff_merged_device  sbgpu_model_diff_merged_device: the same two retained samples on ONE bin table, the union of their bins by
+                   key (differential_usage(other, shared_bins=True); merge.py)
 
 All return a DifferentialUsage.  The per-isoform arrays are laid out as theta is.
+
+model_diff_device tests each sample on the bins it observed, so part of a reported difference is that difference of conditioning
+(the CAVEAT of include/sbgpu.h's differential-usage block); model_diff_merged_device removes it for bins a sample did not observe.
 """
 import ctypes as C
 import math
@@ -279,4 +284,31 @@ def model_diff_device(ctx_a, handle_a, ctx_b, handle_b, d_keep_a=None, d_keep_b=
         t.sub = dict(sh, count=sub_count[:-1], F=sub_F[:-1])
     _lib.check(L.sbgpu_model_diff_device(ctx_a.h, handle_a, ctx_b.h, handle_b, addr(d_keep_a), addr(d_keep_b), C.byref(p), stream, C.byref(s)),
                "sbgpu_model_diff_device")
+    return t._finish(s)
+
+
+def model_diff_merged_device(ctx_a, handle_a, ctx_b, handle_b, d_keep_a=None, d_keep_b=None, max_bytes=0, stream=None, want=None, merged_want=(),
+                             merge_only=False):
+    """As model_diff_device, on ONE bin table for both samples: the union of their bins by key, zero counts where a sample saw
+    nothing, a missing bin's weights from the other sample's bin under this sample's insert-size law (sbgpu_model_diff_merged_device;
+    DESIGN 3.29).  Needs handles whose bins were grouped on the device.  The result carries the merge.MergedBins as .merged:
+    offsets, device addresses, and on the host the arrays merged_want names (None: all).  merge_only: no test -- the MergedBins
+    alone is returned (and the context's stage times are the merge's)."""
+    from . import merge as _merge
+    L = ctx_a.L
+    handle_a, handle_b = getattr(handle_a, "h", handle_a), getattr(handle_b, "h", handle_b)
+    if handle_a is None or handle_b is None:
+        raise _lib.SbgpuError("model_diff_merged_device: null argument (a handle is None)")
+    check_tensors("model_diff_merged_device", d_keep_a=(d_keep_a, "torch.int32"), d_keep_b=(d_keep_b, "torch.int32"))
+    n_loci = bins_info(L, handle_a)[0]
+    row_off, iso_off = np.zeros(n_loci + 1, np.int64), np.zeros(n_loci + 1, np.int64)
+    _lib.check(L.sbgpu_bins_export(handle_a, row_off.ctypes.data, iso_off.ctypes.data, *([None] * 11)), "sbgpu_bins_export")
+    t, m = DifferentialUsage(iso_off, want), _merge.MergedBins(iso_off, merged_want)
+    s, ms, p = t._struct(), m._struct(), params(max_bytes)
+    _lib.check(L.sbgpu_model_diff_merged_device(ctx_a.h, handle_a, ctx_b.h, handle_b, addr(d_keep_a), addr(d_keep_b), C.byref(p), stream,
+                                                None if merge_only else C.byref(s), C.byref(ms)), "sbgpu_model_diff_merged_device")
+    m.fetch(ctx_a, ms, stream)
+    if merge_only:
+        return m
+    t.merged = m
     return t._finish(s)
