@@ -15,7 +15,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/sbgpu.h"
-#include "api_internal.h"
+#include "front_common.h"
 #include "bamdecode_device.h"
 
 using sb::api_fail;
@@ -44,28 +44,18 @@ const int64_t *bamreads_device_record(const sbgpu_bamreads_t *b) { return b && b
 } // namespace sb
 
 namespace {
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// the handle's arrays inside one block of memory; returns its size
-size_t lay_out(sbgpu_bamreads *B, char *base)
+// the handle's arrays inside one block of memory laid out by front_schedule.h
+void place(sbgpu_bamreads *B, char *base, const sb::BamReadsLayout &L)
 {
-   size_t off = 0;
-   auto take = [&](size_t bytes) {
-      char *p = base ? base + off : nullptr;
-      off += up256(bytes ? bytes : 8);
-      return p;
-   };
-   const size_t n = (size_t)B->n_records, m = (size_t)B->n_reads, nb = (size_t)B->n_blocks;
-   B->status = (uint8_t *)take(n);
-   B->record = (int64_t *)take(m * 8);
-   B->read_id = (uint64_t *)take(m * 8);
-   B->ref = (int32_t *)take(m * 4), B->nh = (int32_t *)take(m * 4), B->nm = (int32_t *)take(m * 4), B->read_len = (int32_t *)take(m * 4);
-   B->left = (uint32_t *)take(m * 4), B->right = (uint32_t *)take(m * 4), B->partner_pos = (uint32_t *)take(m * 4);
-   B->sam_flag = (uint32_t *)take(m * 4);
-   B->flags = (uint8_t *)take(m);
-   B->block_off = (int64_t *)take((m + 1) * 8);
-   B->block_left = (uint32_t *)take(nb * 4), B->block_right = (uint32_t *)take(nb * 4);
-   return off;
+   B->status = (uint8_t *)(base + L.status);
+   B->record = (int64_t *)(base + L.record);
+   B->read_id = (uint64_t *)(base + L.read_id);
+   B->ref = (int32_t *)(base + L.ref), B->nh = (int32_t *)(base + L.nh), B->nm = (int32_t *)(base + L.nm), B->read_len = (int32_t *)(base + L.read_len);
+   B->left = (uint32_t *)(base + L.left), B->right = (uint32_t *)(base + L.right), B->partner_pos = (uint32_t *)(base + L.partner_pos);
+   B->sam_flag = (uint32_t *)(base + L.sam_flag);
+   B->flags = (uint8_t *)(base + L.flags);
+   B->block_off = (int64_t *)(base + L.block_off);
+   B->block_left = (uint32_t *)(base + L.block_left), B->block_right = (uint32_t *)(base + L.block_right);
 }
 
 int check_opts(const sbgpu_bam_opts_t *o, const char *who)
@@ -168,8 +158,9 @@ int sbgpu_bam_decode_host(const uint8_t *bytes, int64_t n_bytes, const int64_t *
          for (int k = 0; k <= SBGPU_BAM_TRUNCATED; ++k) B->by_status[k] += part[t].by_status[k];
       }
       B->n_reads = read_base[nt], B->n_blocks = block_base[nt];
-      B->host.resize(lay_out(B, nullptr));
-      lay_out(B, B->host.data());
+      const sb::BamReadsLayout R = sb::bam_reads_layout(B->n_records, B->n_reads, B->n_blocks);
+      B->host.resize(R.bytes);
+      place(B, B->host.data(), R);
       run([&](unsigned t) {
          const Part &p = part[t];
          int64_t k = read_base[t], b = block_base[t];
@@ -198,6 +189,150 @@ int sbgpu_bam_decode_host(const uint8_t *bytes, int64_t n_bytes, const int64_t *
    return SBGPU_OK;
 }
 
+} // extern "C"
+
+namespace {
+static_assert(sb::kOneWaves == sb::kFrontOneWaves && sb::kOneTile == sb::kFrontOneTile && sb::kBamInlineBlocks == sb::kFrontInlineBlocks,
+              "front_schedule.h sizes the decode's launches and scratch");
+
+// ---- the device decode: the one-pass kernel where it can serve the call, else two passes.  What the call decides is
+// front_schedule.h's (the two launches, the three layouts); the steps below issue it.
+struct BamDecodeCall {
+   sbgpu_ctx_t *const c;
+   const uint8_t *const d_bytes;
+   const int64_t n_bytes;
+   const int64_t *const d_rec_off;
+   const int64_t n;
+   const sbgpu_bam_opts_t *const opts;
+   const hipStream_t s;
+   sbgpu_bamreads *const B;
+   int lds_max = 0; // what a workgroup may ask for on this device
+
+   // the handle's arrays, sized by its counts, in an arena of their own
+   int take_arena()
+   {
+      const sb::BamReadsLayout R = sb::bam_reads_layout(B->n_records, B->n_reads, B->n_blocks);
+      SB_FRONT_TRY(sb::dev_take(R.bytes, &B->arena, &B->arena_cap));
+      place(B, B->arena, R);
+      return SBGPU_OK;
+   }
+   void set_counts(const unsigned long long *counts)
+   {
+      for (int k = 0; k <= SBGPU_BAM_TRUNCATED; ++k) B->by_status[k] = (int64_t)counts[k];
+      B->any_paired = counts[11] ? 1 : 0;
+   }
+
+   // ---- one pass (bam_onepass_kernel): the handle's arrays get room for EVERY record and two blocks per record; a sample
+   // whose accepted records hold more blocks than that (or a look-back that ran out, or a launch that is refused -- the staging
+   // buffer on a device with less LDS than it was told) is not served: *served is false and the handle has no arena
+   int one_pass(bool *served)
+   {
+      const sb::BamOnepassLaunch p = sb::bam_onepass_launch(n, n_bytes, lds_max, sb::ctx_cu_count(c));
+      B->n_reads = n, B->n_blocks = p.block_cap;
+      SB_FRONT_RC(take_arena());
+      const sb::BamOnepassScratch L = sb::bam_onepass_scratch(p.tiles);
+      sb::DevBlock w(s);
+      SB_FRONT_TRY(w.take(L.bytes));
+      SB_FRONT_TRY(hipMemsetAsync(w.p, 0, L.bytes, s));
+      sb::BamOneArgs a = {};
+      a.bytes = d_bytes, a.n_bytes = n_bytes, a.rec_off = d_rec_off, a.n = n, a.opts = *opts;
+      a.status = B->status;
+      a.o_record = B->record, a.o_read_id = B->read_id, a.o_ref = B->ref, a.o_nh = B->nh, a.o_nm = B->nm, a.o_read_len = B->read_len;
+      a.o_left = B->left, a.o_right = B->right, a.o_partner_pos = B->partner_pos, a.o_sam_flag = B->sam_flag, a.o_flags = B->flags;
+      a.o_block_off = B->block_off, a.o_block_left = B->block_left, a.o_block_right = B->block_right, a.block_cap = p.block_cap;
+      a.counts = w.at<unsigned long long>(L.counts), a.tile_state = w.at<unsigned long long>(L.state), a.ticket = w.at<unsigned int>(L.ticket);
+      hipLaunchKernelGGL(sb::bam_onepass_kernel, dim3((unsigned)p.grid), dim3(64 * sb::kOneWaves), (size_t)p.stage_bytes * sb::kOneWaves, s, a, p.stage_bytes);
+      unsigned long long counts[16] = {};
+      counts[12] = 1;
+      if (hipGetLastError() == hipSuccess) {
+         SB_FRONT_TRY(hipMemcpyAsync(counts, w.p + L.counts, sizeof(counts), hipMemcpyDeviceToHost, s));
+         SB_FRONT_TRY(hipStreamSynchronize(s));
+      }
+      w.give();
+      *served = counts[12] == 0;
+      if (*served) {
+         B->n_reads = (int64_t)counts[13], B->n_blocks = (int64_t)counts[14];
+         set_counts(counts);
+      } else {
+         sb::dev_give(B->arena, B->arena_cap);
+         B->arena = nullptr, B->arena_cap = 0;
+      }
+      return SBGPU_OK;
+   }
+
+   // ---- two passes: decide and count (bam_scan_kernel), scans over the waves' totals, compact (bam_fill_kernel)
+   int two_passes()
+   {
+      const sb::BamScanLaunch p = sb::bam_scan_launch(n, n_bytes, lds_max, sb::ctx_cu_count(c));
+      size_t tmp_bytes = 0;
+      (void)rocprim::exclusive_scan(nullptr, tmp_bytes, rocprim::make_transform_iterator((const int32_t *)nullptr, sb::I32AsI64()), (int64_t *)nullptr, (int64_t)0, sb::front_tiles64((size_t)n) + 1, rocprim::plus<int64_t>(), s);
+      const sb::BamScanScratch L = sb::bam_scan_scratch(n, tmp_bytes);
+      sb::DevBlock w(s);
+      SB_FRONT_TRY(w.take(L.bytes));
+      SB_FRONT_TRY(hipMemsetAsync(w.p + L.cnt, 0, L.cnt_bytes, s));
+      SB_FRONT_TRY(hipMemsetAsync(w.p + L.tr_tail, 0, 4, s));
+      SB_FRONT_TRY(hipMemsetAsync(w.p + L.tb_tail, 0, 4, s));
+      sb::BamScanArgs a = {};
+      a.bytes = d_bytes, a.n_bytes = n_bytes, a.rec_off = d_rec_off, a.n = n, a.opts = *opts;
+      a.status = w.at<uint8_t>(L.status), a.n_blocks = w.at<int32_t>(L.nb), a.accepted = w.at<uint8_t>(L.acc);
+      a.read_id = w.at<uint64_t>(L.rid), a.ref = w.at<int32_t>(L.ref), a.nh = w.at<int32_t>(L.nh), a.nm = w.at<int32_t>(L.nm);
+      a.read_len = w.at<int32_t>(L.rl), a.left = w.at<uint32_t>(L.left), a.right = w.at<uint32_t>(L.right);
+      a.partner_pos = w.at<uint32_t>(L.pp), a.sam_flag = w.at<uint32_t>(L.sf), a.flags = w.at<uint8_t>(L.fl);
+      a.inline_blocks = w.at<uint32_t>(L.ib);
+      a.counts = w.at<unsigned long long>(L.cnt);
+      a.tile_reads = w.at<int32_t>(L.tr), a.tile_blocks = w.at<int32_t>(L.tb);
+      // (a launch that is refused all the same is repeated without the staging buffer: the kernel then walks every record in
+      // global memory: slower, same results)
+      hipLaunchKernelGGL(sb::bam_scan_kernel, dim3((unsigned)p.scan_blocks), dim3(64), (size_t)p.stage_bytes, s, a, p.stage_bytes);
+      if (hipGetLastError() != hipSuccess && p.stage_bytes > 0) hipLaunchKernelGGL(sb::bam_scan_kernel, dim3((unsigned)p.scan_blocks), dim3(64), 0, s, a, 0);
+      SB_FRONT_TRY(hipGetLastError());
+      size_t tb = tmp_bytes;
+      SB_FRONT_TRY(rocprim::exclusive_scan(w.p + L.tmp, tb, rocprim::make_transform_iterator((const int32_t *)a.tile_reads, sb::I32AsI64()), w.at<int64_t>(L.rat), (int64_t)0, L.tiles + 1, rocprim::plus<int64_t>(), s));
+      tb = tmp_bytes;
+      SB_FRONT_TRY(rocprim::exclusive_scan(w.p + L.tmp, tb, rocprim::make_transform_iterator((const int32_t *)a.tile_blocks, sb::I32AsI64()), w.at<int64_t>(L.bat), (int64_t)0, L.tiles + 1, rocprim::plus<int64_t>(), s));
+      // the totals: the output arena's size depends on them
+      int64_t totals[2] = {0, 0};
+      unsigned long long counts[16];
+      SB_FRONT_TRY(hipMemcpyAsync(&totals[0], w.p + L.rat_total, 8, hipMemcpyDeviceToHost, s));
+      SB_FRONT_TRY(hipMemcpyAsync(&totals[1], w.p + L.bat_total, 8, hipMemcpyDeviceToHost, s));
+      SB_FRONT_TRY(hipMemcpyAsync(counts, w.p + L.cnt, sizeof(counts), hipMemcpyDeviceToHost, s));
+      SB_FRONT_TRY(hipStreamSynchronize(s));
+      B->n_reads = totals[0], B->n_blocks = totals[1];
+      set_counts(counts);
+      SB_FRONT_RC(take_arena());
+      SB_FRONT_TRY(hipMemcpyAsync(B->status, w.p + L.status, (size_t)n, hipMemcpyDeviceToDevice, s));
+      sb::BamFillArgs f = {};
+      f.bytes = d_bytes, f.rec_off = d_rec_off, f.n = n;
+      f.accepted = a.accepted, f.tile_read_at = w.at<const int64_t>(L.rat), f.tile_block_at = w.at<const int64_t>(L.bat);
+      f.read_id = a.read_id, f.ref = a.ref, f.nh = a.nh, f.nm = a.nm, f.read_len = a.read_len;
+      f.left = a.left, f.right = a.right, f.partner_pos = a.partner_pos, f.sam_flag = a.sam_flag, f.flags = a.flags;
+      f.n_blocks = a.n_blocks, f.inline_blocks = a.inline_blocks;
+      f.o_record = B->record, f.o_read_id = B->read_id, f.o_ref = B->ref, f.o_nh = B->nh, f.o_nm = B->nm, f.o_read_len = B->read_len;
+      f.o_left = B->left, f.o_right = B->right, f.o_partner_pos = B->partner_pos, f.o_sam_flag = B->sam_flag, f.o_flags = B->flags;
+      f.o_block_off = B->block_off, f.o_block_left = B->block_left, f.o_block_right = B->block_right;
+      hipLaunchKernelGGL(sb::bam_fill_kernel, dim3((unsigned)p.fill_blocks), dim3(256), 0, s, f);
+      SB_FRONT_TRY(hipGetLastError());
+      SB_FRONT_TRY(hipStreamSynchronize(s)); // (the scratch goes back to the pool; the handle's arrays are complete when the call returns)
+      return SBGPU_OK;
+   }
+
+   int run(const sb::FrontHooks &hooks)
+   {
+      SB_FRONT_TRY(hipSetDevice(B->device));
+      if (n == 0) return SBGPU_OK;
+      if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, sb::ctx_device(c)) != hipSuccess || lds_max <= 0) lds_max = 64 * 1024;
+      if (!hooks.bam_two_pass && n <= sb::kOneMaxRecords) {
+         bool served = false;
+         SB_FRONT_RC(one_pass(&served));
+         if (served) return SBGPU_OK;
+      }
+      return two_passes();
+   }
+};
+} // namespace
+
+extern "C" {
+
 int sbgpu_bam_decode_device(sbgpu_ctx_t *c, const uint8_t *d_bytes, int64_t n_bytes, const int64_t *d_rec_off, int64_t n,
                             const sbgpu_bam_opts_t *opts, void *stream, sbgpu_bamreads_t **out)
 {
@@ -205,159 +340,14 @@ int sbgpu_bam_decode_device(sbgpu_ctx_t *c, const uint8_t *d_bytes, int64_t n_by
    *out = nullptr;
    if (const int rc = check_opts(opts, "sbgpu_bam_decode_device")) return rc;
    if (n >= ((int64_t)1 << 31) - 2) return api_fail(SBGPU_EUNSUPPORTED, "sbgpu_bam_decode_device: more than 2^31 records in one call; split the stream");
-   sbgpu_bamreads *B = new (std::nothrow) sbgpu_bamreads();
+   sb::BamReadsHandle B(new (std::nothrow) sbgpu_bamreads());
    if (!B) return api_fail(SBGPU_ENOMEM, "sbgpu_bam_decode_device: out of memory");
    B->on_device = true;
    B->device = sb::ctx_device(c);
    B->n_records = n;
-   hipStream_t s = stream ? (hipStream_t)stream : sb::ctx_stream(c);
-   char *w = nullptr;
-   size_t w_cap = 0;
-   auto bail = [&](int code, const std::string &msg) {
-      (void)hipStreamSynchronize(s);
-      sb::dev_give(w, w_cap);
-      sbgpu_bamreads_destroy(B);
-      return api_fail(code, msg);
-   };
-#define SB_TRY(expr)                                                                                     \
-   do {                                                                                                  \
-      hipError_t e_ = (expr);                                                                            \
-      if (e_ != hipSuccess) return bail(e_ == hipErrorOutOfMemory ? SBGPU_ENOMEM : SBGPU_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-   } while (0)
-   SB_TRY(hipSetDevice(B->device));
-   if (n == 0) {
-      *out = B;
-      return SBGPU_OK;
-   }
-   // what a workgroup may ask for on this device
-   int lds_max = 0;
-   if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, sb::ctx_device(c)) != hipSuccess || lds_max <= 0) lds_max = 64 * 1024;
-   // ---- one pass (bam_onepass_kernel): the handle's arrays get room for EVERY record and two blocks per record; a sample
-   // whose accepted records hold more blocks than that (or more than 2^30 records, or a look-back that ran out) is decoded
-   // by the two kernels below instead
-   const bool two_pass_only = std::getenv("SBGPU_BAM_TWO_PASS") && std::atoi(std::getenv("SBGPU_BAM_TWO_PASS")) != 0; // (the tests' hook for the fallback)
-   if (!two_pass_only && n <= sb::kOneMaxRecords) {
-      const int64_t block_cap = 2 * n + 1024;
-      B->n_reads = n, B->n_blocks = block_cap;
-      SB_TRY(sb::dev_take(lay_out(B, nullptr), &B->arena, &B->arena_cap));
-      lay_out(B, B->arena);
-      const size_t tiles = ((size_t)n + sb::kOneTile - 1) / sb::kOneTile;
-      const size_t o_state = 0, o_cnt1 = up256(tiles * 8), o_ticket = o_cnt1 + up256(16 * 8), w_bytes = o_ticket + 256;
-      SB_TRY(sb::dev_take(w_bytes, &w, &w_cap));
-      SB_TRY(hipMemsetAsync(w, 0, w_bytes, s));
-      sb::BamOneArgs a = {};
-      a.bytes = d_bytes, a.n_bytes = n_bytes, a.rec_off = d_rec_off, a.n = n, a.opts = *opts;
-      a.status = B->status;
-      a.o_record = B->record, a.o_read_id = B->read_id, a.o_ref = B->ref, a.o_nh = B->nh, a.o_nm = B->nm, a.o_read_len = B->read_len;
-      a.o_left = B->left, a.o_right = B->right, a.o_partner_pos = B->partner_pos, a.o_sam_flag = B->sam_flag, a.o_flags = B->flags;
-      a.o_block_off = B->block_off, a.o_block_left = B->block_left, a.o_block_right = B->block_right, a.block_cap = block_cap;
-      a.counts = (unsigned long long *)(w + o_cnt1), a.tile_state = (unsigned long long *)(w + o_state), a.ticket = (unsigned int *)(w + o_ticket);
-      // a wave's part of the staging buffer: 64 average records + 4 % + 512 bytes, in steps of 256 (a pass whose records do
-      // not fit walks them in global memory: slower, same results) -- three workgroups of four waves then fit a CU's 160 KB
-      // up to ~195 bytes per record
-      int stage_bytes = (int)std::min<int64_t>(std::max<int64_t>(4096, ((64 * (n_bytes / n + 1)) * 26 / 25 + 512 + 255) & ~(int64_t)255), 32 * 1024);
-      stage_bytes = std::max(0, std::min(stage_bytes, (lds_max - 512) / sb::kOneWaves)) & ~255;
-      const int resident = std::max(1, std::min(8, (int)(160 * 1024 / ((size_t)stage_bytes * sb::kOneWaves + 512))));
-      const int64_t grid = std::min<int64_t>((int64_t)tiles, (int64_t)sb::ctx_cu_count(c) * resident);
-      hipLaunchKernelGGL(sb::bam_onepass_kernel, dim3((unsigned)grid), dim3(64 * sb::kOneWaves), (size_t)stage_bytes * sb::kOneWaves, s, a, stage_bytes);
-      // (a launch that is refused -- the staging buffer on a device with less LDS than it was told -- counts as a failure too)
-      unsigned long long counts[16] = {};
-      counts[12] = 1;
-      if (hipGetLastError() == hipSuccess) {
-         SB_TRY(hipMemcpyAsync(counts, w + o_cnt1, sizeof(counts), hipMemcpyDeviceToHost, s));
-         SB_TRY(hipStreamSynchronize(s));
-      }
-      sb::dev_give(w, w_cap);
-      w = nullptr, w_cap = 0;
-      if (counts[12] == 0) {
-         B->n_reads = (int64_t)counts[13], B->n_blocks = (int64_t)counts[14];
-         for (int k = 0; k <= SBGPU_BAM_TRUNCATED; ++k) B->by_status[k] = (int64_t)counts[k];
-         B->any_paired = counts[11] ? 1 : 0;
-         *out = B;
-         return SBGPU_OK;
-      }
-      sb::dev_give(B->arena, B->arena_cap);
-      B->arena = nullptr, B->arena_cap = 0;
-   }
-   // ---- two passes: decide and count (bam_scan_kernel), scans over the waves' totals, compact (bam_fill_kernel)
-   const size_t nn = (size_t)n, n1 = nn + 1, nt = (nn + 63) / 64, nt1 = nt + 1; // (tiles of 64 records: a wave's pass)
-   auto as_i64_i32 = [] __device__(int32_t v) { return (int64_t)v; };
-   size_t tmp_bytes = 0;
-   {
-      size_t b = 0;
-      (void)rocprim::exclusive_scan(nullptr, b, rocprim::make_transform_iterator((const int32_t *)nullptr, as_i64_i32), (int64_t *)nullptr, (int64_t)0, nt1, rocprim::plus<int64_t>(), s);
-      tmp_bytes = std::max(tmp_bytes, b);
-   }
-   size_t off = 0;
-   auto take = [&](size_t bytes) {
-      const size_t o = off;
-      off += up256(bytes ? bytes : 8);
-      return o;
-   };
-   const size_t o_status = take(nn), o_acc = take(n1), o_nb = take(n1 * 4), o_rid = take(nn * 8), o_ref = take(nn * 4), o_nh = take(nn * 4),
-                o_nm = take(nn * 4), o_rl = take(nn * 4), o_left = take(nn * 4), o_right = take(nn * 4), o_pp = take(nn * 4), o_sf = take(nn * 4),
-                o_fl = take(nn), o_ib = take(nn * 4 * 2 * sb::kBamInlineBlocks), o_tr = take(nt1 * 4), o_tb = take(nt1 * 4), o_rat = take(nt1 * 8), o_bat = take(nt1 * 8),
-                o_cnt = take(16 * 8), o_tmp = take(tmp_bytes);
-   SB_TRY(sb::dev_take(off, &w, &w_cap));
-   SB_TRY(hipMemsetAsync(w + o_cnt, 0, 16 * 8, s));
-   SB_TRY(hipMemsetAsync(w + o_tr + nt * 4, 0, 4, s)); // (the scans' entry beyond the last tile)
-   SB_TRY(hipMemsetAsync(w + o_tb + nt * 4, 0, 4, s));
-   sb::BamScanArgs a = {};
-   a.bytes = d_bytes, a.n_bytes = n_bytes, a.rec_off = d_rec_off, a.n = n, a.opts = *opts;
-   a.status = (uint8_t *)(w + o_status), a.n_blocks = (int32_t *)(w + o_nb), a.accepted = (uint8_t *)(w + o_acc);
-   a.read_id = (uint64_t *)(w + o_rid), a.ref = (int32_t *)(w + o_ref), a.nh = (int32_t *)(w + o_nh), a.nm = (int32_t *)(w + o_nm);
-   a.read_len = (int32_t *)(w + o_rl), a.left = (uint32_t *)(w + o_left), a.right = (uint32_t *)(w + o_right);
-   a.partner_pos = (uint32_t *)(w + o_pp), a.sam_flag = (uint32_t *)(w + o_sf), a.flags = (uint8_t *)(w + o_fl);
-   a.inline_blocks = (uint32_t *)(w + o_ib);
-   a.counts = (unsigned long long *)(w + o_cnt);
-   a.tile_reads = (int32_t *)(w + o_tr), a.tile_blocks = (int32_t *)(w + o_tb);
-   const int64_t cap = (int64_t)sb::ctx_cu_count(c) * 32, blocks = std::min<int64_t>((n + 255) / 256, cap);
-   // the staging buffer of a workgroup (one wave, 64 records): 1.1 x 64 average records, 8-64 KB
-   int stage_bytes = 8 * 1024;
-   while (stage_bytes < 64 * 1024 && (int64_t)stage_bytes < 70 * (n_bytes / n + 1)) stage_bytes += 2 * 1024;
-   // (what a workgroup may ask for, less the kernel's static words; a launch that is refused all the same is repeated
-   // without the buffer: the kernel then walks every record in global memory: slower, same results)
-   stage_bytes = std::max(0, std::min(stage_bytes, lds_max - 256));
-   const int resident = std::max(1, std::min(16, (int)(160 * 1024 / (stage_bytes + 256))));
-   const int64_t scan_blocks = std::min<int64_t>((n + 63) / 64, (int64_t)sb::ctx_cu_count(c) * resident * 4);
-   hipLaunchKernelGGL(sb::bam_scan_kernel, dim3((unsigned)scan_blocks), dim3(64), (size_t)stage_bytes, s, a, stage_bytes);
-   if (hipGetLastError() != hipSuccess && stage_bytes > 0) {
-      stage_bytes = 0;
-      hipLaunchKernelGGL(sb::bam_scan_kernel, dim3((unsigned)scan_blocks), dim3(64), 0, s, a, 0);
-   }
-   SB_TRY(hipGetLastError());
-   size_t tb = tmp_bytes;
-   SB_TRY(rocprim::exclusive_scan(w + o_tmp, tb, rocprim::make_transform_iterator((const int32_t *)a.tile_reads, as_i64_i32), (int64_t *)(w + o_rat), (int64_t)0, nt1, rocprim::plus<int64_t>(), s));
-   tb = tmp_bytes;
-   SB_TRY(rocprim::exclusive_scan(w + o_tmp, tb, rocprim::make_transform_iterator((const int32_t *)a.tile_blocks, as_i64_i32), (int64_t *)(w + o_bat), (int64_t)0, nt1, rocprim::plus<int64_t>(), s));
-   // the totals: the output arena's size depends on them
-   int64_t totals[2] = {0, 0};
-   unsigned long long counts[16];
-   SB_TRY(hipMemcpyAsync(&totals[0], w + o_rat + nt * 8, 8, hipMemcpyDeviceToHost, s));
-   SB_TRY(hipMemcpyAsync(&totals[1], w + o_bat + nt * 8, 8, hipMemcpyDeviceToHost, s));
-   SB_TRY(hipMemcpyAsync(counts, w + o_cnt, sizeof(counts), hipMemcpyDeviceToHost, s));
-   SB_TRY(hipStreamSynchronize(s));
-   B->n_reads = totals[0], B->n_blocks = totals[1];
-   for (int k = 0; k <= SBGPU_BAM_TRUNCATED; ++k) B->by_status[k] = (int64_t)counts[k];
-   B->any_paired = counts[11] ? 1 : 0;
-   SB_TRY(sb::dev_take(lay_out(B, nullptr), &B->arena, &B->arena_cap));
-   lay_out(B, B->arena);
-   SB_TRY(hipMemcpyAsync(B->status, w + o_status, nn, hipMemcpyDeviceToDevice, s));
-   sb::BamFillArgs f = {};
-   f.bytes = d_bytes, f.rec_off = d_rec_off, f.n = n;
-   f.accepted = a.accepted, f.tile_read_at = (const int64_t *)(w + o_rat), f.tile_block_at = (const int64_t *)(w + o_bat);
-   f.read_id = a.read_id, f.ref = a.ref, f.nh = a.nh, f.nm = a.nm, f.read_len = a.read_len;
-   f.left = a.left, f.right = a.right, f.partner_pos = a.partner_pos, f.sam_flag = a.sam_flag, f.flags = a.flags;
-   f.n_blocks = a.n_blocks, f.inline_blocks = a.inline_blocks;
-   f.o_record = B->record, f.o_read_id = B->read_id, f.o_ref = B->ref, f.o_nh = B->nh, f.o_nm = B->nm, f.o_read_len = B->read_len;
-   f.o_left = B->left, f.o_right = B->right, f.o_partner_pos = B->partner_pos, f.o_sam_flag = B->sam_flag, f.o_flags = B->flags;
-   f.o_block_off = B->block_off, f.o_block_left = B->block_left, f.o_block_right = B->block_right;
-   hipLaunchKernelGGL(sb::bam_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, s, f);
-   SB_TRY(hipGetLastError());
-   SB_TRY(hipStreamSynchronize(s)); // (the scratch goes back to the pool; the handle's arrays are complete when the call returns)
-   sb::dev_give(w, w_cap);
-#undef SB_TRY
-   *out = B;
+   BamDecodeCall call = {c, d_bytes, n_bytes, d_rec_off, n, opts, stream ? (hipStream_t)stream : sb::ctx_stream(c), B.get()};
+   SB_FRONT_RC(call.run(sb::front_hooks_from_env()));
+   *out = B.release();
    return SBGPU_OK;
 }
 

@@ -19,7 +19,7 @@ using sb::api_fail_hip;
 
 namespace {
 
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+using sb::up256;
 
 // What depends on the counts alone, shared by all replicates of a call: in the context's bootstrap scratch
 struct BootPrep {

@@ -25,6 +25,7 @@
 #include "../../include/sbgpu.h"
 #include "api_internal.h"
 #include "fraglen_device.h"
+#include "stage_host.h"
 
 using sb::api_fail;
 using sb::api_fail_hip;
@@ -43,23 +44,11 @@ using sb::api_fail_hip;
 
 namespace {
 
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// ---- layouts: where the parts of an arena lie (every part begins at a multiple of 256 bytes)
+// ---- layouts: where the parts of an arena lie (sb::Arena: every part begins at a multiple of 256 bytes)
 
 struct Slab {
    const void *src = nullptr; // host array it is filled from
    size_t bytes = 0, off = 0; // bytes == 0: nothing to copy (it still has a place)
-};
-struct ArenaSize {
-   size_t total = 0;
-   size_t add(size_t bytes)
-   {
-      const size_t off = total;
-      total += up256(bytes);
-      return off;
-   }
-   void place(Slab &s) { s.off = add(s.bytes ? s.bytes : 8); }
 };
 struct AnnotationCounts {
    int64_t nl, n_iso, n_exon, n_seg;
@@ -80,9 +69,9 @@ struct AnnotationLayout {
       exon_left = {an->exon_left, on * (size_t)n.n_exon * 4, 0}, exon_right = {an->exon_right, on * (size_t)n.n_exon * 4, 0};
       seg_left = {an->seg_left, on * (size_t)n.n_seg * 4, 0}, seg_right = {an->seg_right, on * (size_t)n.n_seg * 4, 0};
    }
-   void place(ArenaSize &size)
+   void place(sb::Arena &size)
    {
-      for (Slab *s : {&iso_off, &exon_off, &seg_off, &exon_left, &exon_right, &seg_left, &seg_right}) size.place(*s);
+      for (Slab *s : {&iso_off, &exon_off, &seg_off, &exon_left, &exon_right, &seg_left, &seg_right}) s->off = size.take_nonempty(s->bytes);
    }
    sbgpu_annotation_t on_device(const sbgpu_annotation_t &an, const char *base) const
    {
@@ -104,9 +93,9 @@ struct HitsLayout {
       feat_left = {h->feat_left, on * (size_t)n_feat * 4, 0}, feat_right = {h->feat_right, on * (size_t)n_feat * 4, 0};
       feat_code = {h->feat_code, on * (size_t)n_feat, 0}, mass = {hit_mass, on * nh * 4, 0};
    }
-   void place(ArenaSize &size)
+   void place(sb::Arena &size)
    {
-      for (Slab *s : {&feat_off, &hit_locus, &feat_left, &feat_right, &feat_code, &mass}) size.place(*s);
+      for (Slab *s : {&feat_off, &hit_locus, &feat_left, &feat_right, &feat_code, &mass}) s->off = size.take_nonempty(s->bytes);
    }
    sbgpu_hits_t on_device(const sbgpu_hits_t &h, const char *base) const
    {
@@ -125,12 +114,12 @@ struct InputArena {
    char *base = nullptr;
    InputArena(const AnnotationLayout &a, const HitsLayout &h, size_t nh1, int32_t cw, int32_t kw) : annot(a), hits(h)
    {
-      ArenaSize size;
+      sb::Arena size;
       annot.place(size), hits.place(size);
-      o_compat = size.add(nh1 * 4 * (size_t)cw), o_key = size.add(nh1 * 4 * (size_t)kw);
-      o_hit_bin = size.add(8); // (hit -> bin has an arena of its own where it is made at all)
-      o_span = size.add(nh1 * 8), o_fhash = size.add(nh1 * 4);
-      total = size.total;
+      o_compat = size.take(nh1 * 4 * (size_t)cw), o_key = size.take(nh1 * 4 * (size_t)kw);
+      o_hit_bin = size.take(8); // (hit -> bin has an arena of its own where it is made at all)
+      o_span = size.take(nh1 * 8), o_fhash = size.take(nh1 * 4);
+      total = size.size;
    }
    // one copy per array, in this order
    std::array<const Slab *, 13> uploads() const
@@ -154,16 +143,16 @@ struct WorkArena {
    WorkArena(int64_t n_pairs, int64_t n_pair_segs, int64_t n_bins, int64_t n_elem, int64_t n_iso, int64_t nl, bool epilogue)
    {
       const size_t np1 = (size_t)std::max<int64_t>(n_pairs, 1), ni1 = (size_t)(n_iso + 1), nl1 = (size_t)(nl + 1);
-      ArenaSize size;
-      o_pair_off = size.add((np1 + 1) * 8), o_pair_idx = size.add(np1 * 8), o_pair_seg = size.add((size_t)(n_pair_segs + 1) * 4);
-      o_pair_mask = size.add(np1 * 4), o_pair_len = size.add(np1 * 4);
-      o_count = size.add((size_t)std::max<int64_t>(n_bins, 1) * 4), o_F = size.add((size_t)std::max<int64_t>(n_elem, 1) * 8);
-      o_theta = size.add(ni1 * 8), o_status = size.add(nl1 * 4), o_iters = size.add(nl1 * 4);
+      sb::Arena size;
+      o_pair_off = size.take((np1 + 1) * 8), o_pair_idx = size.take(np1 * 8), o_pair_seg = size.take((size_t)(n_pair_segs + 1) * 4);
+      o_pair_mask = size.take(np1 * 4), o_pair_len = size.take(np1 * 4);
+      o_count = size.take((size_t)std::max<int64_t>(n_bins, 1) * 4), o_F = size.take((size_t)std::max<int64_t>(n_elem, 1) * 8);
+      o_theta = size.take(ni1 * 8), o_status = size.take(nl1 * 4), o_iters = size.take(nl1 * 4);
       if (epilogue) { // the epilogue's arrays (sbgpu_quantify_resident)
-         o_fpkm = size.add(ni1 * 8), o_frac = size.add(ni1 * 8), o_tpm = size.add(ni1 * 8);
-         o_keep = size.add(ni1 * 4), o_iso_len = size.add(ni1 * 4), o_sum = size.add(8);
+         o_fpkm = size.take(ni1 * 8), o_frac = size.take(ni1 * 8), o_tpm = size.take(ni1 * 8);
+         o_keep = size.take(ni1 * 4), o_iso_len = size.take(ni1 * 4), o_sum = size.take(8);
       }
-      total = size.total;
+      total = size.size;
    }
    int64_t *pair_off() const { return (int64_t *)(base + o_pair_off); }
    int64_t *pair_idx() const { return (int64_t *)(base + o_pair_idx); }
@@ -987,13 +976,13 @@ int sbgpu_annotation_pin(sbgpu_ctx_t *c, const sbgpu_annotation_t *an)
    AnnotationLayout annot(an, n, false);
    Slab iso_seg_off = {r->iso.seg_off.data(), r->iso.seg_off.size() * 8, 0}, iso_seg_idx = {r->iso.seg_idx.data(), r->iso.seg_idx.size() * 4, 0},
         iso_locus = {r->iso.locus.data(), r->iso.locus.size() * 4, 0}, iso_len = {r->iso.len.data(), r->iso.len.size() * 4, 0};
-   ArenaSize size;
+   sb::Arena size;
    annot.place(size);
-   for (Slab *p : {&iso_seg_off, &iso_seg_idx, &iso_locus, &iso_len}) size.place(*p);
-   const size_t o_segbasis = size.total;
-   size.total += sb::seg_basis_bytes(n.nl, n.n_iso);
+   for (Slab *p : {&iso_seg_off, &iso_seg_idx, &iso_locus, &iso_len}) p->off = size.take_nonempty(p->bytes);
+   const size_t o_segbasis = size.size;
+   size.size += sb::seg_basis_bytes(n.nl, n.n_iso);
    hipError_t e = hipSetDevice(sb::ctx_device(c));
-   if (e == hipSuccess) e = sb::dev_take(size.total, &r->arena, &r->capacity);
+   if (e == hipSuccess) e = sb::dev_take(size.size, &r->arena, &r->capacity);
    for (const Slab *p : {&annot.iso_off, &annot.exon_off, &annot.seg_off, &annot.exon_left, &annot.exon_right, &annot.seg_left, &annot.seg_right,
                          &iso_seg_off, &iso_seg_idx, &iso_locus, &iso_len})
       if (e == hipSuccess && p->bytes) e = hipMemcpy(r->arena + p->off, p->src, p->bytes, hipMemcpyHostToDevice);

@@ -14,21 +14,21 @@
 #include "api_internal.h"
 #include "bins_device.h"
 #include "exonbin_device.h"
+#include "stage_host.h"
 
 using sb::api_fail;
 
 namespace sb {
 // sbgpu_exonbin_device that also leaves every hit's span and sequence hash (exonbin_device.h) when asked to
-static size_t up256b(size_t b) { return (b + 255) & ~(size_t)255; }
 size_t seg_basis_bytes(int64_t n_loci, int64_t n_iso)
 {
    const size_t ni1 = (size_t)(n_iso > 0 ? n_iso : 1);
-   return 4 * up256b(ni1 * 8) + 2 * up256b((size_t)n_loci * 8) + up256b((size_t)n_loci * 4);
+   return 4 * sb::up256(ni1 * 8) + 2 * sb::up256((size_t)n_loci * 8) + sb::up256((size_t)n_loci * 4);
 }
 int make_seg_basis(sbgpu_ctx_t *c, const sbgpu_annotation_t *an, int64_t n_iso, char *dm, void *stream, DeviceSegBasis *out)
 {
    const size_t ni1 = (size_t)(n_iso > 0 ? n_iso : 1);
-   const size_t isz = up256b(ni1 * 8), lsz = up256b((size_t)an->n_loci * 8);
+   const size_t isz = sb::up256(ni1 * 8), lsz = sb::up256((size_t)an->n_loci * 8);
    const size_t o_mem = 0, o_sta = isz, o_memh = 2 * isz, o_stah = 3 * isz, o_adj = 4 * isz, o_adjh = o_adj + lsz, o_ok = o_adjh + lsz;
    sb::ExonBinArgs a = {};
    a.iso_off = an->iso_off;

@@ -38,13 +38,11 @@
 #include <vector>
 
 #include "../../include/sbgpu.h"
-#include "api_internal.h"
+#include "front_common.h"
 
 using sb::api_fail;
 
 namespace {
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // a device array that grows (geometric; the old block goes back to the pool)
 struct Grow {
    char *p = nullptr;
@@ -52,10 +50,9 @@ struct Grow {
    hipError_t reserve(size_t want, hipStream_t s)
    {
       if (want <= cap) return hipSuccess;
-      size_t ncap = std::max(want, cap + cap / 2);
       char *np = nullptr;
       size_t got = 0;
-      hipError_t e = sb::dev_take(ncap, &np, &got);
+      hipError_t e = sb::dev_take(sb::grow_capacity(want, cap), &np, &got);
       if (e != hipSuccess) return e;
       if (used) e = hipMemcpyAsync(np, p, used, hipMemcpyDeviceToDevice, s);
       if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -142,47 +139,35 @@ struct sbgpu_front_stream {
 
 namespace {
 
-#define SB_TRY(expr)                                                                                                 \
-   do {                                                                                                              \
-      hipError_t e_ = (expr);                                                                                        \
-      if (e_ != hipSuccess)                                                                                          \
-         return api_fail(e_ == hipErrorOutOfMemory ? SBGPU_ENOMEM : SBGPU_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-   } while (0)
-#define SB_RC(expr)                    \
-   do {                                \
-      const int rc_ = (expr);          \
-      if (rc_ != SBGPU_OK) return rc_; \
-   } while (0)
+double now_seconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// the chunk in buffer `b` (uploaded), with the carry in front of it: decode .. unique hits of the clusters it completes
-int compute_pending(sbgpu_front_stream *F, bool last)
-{
-   sbgpu_ctx_t *c = F->ctx;
-   hipStream_t s = sb::ctx_stream(c);
-   // every stage below synchronises the stream it ran on before it returns, so the arenas its handles give back are idle: they
-   // must not wait for the DEVICE -- the next chunk's upload is running on it
-   sb::DevGiveStreamSynced no_device_wait;
+// The chunk in buffer F->cur (uploaded), with the carry in front of it: decode .. unique hits of the clusters it completes.
+// What the window arithmetic decides is front_schedule.h's (stream_clusters_done, stream_carry); the steps below issue it.
+struct PendingCall {
+   sbgpu_front_stream *const F;
+   const bool last;
+   sbgpu_ctx_t *const c = F->ctx;
+   const hipStream_t s = sb::ctx_stream(c);
    const int b = F->cur;
-   auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-   const double t_in = now();
-   SB_TRY(hipEventSynchronize(F->ev_up[b])); // the chunk has arrived
-   const double t_arrived = now();
-   F->t_wait += t_arrived - t_in;
-   struct Clock {
-      double &acc, t0;
-      ~Clock() { acc += std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0; }
-   } clock = {F->t_compute, t_arrived};
    // the window: [carry | chunk], its record offsets
    const int64_t n_carry = F->carry_n;
-   int64_t n_new = F->pending ? F->pend_records : 0;
-   int64_t n_rec = n_carry + n_new, w_bytes = F->carry_bytes + (F->pending ? F->pend_bytes : 0); // w_bytes: the window's whole records
-   int64_t w_end = w_bytes;                                                                      // ... and all its bytes
-   char *w0 = F->buf[b] + F->room - F->carry_bytes; // (the carry was copied to end where the chunk begins)
-   F->n_chunks += F->pending && F->pend_bytes ? 1 : 0; // (an empty push is no chunk)
-   F->redecoded += n_carry;
-   Grow &W = F->d_win[F->win], &P = F->d_win[F->win ^ 1];
-   if (F->mode == 2) {
-      // ---- a chunk of BGZF members: inflate it where an inflated chunk would have landed, then find the window's records
+   int64_t n_new = F->pending ? F->pend_records : 0, n_rec = n_carry + n_new;
+   int64_t w_bytes = F->carry_bytes + (F->pending ? F->pend_bytes : 0), w_end = w_bytes; // the window's whole records; all its bytes
+   char *w0 = F->buf[b] + F->room - F->carry_bytes;                                      // (the carry was copied to end where the chunk begins)
+   Grow &W = F->d_win[F->win], &P = F->d_win[F->win ^ 1];                                // this window's offsets, the one before's
+   bool finished = false; // a step has ended the call: nothing is left to compute
+   // the window's reads, which cluster each is offered to, the clusters they complete
+   sb::BamReadsHandle R;
+   sbgpu_reads_t reads = {};
+   int64_t n_reads = 0, nc = 0;
+   std::vector<int64_t> roff;
+   sb::DevBlock d_cluster{s};
+   sb::StreamDone done = {0, 0};
+   int64_t carry_rec = 0, c0 = 0; // where the next window's carry begins: window record index; its first byte in the window
+
+   // ---- a chunk of BGZF members: inflate it where an inflated chunk would have landed, then find the window's records
+   int inflate_and_index()
+   {
       const int64_t nm = F->pending ? F->pend_blocks : 0;
       int64_t first = 0;
       if (nm) {
@@ -190,12 +175,12 @@ int compute_pending(sbgpu_front_stream *F, bool last)
          uint8_t *d_status = (uint8_t *)(d_out + (nm + 1));
          const int64_t blk0 = F->h_blk[b][0], out0 = F->h_out[b][0];
          int64_t failed = 0;
-         SB_RC(sbgpu_bgzf_inflate_device(c, (const uint8_t *)((uintptr_t)F->d_comp[b].p - (uintptr_t)blk0), F->h_blk[b][(size_t)nm], d_blk, d_out, nm,
-                                         (uint8_t *)((uintptr_t)(F->buf[b] + F->room) - (uintptr_t)out0), s, d_status, &failed));
+         SB_FRONT_RC(sbgpu_bgzf_inflate_device(c, (const uint8_t *)((uintptr_t)F->d_comp[b].p - (uintptr_t)blk0), F->h_blk[b][(size_t)nm], d_blk, d_out, nm,
+                                               (uint8_t *)((uintptr_t)(F->buf[b] + F->room) - (uintptr_t)out0), s, d_status, &failed));
          if (failed) {
             std::vector<uint8_t> st((size_t)nm);
-            SB_TRY(hipMemcpyAsync(st.data(), d_status, (size_t)nm, hipMemcpyDeviceToHost, s));
-            SB_TRY(hipStreamSynchronize(s));
+            SB_FRONT_TRY(hipMemcpyAsync(st.data(), d_status, (size_t)nm, hipMemcpyDeviceToHost, s));
+            SB_FRONT_TRY(hipStreamSynchronize(s));
             size_t k = 0;
             while (k + 1 < st.size() && !st[k]) ++k;
             return api_fail(SBGPU_EINVAL, "sbgpu_front_stream_push_bgzf: the BGZF member at byte " + std::to_string(F->h_blk[b][k]) +
@@ -221,151 +206,191 @@ int compute_pending(sbgpu_front_stream *F, bool last)
       n_new = n_rec - n_carry;
       if (last && w_bytes < w_end) return api_fail(SBGPU_ESHAPE, "sbgpu_front_stream_end: the stream ends inside a record");
       if (n_rec == 0 && w_end > 0) { // no record is whole yet: the window's bytes wait for the next chunk's
-         if (w_end > F->chunk_cap) return api_fail(SBGPU_ESHAPE, "sbgpu_front_stream_push_bgzf: one record exceeds a chunk's capacity: begin the stream with larger chunks");
-         SB_TRY(hipMemcpyAsync(F->buf[b ^ 1] + F->room - w_end, w0, (size_t)w_end, hipMemcpyDeviceToDevice, s));
-         SB_TRY(hipStreamSynchronize(s));
-         F->carry_n = 0, F->carry_rec = 0, F->carry_c0 = 0, F->carry_bytes = w_end;
-         F->carry_max = std::max(F->carry_max, w_end);
-         F->pending = false;
-         return SBGPU_OK;
+         const sb::StreamCarry carry = sb::stream_carry(w_end, 0, F->chunk_cap);
+         if (!carry.fits) return api_fail(SBGPU_ESHAPE, "sbgpu_front_stream_push_bgzf: one record exceeds a chunk's capacity: begin the stream with larger chunks");
+         F->carry_n = 0, F->carry_rec = 0, F->carry_c0 = 0;
+         SB_FRONT_RC(copy_carry(carry.bytes, 0));
+         finished = true;
       }
-   }
-   if (n_rec == 0) {
-      if (last) { // nothing more will come: the clusters not yet finished are, without hits
-         for (int64_t k = F->k0; k < F->n_clusters; ++k) F->locus_hit_off[(size_t)k + 1] = F->n_hits;
-         F->k0 = F->n_clusters;
-      }
-      F->pending = false;
       return SBGPU_OK;
    }
-   // (made on the device from the window before and the chunk's own offsets: 8 bytes per record never pass through host loops)
-   if (F->mode != 2) { // (a window of BGZF members was indexed above)
+
+   // the carry's bytes, in front of where the next chunk lands in the OTHER buffer
+   int copy_carry(int64_t bytes, int64_t from)
+   {
+      F->carry_bytes = bytes;
+      F->carry_max = std::max(F->carry_max, bytes);
+      if (bytes) {
+         SB_FRONT_TRY(hipMemcpyAsync(F->buf[b ^ 1] + F->room - bytes, w0 + from, (size_t)bytes, hipMemcpyDeviceToDevice, s));
+         SB_FRONT_TRY(hipStreamSynchronize(s));
+      }
+      return SBGPU_OK;
+   }
+
+   // the window's record offsets, made on the device from the window before and the chunk's own: 8 bytes per record never pass
+   // through host loops (a window of BGZF members was indexed instead)
+   int window_offsets()
+   {
       W.used = 0;
-      SB_TRY(W.reserve((size_t)(n_rec + 1) * 8, s));
-      hipLaunchKernelGGL(window_off_kernel, dim3((unsigned)((n_rec + 1 + 255) / 256)), dim3(256), 0, s, (int64_t *)W.p,
-                         (const int64_t *)P.p + F->carry_rec, n_carry, F->carry_c0, (const int64_t *)F->d_pend[b].p, n_new, F->carry_bytes);
-      SB_TRY(hipGetLastError());
+      SB_FRONT_TRY(W.reserve((size_t)(n_rec + 1) * 8, s));
+      hipLaunchKernelGGL(window_off_kernel, dim3((unsigned)((n_rec + 1 + 255) / 256)), dim3(256), 0, s, (int64_t *)W.p, (const int64_t *)P.p + F->carry_rec, n_carry,
+                         F->carry_c0, (const int64_t *)F->d_pend[b].p, n_new, F->carry_bytes);
+      SB_FRONT_TRY(hipGetLastError());
+      return SBGPU_OK;
    }
-   sbgpu_bamreads_t *R = nullptr;
-   SB_RC(sbgpu_bam_decode_device(c, (const uint8_t *)w0, w_bytes, (const int64_t *)W.p, n_rec, &F->opts, s, &R));
-   struct ReadsGuard {
-      sbgpu_bamreads_t *r;
-      ~ReadsGuard() { sbgpu_bamreads_destroy(r); }
-   } rg = {R};
-   int64_t binfo[16];
-   SB_RC(sbgpu_bamreads_info(R, binfo));
-   sbgpu_reads_t reads;
-   const int32_t *d_ref = nullptr;
-   const uint32_t *d_left = nullptr, *d_right = nullptr;
-   SB_RC(sbgpu_bamreads_reads(R, &reads, &d_ref, &d_left, &d_right));
-   const int64_t n_reads = reads.n_reads;
-   // which of the remaining clusters every read is offered to
-   const int64_t nc = F->n_clusters - F->k0;
-   std::vector<int64_t> roff((size_t)nc + 1, 0);
-   char *d_cluster = nullptr;
-   size_t d_cluster_cap = 0;
-   SB_TRY(sb::dev_take((size_t)std::max<int64_t>(n_reads, 1) * 4, &d_cluster, &d_cluster_cap));
-   struct Give {
-      char *p;
-      size_t cap;
-      ~Give() { sb::dev_give(p, cap); }
-   } gc = {d_cluster, d_cluster_cap};
-   sbgpu_clusters_t cl = {nc, F->c_ref.data() + F->k0, F->c_left.data() + F->k0, F->c_right.data() + F->k0, F->c_strand.data() + F->k0};
-   if (nc > 0)
-      SB_RC(sbgpu_assign_reads_device(c, &cl, n_reads, d_ref, d_left, d_right, (uint8_t *)reads.flags, (int32_t *)d_cluster, roff.data(), s));
-   // complete: a read behind the cluster's end has been seen (or nothing more will come)
-   int64_t n_done = 0;
-   if (last) n_done = nc;
-   else
-      while (n_done < nc && roff[(size_t)n_done + 1] < n_reads) ++n_done;
-   const int64_t reads_done = nc > 0 ? roff[(size_t)n_done] : n_reads;
+
+   int decode()
+   {
+      sbgpu_bamreads_t *r = nullptr;
+      SB_FRONT_RC(sbgpu_bam_decode_device(c, (const uint8_t *)w0, w_bytes, (const int64_t *)W.p, n_rec, &F->opts, s, &r));
+      R.reset(r);
+      return SBGPU_OK;
+   }
+
+   // which of the remaining clusters every read is offered to; which of them are complete
+   int assign()
+   {
+      const int32_t *d_ref = nullptr;
+      const uint32_t *d_left = nullptr, *d_right = nullptr;
+      SB_FRONT_RC(sbgpu_bamreads_reads(R.get(), &reads, &d_ref, &d_left, &d_right));
+      n_reads = reads.n_reads;
+      nc = F->n_clusters - F->k0;
+      roff.assign((size_t)nc + 1, 0);
+      SB_FRONT_TRY(d_cluster.take((size_t)std::max<int64_t>(n_reads, 1) * 4));
+      sbgpu_clusters_t cl = {nc, F->c_ref.data() + F->k0, F->c_left.data() + F->k0, F->c_right.data() + F->k0, F->c_strand.data() + F->k0};
+      if (nc > 0)
+         SB_FRONT_RC(sbgpu_assign_reads_device(c, &cl, n_reads, d_ref, d_left, d_right, (uint8_t *)reads.flags, d_cluster.at<int32_t>(0), roff.data(), s));
+      done = sb::stream_clusters_done(roff.data(), nc, n_reads, last);
+      return SBGPU_OK;
+   }
+
    // ---- the carry for the next window: from the record of the first read that was not consumed
-   int64_t carry_rec = n_rec, c0 = w_bytes; // (window record index; its first byte in the window)
-   if (!last && reads_done < n_reads) {
-      const int64_t *d_record = sb::bamreads_device_record(R);
-      SB_TRY(hipMemcpyAsync(&carry_rec, d_record + reads_done, 8, hipMemcpyDeviceToHost, s));
-      SB_TRY(hipStreamSynchronize(s));
-      SB_TRY(hipMemcpyAsync(&c0, (const int64_t *)W.p + carry_rec, 8, hipMemcpyDeviceToHost, s));
-      SB_TRY(hipStreamSynchronize(s));
+   int find_carry()
+   {
+      carry_rec = n_rec, c0 = w_bytes;
+      if (!last && done.reads_done < n_reads) {
+         const int64_t *d_record = sb::bamreads_device_record(R.get());
+         SB_FRONT_TRY(hipMemcpyAsync(&carry_rec, d_record + done.reads_done, 8, hipMemcpyDeviceToHost, s));
+         SB_FRONT_TRY(hipStreamSynchronize(s));
+         SB_FRONT_TRY(hipMemcpyAsync(&c0, (const int64_t *)W.p + carry_rec, 8, hipMemcpyDeviceToHost, s));
+         SB_FRONT_TRY(hipStreamSynchronize(s));
+      }
+      return SBGPU_OK;
    }
-   if (n_done > 0 && reads_done > 0) {
+
+   // the complete clusters' reads -> pairs -> unique hits -> the store
+   int pair_and_collapse()
+   {
       sbgpu_reads_t part = reads;
-      part.n_reads = reads_done;
-      sbgpu_matepairs_t *M = nullptr;
-      SB_RC(sbgpu_pair_mates_device(c, n_done, &part, roff.data(), s, &M));
-      struct MG {
-         sbgpu_matepairs_t *m;
-         ~MG() { sbgpu_matepairs_destroy(m); }
-      } mg = {M};
+      part.n_reads = done.reads_done;
+      sbgpu_matepairs_t *m = nullptr;
+      SB_FRONT_RC(sbgpu_pair_mates_device(c, done.n_done, &part, roff.data(), s, &m));
+      sb::MatePairsHandle M(m);
       sbgpu_pairs_t pairs;
       const int64_t *poff = nullptr;
-      SB_RC(sbgpu_matepairs_pairs(M, &pairs, &poff));
+      SB_FRONT_RC(sbgpu_matepairs_pairs(M.get(), &pairs, &poff));
       F->n_pairs += pairs.n_pairs;
-      sbgpu_uniq_dev_t *U = nullptr;
-      SB_RC(sbgpu_collapse_pairs_device(c, n_done, &pairs, poff, s, &U));
-      struct UG {
-         sbgpu_uniq_dev_t *u;
-         ~UG() { sbgpu_uniq_dev_destroy(u); }
-      } ug = {U};
+      sbgpu_uniq_dev_t *u = nullptr;
+      SB_FRONT_RC(sbgpu_collapse_pairs_device(c, done.n_done, &pairs, poff, s, &u));
+      sb::UniqDevHandle U(u);
+      SB_FRONT_RC(append_to_store(U.get()));
+      SB_FRONT_TRY(hipStreamSynchronize(s)); // (the handles go away with this scope)
+      return SBGPU_OK;
+   }
+
+   // the unique hits behind the store's: the cluster numbers and the feature offsets shifted to the stream's
+   int append_to_store(const sbgpu_uniq_dev_t *U)
+   {
       int64_t ui[8];
-      SB_RC(sbgpu_uniq_dev_info(U, ui));
+      SB_FRONT_RC(sbgpu_uniq_dev_info(U, ui));
       sbgpu_hits_t h;
       const float *d_mass = nullptr;
       const int64_t *hoff = nullptr;
-      SB_RC(sbgpu_uniq_dev_hits(U, &h, &d_mass, &hoff));
+      SB_FRONT_RC(sbgpu_uniq_dev_hits(U, &h, &d_mass, &hoff));
       const int64_t nh = ui[0], nf = ui[1];
       F->n_filtered += ui[2], F->mapped_reads += ui[4];
-      // append to the store: the cluster numbers and the feature offsets shifted to the stream's
-      SB_TRY(F->s_locus.reserve((size_t)(F->n_hits + nh) * 4, s));
-      SB_TRY(F->s_foff.reserve((size_t)(F->n_hits + nh + 1) * 8, s));
-      SB_TRY(F->s_mass.reserve((size_t)(F->n_hits + nh) * 4, s));
-      SB_TRY(F->s_code.reserve((size_t)(F->n_feat + nf), s));
-      SB_TRY(F->s_left.reserve((size_t)(F->n_feat + nf) * 4, s));
-      SB_TRY(F->s_right.reserve((size_t)(F->n_feat + nf) * 4, s));
-      if (nh) {
-         int32_t *dl = (int32_t *)F->s_locus.p + F->n_hits;
-         int64_t *df = (int64_t *)F->s_foff.p + F->n_hits;
-         SB_TRY(hipMemcpyAsync(dl, h.hit_locus, (size_t)nh * 4, hipMemcpyDeviceToDevice, s));
-         SB_TRY(hipMemcpyAsync(df, h.feat_off, (size_t)(nh + 1) * 8, hipMemcpyDeviceToDevice, s));
-         SB_TRY(hipMemcpyAsync((float *)F->s_mass.p + F->n_hits, d_mass, (size_t)nh * 4, hipMemcpyDeviceToDevice, s));
-         if (nf) {
-            SB_TRY(hipMemcpyAsync(F->s_code.p + F->n_feat, h.feat_code, (size_t)nf, hipMemcpyDeviceToDevice, s));
-            SB_TRY(hipMemcpyAsync((uint32_t *)F->s_left.p + F->n_feat, h.feat_left, (size_t)nf * 4, hipMemcpyDeviceToDevice, s));
-            SB_TRY(hipMemcpyAsync((uint32_t *)F->s_right.p + F->n_feat, h.feat_right, (size_t)nf * 4, hipMemcpyDeviceToDevice, s));
-         }
-         if (F->k0) hipLaunchKernelGGL(add_i32_kernel, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, s, dl, nh, (int32_t)F->k0);
-         if (F->n_feat) hipLaunchKernelGGL(add_i64_kernel, dim3((unsigned)((nh + 1 + 255) / 256)), dim3(256), 0, s, df, nh + 1, F->n_feat);
-         SB_TRY(hipGetLastError());
+      // one row per array of the store: what is there, what joins it (`tail`: the offsets' entry beyond the last hit)
+      struct Column {
+         Grow &g;
+         const void *src;
+         size_t elem;
+         int64_t have, add, tail;
+      };
+      const Column columns[6] = {{F->s_locus, h.hit_locus, 4, F->n_hits, nh, 0}, {F->s_foff, h.feat_off, 8, F->n_hits, nh, 1}, {F->s_mass, d_mass, 4, F->n_hits, nh, 0},
+                                 {F->s_code, h.feat_code, 1, F->n_feat, nf, 0},  {F->s_left, h.feat_left, 4, F->n_feat, nf, 0}, {F->s_right, h.feat_right, 4, F->n_feat, nf, 0}};
+      for (const Column &col : columns) SB_FRONT_TRY(col.g.reserve((size_t)(col.have + col.add + col.tail) * col.elem, s));
+      for (const Column &col : columns) {
+         if (col.add) SB_FRONT_TRY(hipMemcpyAsync(col.g.p + (size_t)col.have * col.elem, col.src, (size_t)(col.add + col.tail) * col.elem, hipMemcpyDeviceToDevice, s));
+         col.g.used = (size_t)(col.have + col.add + col.tail) * col.elem;
       }
-      for (int64_t k = 0; k < n_done; ++k) F->locus_hit_off[(size_t)(F->k0 + k + 1)] = F->n_hits + hoff[(size_t)k + 1];
+      if (nh) {
+         if (F->k0) hipLaunchKernelGGL(add_i32_kernel, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, s, (int32_t *)F->s_locus.p + F->n_hits, nh, (int32_t)F->k0);
+         if (F->n_feat) hipLaunchKernelGGL(add_i64_kernel, dim3((unsigned)((nh + 1 + 255) / 256)), dim3(256), 0, s, (int64_t *)F->s_foff.p + F->n_hits, nh + 1, F->n_feat);
+         SB_FRONT_TRY(hipGetLastError());
+      }
+      for (int64_t k = 0; k < done.n_done; ++k) F->locus_hit_off[(size_t)(F->k0 + k + 1)] = F->n_hits + hoff[(size_t)k + 1];
       F->n_hits += nh, F->n_feat += nf;
-      F->s_locus.used = (size_t)F->n_hits * 4, F->s_foff.used = (size_t)(F->n_hits + 1) * 8, F->s_mass.used = (size_t)F->n_hits * 4;
-      F->s_code.used = (size_t)F->n_feat, F->s_left.used = F->s_right.used = (size_t)F->n_feat * 4;
-      SB_TRY(hipStreamSynchronize(s)); // (the handles go away with this scope)
-   } else {
-      for (int64_t k = 0; k < n_done; ++k) F->locus_hit_off[(size_t)(F->k0 + k + 1)] = F->n_hits;
+      return SBGPU_OK;
    }
-   // (every accepted record counts once: in the window that consumes it -- the last consumes all, reads behind the last cluster too)
-   F->n_records += n_new, F->n_decoded += n_rec, F->n_accepted += last ? n_reads : reads_done;
-   F->k0 += n_done;
-   // ---- carry: the window's records from carry_rec on, in front of where the next chunk lands in the OTHER buffer
-   const int64_t cb = w_end - c0; // (with it the bytes of a record the window cut: push_bgzf)
-   if (cb > F->chunk_cap)
-      return api_fail(SBGPU_ESHAPE, "sbgpu_front_stream_push: the records of one cluster exceed a chunk's capacity (" + std::to_string(cb) + " bytes): begin the stream with larger chunks");
-   F->carry_n = n_rec - carry_rec, F->carry_rec = carry_rec, F->carry_c0 = c0;
-   F->win ^= 1; // (this window's offsets are the next one's "window before")
-   F->carry_bytes = cb;
-   F->carry_max = std::max(F->carry_max, cb);
-   if (cb) {
-      SB_TRY(hipMemcpyAsync(F->buf[b ^ 1] + F->room - cb, w0 + c0, (size_t)cb, hipMemcpyDeviceToDevice, s));
-      SB_TRY(hipStreamSynchronize(s));
+
+   // the totals, then the carry: the window's records from carry_rec on (with them the bytes of a record the window cut: push_bgzf)
+   int set_carry()
+   {
+      // (every accepted record counts once: in the window that consumes it -- the last consumes all, reads behind the last cluster too)
+      F->n_records += n_new, F->n_decoded += n_rec, F->n_accepted += last ? n_reads : done.reads_done;
+      F->k0 += done.n_done;
+      const sb::StreamCarry carry = sb::stream_carry(w_end, c0, F->chunk_cap);
+      if (!carry.fits)
+         return api_fail(SBGPU_ESHAPE, "sbgpu_front_stream_push: the records of one cluster exceed a chunk's capacity (" + std::to_string(carry.bytes) + " bytes): begin the stream with larger chunks");
+      F->carry_n = n_rec - carry_rec, F->carry_rec = carry_rec, F->carry_c0 = c0;
+      F->win ^= 1; // (this window's offsets are the next one's "window before")
+      return copy_carry(carry.bytes, c0);
    }
-   F->pending = false;
-   F->note_memory();
-   return SBGPU_OK;
+
+   int run()
+   {
+      F->n_chunks += F->pending && F->pend_bytes ? 1 : 0; // (an empty push is no chunk)
+      F->redecoded += n_carry;
+      if (F->mode == 2) SB_FRONT_RC(inflate_and_index());
+      if (finished) return SBGPU_OK;
+      if (n_rec == 0) {
+         if (last) { // nothing more will come: the clusters not yet finished are, without hits
+            for (int64_t k = F->k0; k < F->n_clusters; ++k) F->locus_hit_off[(size_t)k + 1] = F->n_hits;
+            F->k0 = F->n_clusters;
+         }
+         return SBGPU_OK;
+      }
+      if (F->mode != 2) SB_FRONT_RC(window_offsets());
+      SB_FRONT_RC(decode());
+      SB_FRONT_RC(assign());
+      SB_FRONT_RC(find_carry());
+      if (done.n_done > 0 && done.reads_done > 0) SB_FRONT_RC(pair_and_collapse());
+      else
+         for (int64_t k = 0; k < done.n_done; ++k) F->locus_hit_off[(size_t)(F->k0 + k + 1)] = F->n_hits;
+      SB_FRONT_RC(set_carry());
+      F->note_memory();
+      return SBGPU_OK;
+   }
+};
+
+int compute_pending(sbgpu_front_stream *F, bool last)
+{
+   hipStream_t s = sb::ctx_stream(F->ctx);
+   // every stage below synchronises the stream it ran on before it returns, so the arenas its handles give back are idle: they
+   // must not wait for the DEVICE -- the next chunk's upload is running on it
+   sb::DevGiveStreamSynced no_device_wait;
+   const double t_in = now_seconds();
+   SB_FRONT_TRY(hipEventSynchronize(F->ev_up[F->cur])); // the chunk has arrived
+   const double t_arrived = now_seconds();
+   F->t_wait += t_arrived - t_in;
+   const int rc = PendingCall{F, last}.run(); // (the window's handles are back in the pool behind it: their time is the chunk's)
+   F->t_compute += now_seconds() - t_arrived;
+   if (rc == SBGPU_OK) F->pending = false;
+   return rc;
 }
 
 } // namespace
+
 
 extern "C" {
 
@@ -387,7 +412,7 @@ int sbgpu_front_stream_begin(sbgpu_ctx_t *c, const sbgpu_clusters_t *cl, const s
    F->c_strand.assign(cl->strand, cl->strand + cl->n_clusters);
    F->opts = *opts;
    F->chunk_cap = chunk_bytes;
-   F->room = (int64_t)up256((size_t)chunk_bytes);
+   F->room = (int64_t)sb::up256((size_t)chunk_bytes);
    F->locus_hit_off.assign((size_t)cl->n_clusters + 1, 0);
    hipError_t e = hipSetDevice(F->device);
    size_t tot = 0;
@@ -416,7 +441,8 @@ int sbgpu_front_stream_push(sbgpu_front_stream_t *F, const uint8_t *bytes, int64
    if (n_bytes < 0 || (n_bytes && !bytes) || n_bytes > F->chunk_cap) return api_fail(SBGPU_EINVAL, "sbgpu_front_stream_push: a chunk holds at most the bytes the stream was begun with");
    if (F->mode == 2) return api_fail(SBGPU_EINVAL, "sbgpu_front_stream_push: the stream is fed with BGZF members (push_bgzf); the two are not mixed");
    F->mode = 1;
-   SB_TRY(hipSetDevice(F->device));
+   const hipStream_t s = F->up_stream; // the entry's stream: the uploads'
+   SB_FRONT_TRY(hipSetDevice(F->device));
    // the chunk's record offsets: the caller's (noted while inflating), or found here
    std::vector<int64_t> found;
    if (rec_off) {
@@ -428,18 +454,17 @@ int sbgpu_front_stream_push(sbgpu_front_stream_t *F, const uint8_t *bytes, int64
       rec_off = found.data();
    }
    // this chunk starts its way to the device (into the buffer the pending chunk does NOT use), its offsets in front of it ...
-   const double t_push = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+   const double t_push = now_seconds();
    const int nb = F->pending ? F->cur ^ 1 : F->cur;
-   hipStream_t cs = F->up_stream;
    F->d_pend[nb].used = 0;
-   SB_TRY(F->d_pend[nb].reserve((size_t)(n_records + 1) * 8, cs));
-   SB_TRY(hipMemcpyAsync(F->d_pend[nb].p, rec_off, (size_t)(n_records + 1) * 8, hipMemcpyHostToDevice, cs));
-   if (!found.empty()) SB_TRY(hipStreamSynchronize(cs)); // (the offsets found here live in this frame)
-   if (n_bytes) SB_TRY(hipMemcpyAsync(F->buf[nb] + F->room, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, cs));
-   SB_TRY(hipEventRecord(F->ev_up[nb], cs));
-   F->t_enqueue += std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t_push;
+   SB_FRONT_TRY(F->d_pend[nb].reserve((size_t)(n_records + 1) * 8, s));
+   SB_FRONT_TRY(hipMemcpyAsync(F->d_pend[nb].p, rec_off, (size_t)(n_records + 1) * 8, hipMemcpyHostToDevice, s));
+   if (!found.empty()) SB_FRONT_TRY(hipStreamSynchronize(s)); // (the offsets found here live in this frame)
+   if (n_bytes) SB_FRONT_TRY(hipMemcpyAsync(F->buf[nb] + F->room, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, s));
+   SB_FRONT_TRY(hipEventRecord(F->ev_up[nb], s));
+   F->t_enqueue += now_seconds() - t_push;
    // ... while the pending one is computed (its carry lands in front of this chunk, in buffer nb)
-   if (F->pending) SB_RC(compute_pending(F, false));
+   if (F->pending) SB_FRONT_RC(compute_pending(F, false));
    else if (F->carry_bytes) return api_fail(SBGPU_EHIP, "sbgpu_front_stream_push: internal: a carry without a pending chunk");
    F->cur = nb;
    F->pending = true;
@@ -463,27 +488,27 @@ int sbgpu_front_stream_push_bgzf(sbgpu_front_stream_t *F, const uint8_t *file_by
    const int64_t span = n_blocks ? out_off[n_blocks] - out_off[0] : 0;
    if (span > F->chunk_cap)
       return api_fail(SBGPU_ESHAPE, "sbgpu_front_stream_push_bgzf: the push inflates to " + std::to_string(span) + " bytes, more than the chunks the stream was begun with");
-   SB_TRY(hipSetDevice(F->device));
+   const hipStream_t s = F->up_stream; // the entry's stream: the uploads'
+   SB_FRONT_TRY(hipSetDevice(F->device));
    F->mode = 2;
-   const double t_push = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+   const double t_push = now_seconds();
    const int nb = F->pending ? F->cur ^ 1 : F->cur;
-   hipStream_t cs = F->up_stream;
    // the table (kept on the host too: the caller's arrays are free once this returns) and the compressed bytes start their way
    F->h_blk[nb].assign(blk_off, blk_off + (n_blocks ? n_blocks + 1 : 0));
    F->h_out[nb].assign(out_off, out_off + (n_blocks ? n_blocks + 1 : 0));
    if (n_blocks) {
       const size_t tab = (size_t)(n_blocks + 1) * 8;
       F->d_tab[nb].used = 0, F->d_comp[nb].used = 0;
-      SB_TRY(F->d_tab[nb].reserve(2 * tab + (size_t)n_blocks, cs));
-      SB_TRY(F->d_comp[nb].reserve((size_t)n_bytes + 16, cs));
-      SB_TRY(hipMemcpyAsync(F->d_tab[nb].p, F->h_blk[nb].data(), tab, hipMemcpyHostToDevice, cs));
-      SB_TRY(hipMemcpyAsync(F->d_tab[nb].p + tab, F->h_out[nb].data(), tab, hipMemcpyHostToDevice, cs));
-      SB_TRY(hipMemcpyAsync(F->d_comp[nb].p, file_bytes, (size_t)n_bytes, hipMemcpyHostToDevice, cs));
+      SB_FRONT_TRY(F->d_tab[nb].reserve(2 * tab + (size_t)n_blocks, s));
+      SB_FRONT_TRY(F->d_comp[nb].reserve((size_t)n_bytes + 16, s));
+      SB_FRONT_TRY(hipMemcpyAsync(F->d_tab[nb].p, F->h_blk[nb].data(), tab, hipMemcpyHostToDevice, s));
+      SB_FRONT_TRY(hipMemcpyAsync(F->d_tab[nb].p + tab, F->h_out[nb].data(), tab, hipMemcpyHostToDevice, s));
+      SB_FRONT_TRY(hipMemcpyAsync(F->d_comp[nb].p, file_bytes, (size_t)n_bytes, hipMemcpyHostToDevice, s));
    }
-   SB_TRY(hipEventRecord(F->ev_up[nb], cs));
-   F->t_enqueue += std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t_push;
+   SB_FRONT_TRY(hipEventRecord(F->ev_up[nb], s));
+   F->t_enqueue += now_seconds() - t_push;
    // ... while the pending chunk is inflated and computed (its carry lands in front of where this one will be inflated)
-   if (F->pending) SB_RC(compute_pending(F, false));
+   if (F->pending) SB_FRONT_RC(compute_pending(F, false));
    F->cur = nb;
    F->pending = true;
    F->pend_bytes = span, F->pend_records = 0;
@@ -499,11 +524,12 @@ int sbgpu_front_stream_end(sbgpu_front_stream_t *F, const sbgpu_annotation_t *an
    if (!F || F->ended) return api_fail(SBGPU_EINVAL, "sbgpu_front_stream_end: no stream (or it has ended)");
    if (!an || !params || !out || !bins_out) return api_fail(SBGPU_EINVAL, "sbgpu_front_stream_end: null argument");
    if (an->n_loci != F->n_clusters) return api_fail(SBGPU_EINVAL, "sbgpu_front_stream_end: the annotation's loci are the stream's clusters, one to one");
-   SB_TRY(hipSetDevice(F->device));
+   const hipStream_t s = sb::ctx_stream(F->ctx);
+   SB_FRONT_TRY(hipSetDevice(F->device));
    if (!F->pending) { // nothing was pushed (or an empty last chunk): the carry alone, if any
-      SB_TRY(hipEventRecord(F->ev_up[F->cur], sb::ctx_stream(F->ctx)));
+      SB_FRONT_TRY(hipEventRecord(F->ev_up[F->cur], s));
    }
-   SB_RC(compute_pending(F, true));
+   SB_FRONT_RC(compute_pending(F, true));
    F->ended = true;
    // the chunk buffers are not needed any more: the last stage gets their room
    for (int b = 0; b < 2; ++b) {
@@ -512,15 +538,14 @@ int sbgpu_front_stream_end(sbgpu_front_stream_t *F, const sbgpu_annotation_t *an
    }
    for (int b = 0; b < 2; ++b) F->d_win[b].release(), F->d_pend[b].release(), F->d_comp[b].release(), F->d_tab[b].release();
    (void)sbgpu_release_idle_memory();
-   hipStream_t s = sb::ctx_stream(F->ctx);
-   SB_TRY(F->s_foff.reserve(8, s));
-   if (F->n_hits == 0) SB_TRY(hipMemsetAsync(F->s_foff.p, 0, 8, s));
+   SB_FRONT_TRY(F->s_foff.reserve(8, s));
+   if (F->n_hits == 0) SB_FRONT_TRY(hipMemsetAsync(F->s_foff.p, 0, 8, s));
    sbgpu_hits_t h = {F->n_hits, (const int32_t *)F->s_locus.p, (const int64_t *)F->s_foff.p, (const uint8_t *)F->s_code.p,
                      (const uint32_t *)F->s_left.p, (const uint32_t *)F->s_right.p};
-   const double t_q = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+   const double t_q = now_seconds();
    const int rc = sbgpu_quantify_resident(F->ctx, an, &h, (const float *)F->s_mass.p, F->locus_hit_off.data(), insert, read_len, long_read,
                                           F->mapped_reads, params, comm, insert_used, out, bins_out);
-   F->t_last = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t_q;
+   F->t_last = now_seconds() - t_q;
    F->note_memory();
    if (std::getenv("SBGPU_HOST_TIMING")) // diagnostic: where the pass' time went, on stderr
       std::fprintf(stderr, "sbgpu_front_stream: %lld chunks | waiting for uploads %.1f ms | computing chunks %.1f ms | enqueuing uploads %.1f ms | last stage %.1f ms\n",

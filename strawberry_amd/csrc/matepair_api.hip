@@ -13,7 +13,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/sbgpu.h"
-#include "api_internal.h"
+#include "front_common.h"
 #include "matepair_device.h"
 #include "matepair_flat.h"
 
@@ -42,214 +42,192 @@ struct sbgpu_matepairs {
 };
 
 namespace {
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 constexpr int kMaxFragSpanHost = 1000000; // src/common.cpp:17
-} // namespace
+static_assert(sizeof(sb::FlatRec) == sb::kFlatRecBytes, "front_schedule.h lays FlatRec arrays out");
 
-// ---- the flat form (matepair_flat.h): every cluster of the call at once
-static int pair_mates_flat(sbgpu_ctx_t *c, int64_t n_loci, const sbgpu_reads_t *dr, const int64_t *locus_read_off, hipStream_t s,
-                           sbgpu_matepairs *M)
-{
-   const int64_t nr = dr->n_reads;
-   if (nr >= ((int64_t)1 << 31) - 2) return api_fail(SBGPU_EUNSUPPORTED, "sbgpu_pair_mates_device: more than 2^31 records in one call; split the call or use sbgpu_pair_mates_host");
-   char *w = nullptr;
-   size_t w_cap = 0;
-   auto bail = [&](int code, const std::string &msg) {
-      (void)hipStreamSynchronize(s);
-      sb::dev_give(w, w_cap);
-      return api_fail(code, msg);
-   };
-#define SB_TRY(expr)                                                                                     \
-   do {                                                                                                  \
-      hipError_t e_ = (expr);                                                                            \
-      if (e_ != hipSuccess) return bail(e_ == hipErrorOutOfMemory ? SBGPU_ENOMEM : SBGPU_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-   } while (0)
-   SB_TRY(hipSetDevice(M->device));
-   const size_t n = (size_t)nr, n1 = n + 1, nl1 = (size_t)n_loci + 1;
-   if (n_loci > ((int64_t)1 << 23)) return api_fail(SBGPU_EUNSUPPORTED, "sbgpu_pair_mates_device: more than 2^23 clusters in one call; split the call");
-   // the first sort's key (flat_mate_keys_kernel): 32 bits = the number of a group of 2^g neighbouring clusters, then a hash
-   // of (cluster, read id) of two bits more than the logarithm of the biggest group's record count; the smallest g that fits
-   const size_t nt = (n1 + 63) / 64, nt1 = nt + 1; // tiles of 64 pairs (flat_mate_count_kernel's waves)
-   unsigned locus_bits = 1;
-   while (((int64_t)1 << locus_bits) < n_loci) ++locus_bits;
-   unsigned hash_bits = 32, group_shift = locus_bits, sort_bits = 32;
-   for (unsigned g = 0; g <= locus_bits; ++g) {
-      int64_t biggest = 1;
-      for (int64_t l = 0; l < n_loci; l += (int64_t)1 << g) biggest = std::max(biggest, locus_read_off[std::min<int64_t>(n_loci, l + ((int64_t)1 << g))] - locus_read_off[l]);
-      unsigned hb = 2;
-      while (((int64_t)1 << (hb - 2)) < biggest) ++hb;
-      if (locus_bits - g + hb <= 32 || g == locus_bits) {
-         hash_bits = std::min(32u, hb), group_shift = g;
-         sort_bits = std::min(32u, locus_bits - g + hash_bits);
-         break;
-      }
-   }
-   size_t tmp_bytes = 0, sort_tmp_bytes = 0;
-   {
-      size_t b = 0;
-      (void)rocprim::radix_sort_pairs(nullptr, b, (const uint32_t *)nullptr, (uint32_t *)nullptr, rocprim::counting_iterator<int32_t>(0), (int32_t *)nullptr, n, 0, sort_bits, s);
-      sort_tmp_bytes = b;
-      (void)rocprim::exclusive_scan(nullptr, b, rocprim::make_transform_iterator((const int32_t *)nullptr, [] __device__(int32_t v) { return (int64_t)v; }), (int64_t *)nullptr, (int64_t)0, nt1, rocprim::plus<int64_t>(), s);
-      tmp_bytes = std::max(tmp_bytes, b);
-   }
-   size_t off = 0;
-   auto take = [&](size_t bytes) {
-      const size_t o = off;
-      off += up256(bytes ? bytes : 8);
-      return o;
-   };
-   // what both forms use
-   const size_t o_roff = take(nl1 * 8), o_rarr = take(n * sizeof(sb::FlatRec)), o_lefts = take(n * 4), o_claim = take(n * 4), o_slot = take(n * 8), o_runlen = take(n * 4);
-   const size_t o_done = take(n * 8), o_td = take(nt1 * 4), o_tda = take(nt1 * 8), o_prec = take(n * 4), o_pval = take(n * 4);
-   const size_t o_lf = take(n1 * 4), o_rf = take(n1 * 4), o_tl = take(nt1 * 4), o_tr = take(nt1 * 4), o_ls = take(nt1 * 8), o_rs = take(nt1 * 8), o_poff = take(nl1 * 8), o_counts = take(64 * 64 + 256), o_tmp = take(tmp_bytes);
-   SB_TRY(sb::dev_take(off, &w, &w_cap));
-   SB_TRY(hipMemsetAsync(w + o_counts, 0, 64 * 64 + 256, s));
-   SB_TRY(hipMemsetAsync(w + o_td + ((n + 63) / 64) * 4, 0, 4, s)); // (the scans' entry beyond the last tile)
-   SB_TRY(hipMemsetAsync(w + o_tl + nt * 4, 0, 4, s));
-   SB_TRY(hipMemsetAsync(w + o_tr + nt * 4, 0, 4, s));
-   SB_TRY(hipMemcpyAsync(w + o_roff, locus_read_off, nl1 * 8, hipMemcpyHostToDevice, s));
+// ---- the flat form (matepair_flat.h): every cluster of the call at once.  What the call decides is front_schedule.h's
+// (mate_sort_key, the three layouts); the steps below issue it.
+struct PairMatesCall {
+   const int64_t n_loci;
+   const sbgpu_reads_t *const dr;
+   const int64_t *const locus_read_off;
+   const hipStream_t s;
+   sbgpu_matepairs *const M;
+   const size_t n = (size_t)dr->n_reads, nl1 = (size_t)n_loci + 1;
+   sb::MateSortKey key = {};
+   size_t tmp_bytes = 0, sort_tmp_bytes = 0; // the library calls' temporary storage: the scans', the sort's
+   sb::MateScratchLayout L = {};
+   sb::DevBlock w{s};
    sb::FlatMateArgs f = {};
-   sb::MateArgs &a = f.a;
-   a.n_loci = n_loci;
-   a.locus_read_off = (const int64_t *)(w + o_roff);
-   a.read_id = dr->read_id;
-   a.block_off = dr->block_off;
-   a.block_left = dr->block_left, a.block_right = dr->block_right;
-   a.partner_pos = dr->partner_pos;
-   a.flags = dr->flags;
-   a.nh = dr->nh;
-   f.n_reads = nr;
-   f.hash_bits = (int)hash_bits, f.group_shift = (int)group_shift;
-   f.rec_arr = (sb::FlatRec *)(w + o_rarr);
-   f.lefts = (uint32_t *)(w + o_lefts), f.claim = (uint32_t *)(w + o_claim);
-   f.slot = (uint32_t *)(w + o_slot), f.runlen = (uint32_t *)(w + o_runlen);
-   f.done = (unsigned long long *)(w + o_done);
-   f.tile_done = (int32_t *)(w + o_td), f.tile_done_at = (const int64_t *)(w + o_tda);
-   f.pair_rec_w = (uint32_t *)(w + o_prec), f.pair_val_w = (uint32_t *)(w + o_pval);
-   f.pair_rec = (const uint32_t *)(w + o_prec), f.pair_val = (const uint32_t *)(w + o_pval);
-   f.lfeat = (int32_t *)(w + o_lf), f.rfeat = (int32_t *)(w + o_rf);
-   f.tile_l = (int32_t *)(w + o_tl), f.tile_r = (int32_t *)(w + o_tr);
-   f.lscan = (const int64_t *)(w + o_ls), f.rscan = (const int64_t *)(w + o_rs);
-   f.locus_pair_off = (int64_t *)(w + o_poff);
-   f.counts = (unsigned long long *)(w + o_counts);
-   f.trouble = (uint32_t *)(w + o_counts + 64 * 64);
-   const unsigned gr = (unsigned)((n + 255) / 256), gr1 = (unsigned)((std::max(n1, nl1) + 255) / 256);
-   void *tmp = w + o_tmp;
-   size_t tb = tmp_bytes;
-   unsigned long long slots[64 * 8], counts[4] = {0, 0, 0, 0};
+   unsigned gr = 0, gr1 = 0;
+   unsigned long long slots[64 * 8]; // what rank_and_count brings back: the counters' slots, the features' totals, the forms' verdict
    int64_t totals[2] = {0, 0};
    uint32_t trouble = 0;
-   // what follows the matching, whichever form made it: the pairs in the order their completing records arrive, the mates'
-   // feature counts, where every pair's features go; the totals come back with one synchronisation
-   auto rank_and_count = [&]() -> int {
-      hipLaunchKernelGGL(sb::flat_mate_done_tiles_kernel, dim3(gr), dim3(256), 0, s, f);
-      tb = tmp_bytes;
-      SB_TRY(rocprim::exclusive_scan(tmp, tb, rocprim::make_transform_iterator((const int32_t *)f.tile_done, [] __device__(int32_t v) { return (int64_t)v; }), (int64_t *)(w + o_tda), (int64_t)0, (n + 63) / 64 + 1, rocprim::plus<int64_t>(), s));
-      hipLaunchKernelGGL(sb::flat_mate_order_kernel, dim3(gr), dim3(256), 0, s, f);
-      hipLaunchKernelGGL(sb::flat_mate_count_kernel, dim3(sb::xcd_grid(gr1)), dim3(256), 0, s, f);
-      SB_TRY(hipGetLastError());
-      tb = tmp_bytes;
-      SB_TRY(rocprim::exclusive_scan(tmp, tb, rocprim::make_transform_iterator((const int32_t *)f.tile_l, [] __device__(int32_t v) { return (int64_t)v; }), (int64_t *)(w + o_ls), (int64_t)0, nt1, rocprim::plus<int64_t>(), s));
-      tb = tmp_bytes;
-      SB_TRY(rocprim::exclusive_scan(tmp, tb, rocprim::make_transform_iterator((const int32_t *)f.tile_r, [] __device__(int32_t v) { return (int64_t)v; }), (int64_t *)(w + o_rs), (int64_t)0, nt1, rocprim::plus<int64_t>(), s));
-      SB_TRY(hipMemcpyAsync(slots, w + o_counts, sizeof(slots), hipMemcpyDeviceToHost, s));
-      SB_TRY(hipMemcpyAsync(&trouble, w + o_counts + 64 * 64, 4, hipMemcpyDeviceToHost, s));
-      SB_TRY(hipMemcpyAsync(&totals[0], w + o_ls + nt * 8, 8, hipMemcpyDeviceToHost, s));
-      SB_TRY(hipMemcpyAsync(&totals[1], w + o_rs + nt * 8, 8, hipMemcpyDeviceToHost, s));
-      SB_TRY(hipMemcpyAsync(M->locus_pair_off.data(), w + o_poff, nl1 * 8, hipMemcpyDeviceToHost, s));
-      SB_TRY(hipStreamSynchronize(s));
+
+   // the exclusive prefix sums of `count` 32-bit entries, as 64-bit words at offset `out`
+   hipError_t scan_i64(const int32_t *in, size_t out, size_t count)
+   {
+      size_t tb = tmp_bytes;
+      return rocprim::exclusive_scan(w.p + L.tmp, tb, rocprim::make_transform_iterator(in, sb::I32AsI64()), w.at<int64_t>(out), (int64_t)0, count, rocprim::plus<int64_t>(), s);
+   }
+
+   // the sort's key and the library's temporary bytes, the scratch, what must start at zero, the kernels' arguments
+   int lay_out()
+   {
+      key = sb::mate_sort_key(n_loci, locus_read_off);
+      (void)rocprim::radix_sort_pairs(nullptr, sort_tmp_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr, rocprim::counting_iterator<int32_t>(0), (int32_t *)nullptr, n, 0, key.sort_bits, s);
+      (void)rocprim::exclusive_scan(nullptr, tmp_bytes, rocprim::make_transform_iterator((const int32_t *)nullptr, sb::I32AsI64()), (int64_t *)nullptr, (int64_t)0, sb::front_tiles64(n + 1) + 1, rocprim::plus<int64_t>(), s);
+      L = sb::mate_scratch_layout((int64_t)n, n_loci, tmp_bytes);
+      SB_FRONT_TRY(w.take(L.bytes));
+      SB_FRONT_TRY(hipMemsetAsync(w.p + L.counts, 0, L.counts_bytes, s));
+      SB_FRONT_TRY(hipMemsetAsync(w.p + L.td_tail, 0, 4, s));
+      SB_FRONT_TRY(hipMemsetAsync(w.p + L.tl_tail, 0, 4, s));
+      SB_FRONT_TRY(hipMemsetAsync(w.p + L.tr_tail, 0, 4, s));
+      SB_FRONT_TRY(hipMemcpyAsync(w.p + L.roff, locus_read_off, nl1 * 8, hipMemcpyHostToDevice, s));
+      sb::MateArgs &a = f.a;
+      a.n_loci = n_loci;
+      a.locus_read_off = w.at<const int64_t>(L.roff);
+      a.read_id = dr->read_id;
+      a.block_off = dr->block_off;
+      a.block_left = dr->block_left, a.block_right = dr->block_right;
+      a.partner_pos = dr->partner_pos;
+      a.flags = dr->flags;
+      a.nh = dr->nh;
+      f.n_reads = (int64_t)n;
+      f.hash_bits = (int)key.hash_bits, f.group_shift = (int)key.group_shift;
+      f.rec_arr = w.at<sb::FlatRec>(L.rarr);
+      f.lefts = w.at<uint32_t>(L.lefts), f.claim = w.at<uint32_t>(L.claim);
+      f.slot = w.at<uint32_t>(L.slot), f.runlen = w.at<uint32_t>(L.runlen);
+      f.done = w.at<unsigned long long>(L.done);
+      f.tile_done = w.at<int32_t>(L.td), f.tile_done_at = w.at<const int64_t>(L.tda);
+      f.pair_rec_w = w.at<uint32_t>(L.prec), f.pair_val_w = w.at<uint32_t>(L.pval);
+      f.pair_rec = w.at<const uint32_t>(L.prec), f.pair_val = w.at<const uint32_t>(L.pval);
+      f.lfeat = w.at<int32_t>(L.lf), f.rfeat = w.at<int32_t>(L.rf);
+      f.tile_l = w.at<int32_t>(L.tl), f.tile_r = w.at<int32_t>(L.tr);
+      f.lscan = w.at<const int64_t>(L.ls), f.rscan = w.at<const int64_t>(L.rs);
+      f.locus_pair_off = w.at<int64_t>(L.poff);
+      f.counts = w.at<unsigned long long>(L.counts);
+      f.trouble = w.at<uint32_t>(L.trouble);
+      gr = (unsigned)((n + 255) / 256), gr1 = (unsigned)((std::max(n + 1, nl1) + 255) / 256);
       return SBGPU_OK;
-   };
+   }
+
    // ---- the positional form (matepair_flat.h): no sort.  Its kernels say when they cannot serve the call (records that do
    // not ascend by position inside a cluster, a read id with several fitting mates); the ranking behind them has run by then -- it costs the call one more pass, in the rare case.
-   // SBGPU_PAIR_FORCE_SORT=1 (tests): every call takes the sorted form.
-   const char *force_env = std::getenv("SBGPU_PAIR_FORCE_SORT");
-   bool sorted_form = force_env && std::atoi(force_env) != 0;
-   if (!sorted_form) {
-      SB_TRY(hipMemsetAsync(w + o_slot, 0, n * 8, s));
+   int positional_form()
+   {
+      SB_FRONT_TRY(hipMemsetAsync(w.p + L.slot, 0, L.slot_bytes, s));
       hipLaunchKernelGGL(sb::flat_mate_rec_kernel, dim3(sb::xcd_grid(gr)), dim3(256), 0, s, f);
       hipLaunchKernelGGL(sb::flat_mate_match_kernel, dim3(sb::xcd_grid(gr)), dim3(256), 0, s, f);
-      SB_TRY(hipGetLastError());
-      if (const int rc = rank_and_count(); rc != SBGPU_OK) return rc;
-      sorted_form = trouble != 0;
+      SB_FRONT_TRY(hipGetLastError());
+      return rank_and_count();
    }
-   M->positional = !sorted_form;
-   M->why_sorted = trouble;
-   if (sorted_form) {
-      // ---- the sorted form: ONE stable radix sort brings the records of a read id together in arrival order, a walk pairs them
-      // with the reference's chain rules (any number of waiting mates per read id)
-      char *w2 = nullptr;
-      size_t w2_cap = 0, off2 = 0;
-      auto take2 = [&](size_t bytes) {
-         const size_t o = off2;
-         off2 += up256(bytes ? bytes : 8);
-         return o;
-      };
-      const size_t o_key = take2(n * 4), o_skey = take2(n * 4), o_order = take2(n * 4), o_rec = take2(n * sizeof(sb::FlatRec)), o_state = take2(n), o_stmp = take2(sort_tmp_bytes);
-      SB_TRY(sb::dev_take(off2, &w2, &w2_cap));
-      struct Give {
-         char *&p;
-         size_t &cap;
-         hipStream_t s;
-         ~Give()
-         {
-            (void)hipStreamSynchronize(s);
-            sb::dev_give(p, cap);
-         }
-      } give2 = {w2, w2_cap, s};
-      f.key = (uint32_t *)(w2 + o_key);
-      f.skey = (const uint32_t *)(w2 + o_skey);
-      f.order = (const int32_t *)(w2 + o_order);
-      f.rec = (sb::FlatRec *)(w2 + o_rec);
-      f.state = (uint8_t *)(w2 + o_state);
+
+   // what follows the matching, whichever form made it: the pairs in the order their completing records arrive, the mates'
+   // feature counts, where every pair's features go; the totals come back with one synchronisation
+   int rank_and_count()
+   {
+      hipLaunchKernelGGL(sb::flat_mate_done_tiles_kernel, dim3(gr), dim3(256), 0, s, f);
+      SB_FRONT_TRY(scan_i64(f.tile_done, L.tda, L.done_tiles + 1));
+      hipLaunchKernelGGL(sb::flat_mate_order_kernel, dim3(gr), dim3(256), 0, s, f);
+      hipLaunchKernelGGL(sb::flat_mate_count_kernel, dim3(sb::xcd_grid(gr1)), dim3(256), 0, s, f);
+      SB_FRONT_TRY(hipGetLastError());
+      SB_FRONT_TRY(scan_i64(f.tile_l, L.ls, L.pair_tiles + 1));
+      SB_FRONT_TRY(scan_i64(f.tile_r, L.rs, L.pair_tiles + 1));
+      SB_FRONT_TRY(hipMemcpyAsync(slots, w.p + L.counts, sizeof(slots), hipMemcpyDeviceToHost, s));
+      SB_FRONT_TRY(hipMemcpyAsync(&trouble, w.p + L.trouble, 4, hipMemcpyDeviceToHost, s));
+      SB_FRONT_TRY(hipMemcpyAsync(&totals[0], w.p + L.ls_total, 8, hipMemcpyDeviceToHost, s));
+      SB_FRONT_TRY(hipMemcpyAsync(&totals[1], w.p + L.rs_total, 8, hipMemcpyDeviceToHost, s));
+      SB_FRONT_TRY(hipMemcpyAsync(M->locus_pair_off.data(), w.p + L.poff, nl1 * 8, hipMemcpyDeviceToHost, s));
+      SB_FRONT_TRY(hipStreamSynchronize(s));
+      return SBGPU_OK;
+   }
+
+   // ---- the sorted form: ONE stable radix sort brings the records of a read id together in arrival order, a walk pairs them
+   // with the reference's chain rules (any number of waiting mates per read id)
+   int sorted_form()
+   {
+      const sb::MateSortedLayout S = sb::mate_sorted_layout((int64_t)n, sort_tmp_bytes);
+      sb::DevBlock w2(s);
+      SB_FRONT_TRY(w2.take(S.bytes));
+      f.key = w2.at<uint32_t>(S.key);
+      f.skey = w2.at<const uint32_t>(S.skey);
+      f.order = w2.at<const int32_t>(S.order);
+      f.rec = w2.at<sb::FlatRec>(S.rec);
+      f.state = w2.at<uint8_t>(S.state);
       f.claim = nullptr;
-      SB_TRY(hipMemsetAsync(w + o_counts, 0, 64 * 64 + 256, s));
+      SB_FRONT_TRY(hipMemsetAsync(w.p + L.counts, 0, L.counts_bytes, s));
       hipLaunchKernelGGL(sb::flat_mate_keys_kernel, dim3(gr), dim3(256), 0, s, f); // (also: the records as the rules see them, `done` zeroed)
-      SB_TRY(hipGetLastError());
+      SB_FRONT_TRY(hipGetLastError());
       size_t stb = sort_tmp_bytes;
-      SB_TRY(rocprim::radix_sort_pairs(w2 + o_stmp, stb, (const uint32_t *)f.key, (uint32_t *)(w2 + o_skey), rocprim::counting_iterator<int32_t>(0), (int32_t *)(w2 + o_order), n, 0, sort_bits, s));
+      SB_FRONT_TRY(rocprim::radix_sort_pairs(w2.p + S.stmp, stb, (const uint32_t *)f.key, w2.at<uint32_t>(S.skey), rocprim::counting_iterator<int32_t>(0), w2.at<int32_t>(S.order), n, 0, key.sort_bits, s));
       hipLaunchKernelGGL(sb::flat_mate_pack_kernel, dim3(gr), dim3(256), 0, s, f);
       hipLaunchKernelGGL(sb::flat_mate_walk_kernel, dim3(gr), dim3(256), 0, s, f);
-      SB_TRY(hipGetLastError());
-      if (const int rc = rank_and_count(); rc != SBGPU_OK) return rc;
+      SB_FRONT_TRY(hipGetLastError());
+      return rank_and_count();
    }
-   for (int k = 0; k < 64; ++k)
-      for (int i = 0; i < 4; ++i) counts[i] += slots[k * 8 + i]; // (wrapping sums: a slot's orphan count may be "negative")
-   M->n_refused = (int64_t)counts[0], M->n_orphan = (int64_t)counts[1], M->n_single = (int64_t)counts[2], M->n_complete = (int64_t)counts[3];
-   M->n_pairs = M->locus_pair_off[(size_t)n_loci];
-   M->n_lfeat = totals[0], M->n_rfeat = totals[1];
-   if (M->n_pairs != M->n_single + M->n_complete) return bail(SBGPU_EHIP, "sbgpu_pair_mates_device: the pairs' count and the walk's counters disagree");
-   // ---- the pairs' own arena
-   const size_t np1 = (size_t)M->n_pairs + 1, nlf = (size_t)M->n_lfeat + 1, nrf = (size_t)M->n_rfeat + 1;
-   size_t t = 0;
-   const size_t u_mass = t; t += up256(np1 * 8);
-   const size_t u_loff = t; t += up256(np1 * 8);
-   const size_t u_roff = t; t += up256(np1 * 8);
-   const size_t u_ll = t; t += up256(nlf * 4);
-   const size_t u_lr = t; t += up256(nlf * 4);
-   const size_t u_rl = t; t += up256(nrf * 4);
-   const size_t u_rr = t; t += up256(nrf * 4);
-   const size_t u_lc = t; t += up256(nlf);
-   const size_t u_rc = t; t += up256(nrf);
-   SB_TRY(sb::dev_take(t, &M->arena, &M->arena_cap));
-   M->d_mass = (double *)(M->arena + u_mass);
-   M->d_left_off = (int64_t *)(M->arena + u_loff);
-   M->d_right_off = (int64_t *)(M->arena + u_roff);
-   M->d_left_left = (uint32_t *)(M->arena + u_ll), M->d_left_right = (uint32_t *)(M->arena + u_lr);
-   M->d_right_left = (uint32_t *)(M->arena + u_rl), M->d_right_right = (uint32_t *)(M->arena + u_rr);
-   M->d_left_code = (uint8_t *)(M->arena + u_lc), M->d_right_code = (uint8_t *)(M->arena + u_rc);
-   a.pair_mass = M->d_mass;
-   a.left_off = M->d_left_off, a.right_off = M->d_right_off;
-   a.left_code = M->d_left_code, a.right_code = M->d_right_code;
-   a.left_left = M->d_left_left, a.left_right = M->d_left_right;
-   a.right_left = M->d_right_left, a.right_right = M->d_right_right;
-   hipLaunchKernelGGL(sb::flat_mate_fill_kernel, dim3(sb::xcd_grid((int64_t)((np1 + 255) / 256))), dim3(256), 0, s, f, M->n_pairs);
-   SB_TRY(hipGetLastError());
-   SB_TRY(hipStreamSynchronize(s)); // the scratch goes back to the pool
-#undef SB_TRY
-   sb::dev_give(w, w_cap);
-   return SBGPU_OK;
+
+   // the counters' 64 slots summed; the handle's totals
+   int sum_totals()
+   {
+      unsigned long long counts[4] = {0, 0, 0, 0};
+      for (int k = 0; k < 64; ++k)
+         for (int i = 0; i < 4; ++i) counts[i] += slots[k * 8 + i]; // (wrapping sums: a slot's orphan count may be "negative")
+      M->n_refused = (int64_t)counts[0], M->n_orphan = (int64_t)counts[1], M->n_single = (int64_t)counts[2], M->n_complete = (int64_t)counts[3];
+      M->n_pairs = M->locus_pair_off[(size_t)n_loci];
+      M->n_lfeat = totals[0], M->n_rfeat = totals[1];
+      if (M->n_pairs != M->n_single + M->n_complete) return api_fail(SBGPU_EHIP, "sbgpu_pair_mates_device: the pairs' count and the walk's counters disagree");
+      return SBGPU_OK;
+   }
+
+   // ---- the pairs' own arena, filled; the scratch goes back to the pool behind the last synchronisation
+   int fill()
+   {
+      const sb::MatePairsLayout P = sb::mate_pairs_layout(M->n_pairs, M->n_lfeat, M->n_rfeat);
+      SB_FRONT_TRY(sb::dev_take(P.bytes, &M->arena, &M->arena_cap));
+      M->d_mass = (double *)(M->arena + P.mass);
+      M->d_left_off = (int64_t *)(M->arena + P.loff);
+      M->d_right_off = (int64_t *)(M->arena + P.roff);
+      M->d_left_left = (uint32_t *)(M->arena + P.ll), M->d_left_right = (uint32_t *)(M->arena + P.lr);
+      M->d_right_left = (uint32_t *)(M->arena + P.rl), M->d_right_right = (uint32_t *)(M->arena + P.rr);
+      M->d_left_code = (uint8_t *)(M->arena + P.lc), M->d_right_code = (uint8_t *)(M->arena + P.rc);
+      sb::MateArgs &a = f.a;
+      a.pair_mass = M->d_mass;
+      a.left_off = M->d_left_off, a.right_off = M->d_right_off;
+      a.left_code = M->d_left_code, a.right_code = M->d_right_code;
+      a.left_left = M->d_left_left, a.left_right = M->d_left_right;
+      a.right_left = M->d_right_left, a.right_right = M->d_right_right;
+      hipLaunchKernelGGL(sb::flat_mate_fill_kernel, dim3(sb::xcd_grid((int64_t)(((size_t)M->n_pairs + 1 + 255) / 256))), dim3(256), 0, s, f, M->n_pairs);
+      SB_FRONT_TRY(hipGetLastError());
+      SB_FRONT_TRY(hipStreamSynchronize(s));
+      return SBGPU_OK;
+   }
+
+   int run(const sb::FrontHooks &hooks)
+   {
+      SB_FRONT_TRY(hipSetDevice(M->device));
+      if (n_loci > ((int64_t)1 << 23)) return api_fail(SBGPU_EUNSUPPORTED, "sbgpu_pair_mates_device: more than 2^23 clusters in one call; split the call");
+      SB_FRONT_RC(lay_out());
+      bool sorted = hooks.pair_force_sort;
+      if (!sorted) {
+         SB_FRONT_RC(positional_form());
+         sorted = trouble != 0;
+      }
+      M->positional = !sorted;
+      M->why_sorted = trouble;
+      if (sorted) SB_FRONT_RC(sorted_form());
+      SB_FRONT_RC(sum_totals());
+      return fill();
+   }
+};
+} // namespace
+
+static int pair_mates_flat(int64_t n_loci, const sbgpu_reads_t *dr, const int64_t *locus_read_off, hipStream_t s, sbgpu_matepairs *M)
+{
+   if (dr->n_reads >= ((int64_t)1 << 31) - 2) return api_fail(SBGPU_EUNSUPPORTED, "sbgpu_pair_mates_device: more than 2^31 records in one call; split the call or use sbgpu_pair_mates_host");
+   return PairMatesCall{n_loci, dr, locus_read_off, s, M}.run(sb::front_hooks_from_env());
 }
+
 
 extern "C" {
 
@@ -376,23 +354,15 @@ int sbgpu_pair_mates_device(sbgpu_ctx_t *c, int64_t n_loci, const sbgpu_reads_t 
    for (int64_t l = 0; l < n_loci; ++l)
       if (locus_read_off[l + 1] < locus_read_off[l]) return api_fail(SBGPU_EINVAL, "sbgpu_pair_mates_device: locus_read_off must ascend");
    hipStream_t s = (hipStream_t)stream;
-   sbgpu_matepairs *M = new (std::nothrow) sbgpu_matepairs();
+   sb::MatePairsHandle M(new (std::nothrow) sbgpu_matepairs());
    if (!M) return api_fail(SBGPU_ENOMEM, "sbgpu_pair_mates_device: out of host memory");
    M->on_device = true;
    M->device = sb::ctx_device(c);
    M->n_loci = n_loci;
    M->locus_pair_off.assign((size_t)n_loci + 1, 0);
-   if (nr == 0 || n_loci == 0) {
-      *out = M;
-      return SBGPU_OK;
-   }
    // every cluster of the call at once (matepair_flat.h)
-   const int rc = pair_mates_flat(c, n_loci, dr, locus_read_off, s, M);
-   if (rc != SBGPU_OK) {
-      sbgpu_matepairs_destroy(M);
-      return rc;
-   }
-   *out = M;
+   if (nr != 0 && n_loci != 0) SB_FRONT_RC(pair_mates_flat(n_loci, dr, locus_read_off, s, M.get()));
+   *out = M.release();
    return SBGPU_OK;
 }
 
@@ -461,24 +431,15 @@ int sbgpu_assign_reads_device(sbgpu_ctx_t *c, const sbgpu_clusters_t *cl, int64_
    hipStream_t s = (hipStream_t)stream;
    char *w = nullptr;
    const size_t nc1 = (size_t)nc + 1;
-   size_t t = 0;
-   const size_t o_ref = t; t += up256(nc1 * 4);
-   const size_t o_left = t; t += up256(nc1 * 4);
-   const size_t o_right = t; t += up256(nc1 * 4);
-   const size_t o_strand = t; t += up256(nc1);
-   const size_t o_ub = t; t += up256(nc1 * 8);
-   const size_t o_pos = t; t += up256(nc1 * 8);
-   hipError_t e = sb::ctx_scratch(c, 5, t, &w);
+   sb::Arena arena;
+   const size_t o_ref = arena.take(nc1 * 4), o_left = arena.take(nc1 * 4), o_right = arena.take(nc1 * 4), o_strand = arena.take(nc1), o_ub = arena.take(nc1 * 8),
+                o_pos = arena.take(nc1 * 8);
+   hipError_t e = sb::ctx_scratch(c, 5, arena.size, &w);
    if (e != hipSuccess) return sb::api_fail_hip(e, "hipMalloc");
-#define SB_TRY(expr)                                                                                        \
-   do {                                                                                                     \
-      hipError_t e_ = (expr);                                                                               \
-      if (e_ != hipSuccess) return api_fail(SBGPU_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-   } while (0)
-   SB_TRY(hipMemcpyAsync(w + o_ref, cl->ref, (size_t)nc * 4, hipMemcpyHostToDevice, s));
-   SB_TRY(hipMemcpyAsync(w + o_left, cl->left, (size_t)nc * 4, hipMemcpyHostToDevice, s));
-   SB_TRY(hipMemcpyAsync(w + o_right, cl->right, (size_t)nc * 4, hipMemcpyHostToDevice, s));
-   SB_TRY(hipMemcpyAsync(w + o_strand, cl->strand, (size_t)nc, hipMemcpyHostToDevice, s));
+   SB_FRONT_TRY(hipMemcpyAsync(w + o_ref, cl->ref, (size_t)nc * 4, hipMemcpyHostToDevice, s));
+   SB_FRONT_TRY(hipMemcpyAsync(w + o_left, cl->left, (size_t)nc * 4, hipMemcpyHostToDevice, s));
+   SB_FRONT_TRY(hipMemcpyAsync(w + o_right, cl->right, (size_t)nc * 4, hipMemcpyHostToDevice, s));
+   SB_FRONT_TRY(hipMemcpyAsync(w + o_strand, cl->strand, (size_t)nc, hipMemcpyHostToDevice, s));
    sb::AssignArgs a = {};
    a.n_clusters = nc, a.n_reads = n_reads;
    a.c_ref = (const int32_t *)(w + o_ref);
@@ -489,17 +450,16 @@ int sbgpu_assign_reads_device(sbgpu_ctx_t *c, const sbgpu_clusters_t *cl, int64_
    a.pos = (const int64_t *)(w + o_pos);
    a.read_cluster = d_read_cluster;
    hipLaunchKernelGGL(sb::cluster_bounds_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, a);
-   SB_TRY(hipGetLastError());
+   SB_FRONT_TRY(hipGetLastError());
    std::vector<int64_t> ub((size_t)nc);
-   SB_TRY(hipMemcpyAsync(ub.data(), w + o_ub, (size_t)nc * 8, hipMemcpyDeviceToHost, s));
-   SB_TRY(hipStreamSynchronize(s));
+   SB_FRONT_TRY(hipMemcpyAsync(ub.data(), w + o_ub, (size_t)nc * 8, hipMemcpyDeviceToHost, s));
+   SB_FRONT_TRY(hipStreamSynchronize(s));
    for (int64_t k = 0; k < nc; ++k) off[k + 1] = std::max(off[k], ub[(size_t)k]); // the pass never goes back
-   SB_TRY(hipMemcpyAsync(w + o_pos, off, nc1 * 8, hipMemcpyHostToDevice, s));
+   SB_FRONT_TRY(hipMemcpyAsync(w + o_pos, off, nc1 * 8, hipMemcpyHostToDevice, s));
    const int64_t blocks = std::min<int64_t>((n_reads + 255) / 256, (int64_t)sb::ctx_cu_count(c) * 32);
    hipLaunchKernelGGL(sb::assign_reads_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
-   SB_TRY(hipGetLastError());
-   SB_TRY(hipStreamSynchronize(s)); // (`off` was read from host memory)
-#undef SB_TRY
+   SB_FRONT_TRY(hipGetLastError());
+   SB_FRONT_TRY(hipStreamSynchronize(s)); // (`off` was read from host memory)
    return SBGPU_OK;
 }
 

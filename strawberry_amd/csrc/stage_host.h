@@ -39,15 +39,19 @@ inline std::vector<HitItem> build_hit_items(const int64_t *locus_hit_off, int64_
    return items;
 }
 
-// One device block cut into arrays that begin at multiples of 256 bytes, in the order they are taken
+// One device block cut into arrays that begin at multiples of 256 bytes, in the order they are taken (csrc's one rounding and
+// one arena helper: the chain's, the bootstrap's and the front end's layouts use them too)
+inline size_t up256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 struct Arena {
    size_t size = 0;
    size_t take(size_t bytes)
    {
       const size_t at = size;
-      size += (bytes + 255) & ~(size_t)255;
+      size += up256(bytes);
       return at;
    }
+   // an array that keeps a place of its own even when it is empty (the front end's arenas, the chain's uploads)
+   size_t take_nonempty(size_t bytes) { return take(bytes ? bytes : 8); }
 };
 inline size_t at_least_1(int64_t n) { return (size_t)std::max<int64_t>(n, 1); }
 
