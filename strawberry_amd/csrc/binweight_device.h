@@ -97,8 +97,10 @@ __device__ __forceinline__ int effective_len(SegPtr s, const int *SL, const int 
    // covers kR(i) inner segments from the right (as long as rl - bp_last exceeds their running
    // length) and the left mate kL(i) from the left (as long as rl - i does).  kR is
    // non-decreasing and kL non-increasing in i, so every condition is an interval of i and the
-   // count is interval arithmetic on the prefix sums SL / SR -- identical to the scan
-   // (checked against the reference on 180 000 cases), O(segments) instead of O(s_last*segments).
+   // count is interval arithmetic on the prefix sums SL / SR -- identical to the scan, O(segments)
+   // instead of O(s_last*segments).  tests/test_binweight_edges_gpu.py holds this kernel to the scan,
+   // integer for integer, on some 215 000 (pair, fl, rl) cases at 1..32 segments (a one-point density
+   // makes a pair's weight its effective length); tests/test_binweight_oracle.py the scan to the reference.
    const int ni = nseg - 2;
    if ((imask & 1u) || ((imask >> (nseg - 1)) & 1u)) return 0; // ends are never implicit
    const int B = fl - inner;

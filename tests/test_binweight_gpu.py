@@ -100,6 +100,9 @@ def test_binweight_vs_oracle_wide_sweep(ctx, oracle):
         w = bin_weights(seg_off, seg_lens, mask, lens, InsertSize(mean, sd), rl, ctx=ctx)
         ins = oracle.make_insert(mean, sd)
         ref = np.array([oracle.bin_weight(s, i, L, rl, ins) for s, i, L in zip(segs, imps, lens)])
+        # inner segments of up to 349 bases: from about 8 segments on nearly every reference weight is 0 (the widths are
+        # compared on weights that are not in tests/test_binweight_edges_gpu.py); what is left must not shrink further
+        assert (ref != 0).mean() >= 0.25, float((ref != 0).mean())
         check(w, ref, 1e-11)
 
 

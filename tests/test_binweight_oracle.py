@@ -68,6 +68,21 @@ def test_effective_len_vs_reference(oracle, reflib):
             assert a == b, (segs, imp, fl, rl, a, b)
             n += 1
     assert n > 5000
+    # the widths the GPU tests lean on (tests/test_binweight_edges_gpu.py): 1..32 segments, inner segments short enough for
+    # a fragment to span them, one contiguous implicit block or none or a split set; every fragment length of every pair's
+    # range, at both read lengths of that sample
+    import binweight_util as U
+    n, nonzero = 0, np.zeros(33, np.int64)
+    for segs, imp in zip(*U.exact_sample()):
+        for rl in U.EXACT_RLS:
+            lo, hi = U.fl_range(segs, rl)
+            for fl in range(lo, hi + 1):
+                a = oracle.effective_len(segs, imp, fl, rl)
+                b = reflib.effective_len(segs, imp, fl, rl)
+                assert a == b, (segs, imp, fl, rl, a, b)
+                n += 1
+                nonzero[len(segs)] += b != 0
+    assert n > 200000 and nonzero[1:].min() >= 50, (n, nonzero)
 
 
 def test_insert_pdf_vs_reference(oracle, reflib):
