@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "device_common.h"
+#include "em_row_scatter.h"
 
 namespace sb {
 
@@ -555,6 +556,52 @@ __device__ __forceinline__ void row_lanes_sum(float (&x)[NVAL], int lbGR)
 #undef SB_STEP
 }
 
+// Block form, fp64: reduce-scatter of a lane's S per-column values over the row lanes of its wave (em_row_scatter.h has
+// the index math and the slot order this relies on; col_lanes_scatter is the same exchange for rows over column lanes).
+// Each step adds the partner's copy of the kept slots -- no select -- then the row-lane bits below 4 that are not
+// scattered are all-reduced on the S / 2^L values left and bits 4 and 5 by one matrix instruction each (sum_bits45):
+// S / 2^L matrix instructions where the all-reduce (row_lanes_sum) takes 2 S, and the last exchange moves one value
+// where every butterfly step moves S.  Afterwards the slots s = 0, P, 2P, ... of a lane hold the wave's total of their
+// column in every lane that rs_lane_stores() names; the other slots hold partial sums of no further use.
+template <int BIT>
+__device__ __forceinline__ double rs_xor(double x) // x of the partner across lane bit BIT (0 .. 3)
+{
+   if constexpr (BIT == 2) return __hiloint2double(xor4_get_i(__double2hiint(x)), xor4_get_i(__double2loint(x)));
+   else return xor_get<(1 << BIT)>(x);
+}
+template <int T_, int S, int LB_CL>
+__device__ __forceinline__ void row_scatter_step(double (&x)[S])
+{
+   if constexpr (T_ < rs_steps(S, LB_CL)) {
+      constexpr int D = rs_step_distance(S, LB_CL, T_);
+#pragma unroll
+      for (int s = 0; s < S; ++s)
+         if (rs_step_keeps(S, LB_CL, T_, s)) x[s] += rs_xor<rs_scatter_bit(LB_CL, T_)>(x[s + D]);
+   }
+}
+template <int S, int LB_CL>
+__device__ __forceinline__ void row_lanes_scatter(double (&x)[S])
+{
+   static_assert(LB_CL <= 3 && rs_steps(S, LB_CL) >= 1 && rs_steps(S, LB_CL) <= 3, "at least one scatter step");
+   row_scatter_step<0, S, LB_CL>(x);
+   row_scatter_step<1, S, LB_CL>(x);
+   row_scatter_step<2, S, LB_CL>(x);
+   constexpr int kRest = rs_rest_mask(S, LB_CL);
+#pragma unroll
+   for (int s = 0; s < S; ++s) {
+      if (!rs_slot_remains(S, LB_CL, s)) continue;
+      if (kRest & 2) x[s] += rs_xor<1>(x[s]);
+      if ((kRest & 12) == 12) {
+         x[s] += row_ror8(x[s]);
+         x[s] += row_ror4(x[s]); // symmetric under the rotation by 8 by now: this adds the xor-4 partner's pair
+      } else if (kRest & 4) {
+         x[s] += rs_xor<2>(x[s]);
+      }
+      static_assert((kRest & 12) != 8 && !(kRest & 1), "bit 3 is all-reduced only together with bit 2; bit 0 always scatters");
+      x[s] = sum_bits45(x[s]);
+   }
+}
+
 #ifdef SB_STAMPS
 // Diagnostic build only (make stamps): per-wave cycle stamps, never compiled into the
 // product library.  [wave][8] = {start, after class lookup, first refill done, end,
@@ -581,6 +628,7 @@ hipError_t read_stamps_block_tall(void *out, size_t bytes);
 __device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
 
 constexpr int kBlockWaves = 4; // block form: 256 lanes, one wave per SIMD, up to 512 VGPRs each
+constexpr bool kRowScatterTall = false; // the row-lane reduce-scatter in the tall block kernel too (see em_tile_body: kRowScat)
 
 // Block form, tiles of R = 4 or 6 rows: f(ru_tag) with the rows the current locus uses (workgroup-uniform) as a
 // compile-time constant, 2..R.  A locus of one row runs the two-row loop: its second row is an unused row's zeros.
@@ -641,6 +689,18 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
    // inside) and the passes that run once per locus skip by row.  The taller tiles and the fp32 variant skip the rows a
    // locus does not use in blocks of four.
    constexpr bool kRowsCT = BLOCK && std::is_same<T, double>::value && R <= 6;
+   // Block form, fp64, 6 or 8 column slots (the kernel's switch runs 5 and 7 columns per lane on them): the per-column sums
+   // over the row lanes are reduce-scattered inside the wave (row_lanes_scatter) instead of all-reduced -- the LDS round
+   // that follows hands every lane every column's wave partials anyway.  The column slots of a lane then sit in the
+   // lane's own order: slot jj holds column gc * CPL + slot_col(jj), set once as the tile is loaded, for F, theta, nt and
+   // scale alike.  The tall tile keeps the all-reduce (kRowScatterTall): with the exchange its even layouts spill 47 VGPRs
+   // into 192 bytes of scratch against 43 and 176, and its odd layouts cannot move to an even slot count -- their tiles
+   // hold more rows than the next even count's (profiles/EXPERIMENTS_r12.md).
+   constexpr bool kRowScat = BLOCK && std::is_same<T, double>::value && (CPL == 6 || CPL == 8) && (R <= 6 || kRowScatterTall);
+   const int rs_p = kRowScat ? rs_perm(CPL, LB_CL, lane) : 0;
+   const int rs_key = kRowScat ? rs_lane_key(rs_p, gc, CL) : 0;
+   const bool rs_store = kRowScat && rs_lane_stores(CPL, LB_CL, lane);
+   auto slot_col = [&](int jj) -> int { return kRowScat ? rs_slot_column(jj, rs_p) : jj; };
 #ifdef SB_STAMPS
    unsigned long long st_refill = 0, st_events = 0, st_first = 0, st_batches = 0, st_iters = 0, st_t = 0;
 #endif
@@ -652,6 +712,46 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
       constexpr int NVAL = decltype(nval_tag)::value;
       constexpr int LBC = decltype(lb_tag)::value;
       const int lb = LBC >= 0 ? LBC : lbGR;
+      if constexpr (kRowScat && NVAL == NV) {
+         // the per-column values: reduce-scatter inside the wave, one store per remaining value by the lanes that own a
+         // column's wave total, and after the barrier each slot reads the NW partials of the column it holds -- every
+         // lane of a column lane adds the same NW numbers in wave order, so the sums stay bitwise identical across them
+         // (these rounds lay a phase out as [wave][column][column lane], rs_lds_index: what a wave reads for one slot is
+         // then consecutive in LDS; the same elements, the same phase size as the layout below)
+         row_lanes_scatter<NV, LB_MM>(x);
+         T *buf = s_red + (size_t)phase * (NV * CL * NW);
+         // (the key goes through an empty asm, as the lane id does: the slots' LDS addresses are then formed where they
+         // are used, one instruction each, instead of being kept in eight registers across the loop -- which the base
+         // tile's 256 do not have)
+         int key = rs_key;
+         asm volatile("" : "+v"(key));
+         if (rs_store) {
+#pragma unroll
+            for (int v = 0; v < NV; ++v)
+               if (rs_slot_remains(NV, LB_MM, v)) buf[rs_read_index(v, key, CL) + wave_id * rs_wave_stride(NV, CL)] = x[v];
+         }
+         __syncthreads();
+         constexpr int kChunk = 2; // (as below: a few values' partials in flight at a time; four at a time measured the same)
+#pragma unroll
+         for (int v0 = 0; v0 < NV; v0 += kChunk) {
+            T part[kChunk][NW];
+#pragma unroll
+            for (int u = 0; u < kChunk; ++u) {
+               const T *p = buf + rs_read_index(v0 + u, key, CL);
+#pragma unroll
+               for (int w = 0; w < NW; ++w) part[u][w] = p[w * rs_wave_stride(NV, CL)];
+            }
+#pragma unroll
+            for (int u = 0; u < kChunk; ++u) {
+               T sum = part[u][0];
+#pragma unroll
+               for (int w = 1; w < NW; ++w) sum += part[u][w];
+               x[v0 + u] = sum;
+            }
+         }
+         phase ^= 1;
+         return;
+      }
       if constexpr (HIMAP) top_bits_sum<NVAL>(x, lb);
       else row_lanes_sum<LB_MM, NVAL>(x, lb);
       if (BLOCK) {
@@ -811,7 +911,7 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
             T mx = T(0);
 #pragma unroll
             for (int jj = 0; jj < CPL; ++jj) {
-               const int j = gc * CPL + jj;
+               const int j = gc * CPL + slot_col(jj);
                const int jc = (j < ni) ? j : ni - 1;
                T x = T(0);
                if (nrow > 0) x = Fg[(int64_t)ic * ni + jc];
@@ -822,7 +922,7 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
                const T rb = a.row_bias[r0 + ic];
 #pragma unroll
                for (int jj = 0; jj < CPL; ++jj) {
-                  const int j = gc * CPL + jj;
+                  const int j = gc * CPL + slot_col(jj);
                   const int jc = (j < ni) ? j : ni - 1;
                   v[jj] *= bias_factor(rb * a.iso_bias[ib + jc]);
                }
@@ -876,7 +976,7 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
          theta0 = red[0] / (T)ni; // :375, IEEE division
 #pragma unroll
          for (int jj = 0; jj < CPL; ++jj) {
-            theta[jj] = (gc * CPL + jj < ni) ? theta0 : T(0);
+            theta[jj] = (gc * CPL + slot_col(jj) < ni) ? theta0 : T(0);
             scale[jj] = T(1);
          }
          it = 0;
@@ -890,7 +990,7 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
             it = __builtin_amdgcn_readfirstlane(got ? a.iters[loc] : 0);
 #pragma unroll
             for (int jj = 0; jj < CPL; ++jj)
-               theta[jj] = (gc * CPL + jj < ni) ? a.theta[ib + gc * CPL + jj] : T(0);
+               theta[jj] = (gc * CPL + slot_col(jj) < ni) ? a.theta[ib + gc * CPL + slot_col(jj)] : T(0);
             column_scale();
             normalise_tile(true);
          }
@@ -904,7 +1004,7 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
             if (gr == 0) {
 #pragma unroll
                for (int jj = 0; jj < CPL; ++jj)
-                  if (gc * CPL + jj < ni) a.theta[ib + gc * CPL + jj] = theta0;
+                  if (gc * CPL + slot_col(jj) < ni) a.theta[ib + gc * CPL + slot_col(jj)] = theta0;
             }
          }
          have = got && !empty;
@@ -1032,12 +1132,36 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
          }
          row_lane_sum(acc, std::integral_constant<int, NV>(), lb_tag);
          T p2 = T(0);
+         if constexpr (kRowScat) {
+            // The row lanes of a column lane hold its columns in different slot orders and must still agree on this sum
+            // bit for bit (the stop decision is workgroup-uniform): the squares are added as a balanced tree inside each
+            // aligned block of P = 2^L slots -- a lane's order is the column order xor-ed with a number below P, which
+            // only swaps the operands of the tree's additions -- and the blocks, which every lane holds in column order,
+            // one after the other.
+            constexpr int P = 1 << rs_steps(CPL, LB_MM);
+            T sq[CPL];
+#pragma unroll
+            for (int jj = 0; jj < CPL; ++jj) {
+               const T t = tin[jj] * acc[jj]; // next_theta_j = sum_i U_ij, :454-464
+               const T df = t - tin[jj];
+               sq[jj] = df * df; // :479
+               tout[jj] = t;
+            }
+#pragma unroll
+            for (int w = 1; w < P; w *= 2) {
+#pragma unroll
+               for (int jj = 0; jj < CPL; jj += 2 * w) sq[jj] += sq[jj + w];
+            }
+#pragma unroll
+            for (int jj = 0; jj < CPL; jj += P) p2 = (jj == 0) ? sq[0] : p2 + sq[jj];
+         } else {
 #pragma unroll
          for (int jj = 0; jj < CPL; ++jj) {
             const T t = tin[jj] * acc[jj]; // next_theta_j = sum_i U_ij, :454-464
             const T df = t - tin[jj];
             p2 = fma_t(df, df, p2); // :479
             tout[jj] = t;
+         }
          }
          const T d2 = col_sum(p2);
          // ||next - theta||_2 < 1e-2 (:479-480) tested on the square: kThetaLimitSq is the largest T whose
@@ -1179,7 +1303,7 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
             if (gr == 0) {
 #pragma unroll
                for (int jj = 0; jj < CPL; ++jj)
-                  if (gc * CPL + jj < niso) a.theta[iso_base + gc * CPL + jj] = theta[jj];
+                  if (gc * CPL + slot_col(jj) < niso) a.theta[iso_base + gc * CPL + slot_col(jj)] = theta[jj];
             }
             have = false;
          }
@@ -1206,6 +1330,8 @@ __device__ __forceinline__ void em_tile_body(const EmArgsT<T> &a, const ClassArg
 // instantiation.  `shape` packs (column-layout index, rows-per-lane multiplier,
 // log2 lanes per group).
 constexpr int kLayouts = 6; // (CPL, CL): (2,1) (4,1) (8,1) (8,2) (8,4) (8,8)
+// column slots of the instantiation that serves a class of cpl columns per lane (even_slots: see em_fused_kernel)
+constexpr int block_slots(int cpl, bool even_slots) { return (even_slots && (cpl == 5 || cpl == 7)) ? cpl + 1 : cpl; }
 
 // class of workgroup b: the last descriptor whose first block is <= b (wave-uniform binary search; empty classes
 // share their successor's first block and are skipped that way)
@@ -1299,10 +1425,20 @@ __global__ __launch_bounds__(NWAVES > 0 ? 64 * NWAVES : 64,
    // layout = (CPL - 1) + 8 * log2(CL): exact columns per lane (no padding to a power of two),
    // CL = 1 for up to 8 isoforms, else 2 / 4 / 8 column lanes of 5..8 columns each.
    // Rows per row lane: RH halves of the base height (16, 8, 8, 8, 6, 6, 4, 4 for CPL = 1..8).
+   // Block form, fp64, base tile: the classes of 5 and 7 columns per lane run the 6- and 8-slot instantiations (column
+   // lane gc then owns columns [S gc, S gc + S); the slots past the locus' last column hold F = 0 and theta = 0 like any
+   // column beyond it), so that every layout has an even slot count for the row-lane reduce-scatter -- and the kernel
+   // half as many bodies.  The plan and its shape codes know nothing of this: the tile is as tall for 6 as for 5 and for
+   // 8 as for 7.  (Not the tall tile: there the odd counts hold more rows.)
 #define SB_BODY(CPLV, CLV, RHALF)                                                                  \
-   case (CPLV - 1) + 8 * ilog2(CLV):                                                               \
-      em_tile_body<T, CPLV, CLV, tile_rows(CPLV, RHALF, RH), NWAVES>(a, cls, lbG, s_red);          \
-      break;
+   case (CPLV - 1) + 8 * ilog2(CLV): {                                                             \
+      constexpr int kSlots = block_slots(CPLV, NWAVES > 0 && std::is_same<T, double>::value && RH <= 2); \
+      static_assert(tile_rows(kSlots, RHALF, RH) == tile_rows(CPLV, RHALF, RH), "the plan's rows"); \
+      if constexpr (kSlots == CPLV) {                                                              \
+         em_tile_body<T, CPLV, CLV, tile_rows(CPLV, RHALF, RH), NWAVES>(a, cls, lbG, s_red);       \
+         break;                                                                                    \
+      }                                                                                            \
+   } /* else: falls through to the next case, the even count of the same column lanes */
    switch (layout) {
       SB_BODY(1, 1, 8)
       SB_BODY(2, 1, 4)
