@@ -1480,6 +1480,151 @@ int sbgpu_model_diff_device(sbgpu_ctx_t *ctx_a, const sbgpu_bins_t *bins_a, sbgp
  * of a workgroup; [6] workgroups per CU a launch's grid is capped at; [7] the default scratch budget in bytes.              */
 int sbgpu_em_diff_limits(int64_t out[8]);
 
+/* ---- differential isoform usage between two GROUPS of replicate samples -------------------------------------
+ * A one-sample against one-sample likelihood ratio has no estimate of biological variation: two samples whose shares were
+ * drawn independently reject almost every locus.  Experiments come as two conditions with a few replicates each, and the
+ * question is whether usage differs between the conditions by MORE than it differs among replicates.  The pooled-solve rule
+ * above generalises: a pool of P samples gives every sample 1/P of each column's mass.  The rule (csrc/gdiff_rules.h, shared by
+ * both forms, compiled under -ffp-contract=off):
+ * Group A holds n_a >= 1 batches and group B n_b >= 1; S = n_a + n_b <= SBGPU_GDIFF_MAX_SAMPLES (anything else, 0 samples in a
+ * group included, is SBGPU_EINVAL).  All batches are over one annotation: the same n_loci and identical iso_off, else
+ * SBGPU_EINVAL; each has its own row_off, f_off, count, F and optional keep.  Samples are numbered A's first, in the caller's
+ * order.  Every sum starts from its first term and adds in ascending index.
+ *    1. kept(j) = kept in ANY sample (loo_kept's bit per sample; a NULL keep keeps everything); K = the kept isoforms of the
+ *       locus.  Sample s is PRESENT at a locus when it has at least one bin there (nb_s > 0): decided from offsets alone.  p_a
+ *       and p_b are the present samples of the two groups.  gdiff_status[l] before the solves, tested in this order:
+ *       SBGPU_DIFF_EMPTY when K = 0; SBGPU_DIFF_SOLE when K = 1: no solve, both statistics 0.0, both dofs 0, usage 1.0 for
+ *       the kept isoform in every present sample that placed a fragment (a count > 0), in every group one of whose samples
+ *       did, and in ALL where any did, 0.0 otherwise; SBGPU_DIFF_TOO_WIDE when K > SBGPU_DIFF_MAX_KEPT;
+ *       SBGPU_GDIFF_ONE_GROUP when p_a = 0 or p_b = 0; SBGPU_DIFF_TOO_DEEP when the present samples' bins together exceed
+ *       SBGPU_DIFF_MAX_POOLED_BINS; SBGPU_DIFF_OK otherwise.  These are statuses, not refusals of the call.  A single sample's
+ *       locus beyond the fit's limits (5632 bins, 4096 isoforms) refuses the call with SBGPU_ESHAPE, as the fit does.
+ *    2. The sub-problems of an OK locus, in this order, numbered consecutively over the call (a sub-batch): one OWN
+ *       sub-problem per present sample, in sample order -- the kept columns compacted, row-major; GROUP_A, if p_a >= 2 -- A's
+ *       present samples' rows stacked in sample order, scaled by rule 3; GROUP_B, if p_b >= 2; ALL -- every present sample's
+ *       rows, A's then B's, scaled.  A group with ONE present sample has no group sub-problem: its group theta, status and
+ *       group-level fit ARE that sample's own -- the same numbers, not a second solve.
+ *    3. Row liveness (asg_row_live on the kept weights) and c^s_j are exactly rule 3 of the two-sample test.  For a pool P of
+ *       present samples, alpha^{s,P}_j = ((sum over t in P of c^t_j) / c^s_j) / (double)|P| where c^s_j != 0, and 1.0 otherwise:
+ *       the sum first, in ascending sample order, then the quotient, then the division.  At |P| = 2 this is the two-sample
+ *       alpha bit for bit.  Why: the EM renormalises every column over the live rows, so with alpha every column puts 1/|P| of
+ *       its mass in each sample of the pool, the responsibilities are those of the samples' own column-normalised models, the
+ *       M-step sums all their fragments, and the stacked solve is the joint MLE under one theta -- the two-sample argument.
+ *    4. Every sub-problem is solved inside the call as sbgpu_em_run_device solves any locus.  Three fits run over the
+ *       sub-batch with nothing erased: OWN -- every sub-problem at its own theta and status; GROUP cross -- every OWN
+ *       sub-problem at its group's theta and status; ALL cross -- every OWN sub-problem at ALL's theta and status.
+ *    5. For a present sample s let own_s = ll_s(theta_s), grp_s = ll_s(theta_g(s)), all_s = ll_s(theta_ALL).
+ *       lr_between = 2.0 * sum_s (grp_s - all_s), dof_between = K - 1: what the groups lose when they must share one theta.
+ *       lr_within = 2.0 * sum_s (own_s - grp_s), dof_within = (p_a + p_b - 2)(K - 1): what the replicates lose when each
+ *       group shares one -- the estimate of biological variation, on the same scale.  Each loss is one subtraction, the sum
+ *       runs over the present samples in order, there is one product.  A singleton group's samples contribute exactly 0.0 to
+ *       lr_within.  Both are reported raw: every solve stops at SBGPU_EM_THETA_CHANGE_LIMIT, so small negatives are real.
+ *    6. Integers, exact: n_frag[s] = n_live - n_impossible of s's own fit.  With lost(.) = n_dropped + n_impossible,
+ *       lost_shift = (lost(ALL) - sum_s lost(s)) + sum over the groups with a sub-problem (lost(G) - sum_{s in G} lost(s))
+ *       + sum_s (lost(s at its group's theta) - lost(s)) + sum_s (lost(s at ALL's theta) - lost(s)).  At 1 + 1 samples this is
+ *       the two-sample expression.
+ *    7. After the solves an OK locus becomes SBGPU_GDIFF_THIN when a present sample has n_frag = 0 or its solve ended
+ *       SBGPU_EM_INIT_EMPTY; otherwise SBGPU_DIFF_UNSOLVED when any solve of the locus ended SBGPU_EM_DENOM_ZERO.  For a status
+ *       other than OK or SOLE every double of the locus and of its isoforms is 0.0, n_frag, lost_shift and the dofs are 0,
+ *       top_iso is -1.  p_a and p_b are always reported.  The statuses and iteration counts of the sub-problems are STILL
+ *       REPORTED where sub-problems existed (a singleton group's are its sample's), and are -1 where none existed and for an
+ *       absent sample.
+ *    8. Per isoform: theta_sample [S x n_iso], sample-major, 0.0 for an absent sample; theta_group [2 x n_iso]; theta_all
+ *       [n_iso]; the usages likewise, each theta over the ascending sum of its sub-problem's theta (0.0 where that is 0);
+ *       delta_usage = usage_group[B] - usage_group[A].
+ *    9. Per locus: the two statistics and dofs, p_a, p_b, loglik_own, loglik_group, loglik_all and n_frag [S x n_loci]
+ *       (sample-major), lost_shift, the final status, top_iso -- the two-sample rule 9 on the two GROUP usages, with the same
+ *       K = 2 remark --, status_sample / iters_sample [S x n_loci], status_group / iters_group [2 x n_loci], status_all /
+ *       iters_all [n_loci].
+ * THE ANCHOR.  With n_a = n_b = 1 and both samples present at a locus the sub-batch is the two-sample A, B, POOLED in the same
+ * order; lr_between, every theta, usage, log-likelihood, integer and top_iso are sbgpu_em_diff_device's bits; lr_within is 0.0
+ * and dof_within 0.  Where a sample is absent the two-sample rule says ONE_SAMPLE and this one ONE_GROUP; where a present
+ * sample placed nothing, ONE_SAMPLE there is THIN here.
+ * p-values are the caller's (strawberry_amd/gdiff.py: chi-squared on lr_between, or the quasi-likelihood F test
+ * F = (lr_between / dof_between) / max(1, lr_within / dof_within) on (dof_between, dof_within) degrees of freedom).  The CAVEAT
+ * of the two-sample rule holds per sample: each is tested on the bins it observed.  Out of this rule: more than two groups, an
+ * N-way merge onto one bin table (shared_bins for groups), multiple-testing correction, warm starts, multi-rank wiring, columns
+ * in the parity writers.
+ * The struct: host arrays to fill (any may be NULL) and, on return -- device forms only -- the device arrays of all of them:
+ * the (first) context's memory, in a scratch slot of their own, valid until that context's next sbgpu_quantify_* or gdiff call. */
+#define SBGPU_GDIFF_MAX_SAMPLES 16
+#define SBGPU_GDIFF_ONE_GROUP 7
+#define SBGPU_GDIFF_THIN 8
+#define SBGPU_GDIFF_KIND_OWN 0
+#define SBGPU_GDIFF_KIND_GROUP_A 1
+#define SBGPU_GDIFF_KIND_GROUP_B 2
+#define SBGPU_GDIFF_KIND_ALL 3
+typedef struct {
+   double *theta_sample, *theta_group, *theta_all, *usage_sample, *usage_group, *usage_all, *delta_usage; /* in: [S | 2 | 1 x n_iso] */
+   double *lr_between, *lr_within, *loglik_own, *loglik_group, *loglik_all;                                /* in: [n_loci]; loglik_*: [S x n_loci] */
+   int64_t *n_frag, *lost_shift;                                                                           /* in: [S x n_loci], [n_loci] */
+   int32_t *dof_between, *dof_within, *p_a, *p_b, *gdiff_status, *top_iso;                                 /* in: [n_loci] */
+   int32_t *status_sample, *iters_sample, *status_group, *iters_group, *status_all, *iters_all;           /* in: [S | 2 | 1 x n_loci] */
+   const double *d_theta_sample, *d_theta_group, *d_theta_all, *d_usage_sample, *d_usage_group, *d_usage_all, *d_delta_usage; /* out: device forms only */
+   const double *d_lr_between, *d_lr_within, *d_loglik_own, *d_loglik_group, *d_loglik_all;
+   const int64_t *d_n_frag, *d_lost_shift;
+   const int32_t *d_dof_between, *d_dof_within, *d_p_a, *d_p_b, *d_gdiff_status, *d_top_iso;
+   const int32_t *d_status_sample, *d_iters_sample, *d_status_group, *d_iters_group, *d_status_all, *d_iters_all;
+   int32_t *sub_count;                          /* in, device forms only: [sizes[1]] and [sizes[3]] of the shapes call, or NULL: the */
+   double *sub_F;                               /* expanded sub-batch, for a caller that checks it */
+} sbgpu_em_gdiff_t;
+typedef struct {
+   int64_t max_bytes; /* device scratch one chunk of sub-problems may take; 0: 1 GiB.  Any positive value is legal: consecutive
+                         whole loci form a chunk, and a locus above the budget is a chunk alone */
+   int64_t reserved;  /* 0 */
+} sbgpu_gdiff_params_t;
+/* Host form (csrc/gdiff_host.cpp; no GPU needed, free of HIP) in three calls around a solver the caller brings, as the
+ * two-sample one: the caller solves the sub-batch between the second and the third and fits it three times
+ * (sbgpu_em_fit_host: own, group cross, ALL cross; rule 4).  Samples are given as arrays of S = n_a + n_b pointers, A's first.
+ * Shapes (rules 1, 2): row_off [S] pointers to [n_loci + 1] arrays; keep [S] pointers to [n_iso] arrays, any of them or the
+ * array itself NULL.  sizes[4] = the sub-problems, their bins, isoforms and weights together -- always filled; every other
+ * output may be NULL: gdiff_status [n_loci] (before the solves); sub_locus, sub_kind (SBGPU_GDIFF_KIND_*), sub_sample (-1 for a
+ * group's and ALL's) [sizes[0]]; sub_row_off, sub_iso_off, sub_f_off [sizes[0] + 1].  SBGPU_EINVAL: the group sizes, NULL
+ * offsets, n_loci < 0, offsets that do not begin at 0 or do not ascend; SBGPU_ESHAPE: rule 1.                              */
+int sbgpu_em_gdiff_shapes_host(int64_t n_loci, int32_t n_a, int32_t n_b, const int64_t *const *row_off, const int64_t *iso_off,
+                               const int32_t *const *keep, int64_t sizes[4], int32_t *gdiff_status, int32_t *sub_locus, int32_t *sub_kind,
+                               int32_t *sub_sample, int64_t *sub_row_off, int64_t *sub_iso_off, int64_t *sub_f_off);
+/* Expansion (rules 2, 3): the sub-batch's counts [sizes[1]] and weights [sizes[3]].  Refusals as sbgpu_em_fit_host's for each
+ * batch; SBGPU_EINVAL also where the batches' n_loci or iso_off differ.                                                    */
+int sbgpu_em_gdiff_expand_host(int32_t n_a, int32_t n_b, const sbgpu_batch_t *const *batches, const int32_t *const *keep, int32_t *sub_count,
+                               double *sub_F);
+/* Statistics (rules 5-9) from the sub-batch's solve -- sub_theta [sizes[2]], sub_status, sub_iters [sizes[0]] --, its own fit --
+ * own_loglik, own_n_live, own_n_dropped, own_n_impossible [sizes[0]] -- and its two cross fits -- group_* and all_*: loglik,
+ * n_dropped, n_impossible [sizes[0]]; only the OWN sub-problems' entries of the cross arrays are read.  Of the batches the
+ * offsets and the counts are read (F may be NULL).  SBGPU_EINVAL: a NULL input, malformed or differing offsets.            */
+int sbgpu_em_gdiff_stat_host(int32_t n_a, int32_t n_b, const sbgpu_batch_t *const *batches, const int32_t *const *keep, const double *sub_theta,
+                             const int32_t *sub_status, const int32_t *sub_iters, const double *own_loglik, const int64_t *own_n_live,
+                             const int64_t *own_n_dropped, const int64_t *own_n_impossible, const double *group_loglik,
+                             const int64_t *group_n_dropped, const int64_t *group_n_impossible, const double *all_loglik,
+                             const int64_t *all_n_dropped, const int64_t *all_n_impossible, sbgpu_em_gdiff_t *out);
+/* Device form (csrc/gdiff_device.h) for S batches sbgpu_em_run_device solves, all on ctx's device: plans, d_count, d_F: host
+ * arrays of S entries, each as given to it; d_keep: a host array of S device [n_iso] arrays (any NULL), or NULL; params: NULL
+ * for the defaults.  The keeps are read back once (the shapes are made on the host, by the function the host form calls); the
+ * samples' arrays reach the kernels through a small device table indexed by sample, not through kernel arguments.  Per chunk
+ * of consecutive whole loci: a plan for the chunk's sub-batch, gdiff_colscale_kernel (rule 3's live rows, c, the pools' sums
+ * and the two alphas), gdiff_expand_kernel (a workgroup per row tile of one sample; a weight is loaded once and stored up to
+ * three times: bitwise the host expansion), the EM through sbgpu_em_run_device, gdiff_cross_kernel and the fit's launches for
+ * the group level, the same for ALL, the own fit, gdiff_stat_kernel, one synchronisation.  No atomics.  Every integer, every
+ * status and -- given the same solves and fits -- every double are the host form's.  Only the arrays the caller gave pointers
+ * for cross PCIe.  Synchronises on `stream` (NULL: the context's own).  SBGPU_ESHAPE: rule 1; SBGPU_EINVAL: a NULL argument,
+ * the group sizes, plans that differ in n_loci or iso_off, counts or weights that are not on the device, a negative max_bytes. */
+int sbgpu_em_gdiff_device(sbgpu_ctx_t *ctx, int32_t n_a, int32_t n_b, const sbgpu_plan_t *const *plans, const int32_t *const *d_count,
+                          const double *const *d_F, const int32_t *const *d_keep, const sbgpu_gdiff_params_t *params, void *stream,
+                          sbgpu_em_gdiff_t *out);
+/* The same from what S contexts' resident calls (or sbgpu_front_stream_end) kept with sbgpu_bootstrap_keep on: sample s is
+ * ctxs[s]'s record; each handle is checked against its context's record as sbgpu_model_loo_device checks one.  All contexts
+ * must be on one device (SBGPU_EINVAL otherwise); every other context's own stream is synchronised before its arrays are read;
+ * the work, the sub-batch's plan and the scratch are the first context's.  No record changes: every call's seven results are
+ * the same bits with and without it, and every other stage still answers on every context, in any order.                   */
+int sbgpu_model_gdiff_device(int32_t n_a, int32_t n_b, sbgpu_ctx_t *const *ctxs, const sbgpu_bins_t *const *bins, const int32_t *const *d_keep,
+                             const sbgpu_gdiff_params_t *params, void *stream, sbgpu_em_gdiff_t *out);
+/* The thresholds (csrc/gdiff_rules.h, csrc/gdiff_device.h; the two-sample kernels' shapes are kept): out[0] the most kept
+ * isoforms of a tested locus; [1] the most bins of the present samples together; [2] weights of one row tile of the expand
+ * kernel, [3] the most rows of one tile; [4] kept isoforms up to which the column-scale kernel serves a locus with a group of
+ * lanes; [5] threads of a workgroup; [6] workgroups per CU a launch's grid is capped at; [7] the default scratch budget in
+ * bytes; [8] the most samples of a call.                                                                                    */
+int sbgpu_em_gdiff_limits(int64_t out[9]);
+
 /* ---- two samples on ONE bin table: the merge of two bin tables by key ---------------------------------------
  * The differential usage above conditions each sample on the bins it observed.  The merge gives both samples the union of their
  * bins, with zero counts where a sample saw nothing, so that the unchanged rule above tests them on one bin set.  The rule

@@ -1147,6 +1147,103 @@ class DifferentialUsage {
    }
 };
 
+/* Differential isoform usage between two GROUPS of replicate samples (sbgpu_em_gdiff_device / sbgpu_model_gdiff_device,
+ * include/sbgpu.h): per locus lr_between ("one theta for all" against "a theta per group") and lr_within ("a theta
+ * per group" against "a theta per sample") with their degrees of freedom, per isoform the thetas and usages of every sample, of
+ * the two groups and of all, and the groups' usage difference.  Samples are numbered group A's first; a per-sample array is
+ * sample-major ([S x n_iso] or [S x n_loci]), a per-group one [2 x ...].  device(): for S batches (plans) of one annotation, or
+ * right after S resident calls on S contexts of one device (bins).  p-values are the caller's.                              */
+class GroupDifferentialUsage {
+ public:
+   int32_t n_a = 0, n_b = 0;
+   std::vector<double> theta_sample, theta_group, theta_all, usage_sample, usage_group, usage_all, delta_usage;
+   std::vector<double> lr_between, lr_within, loglik_own, loglik_group, loglik_all;
+   std::vector<int64_t> n_frag, lost_shift;
+   std::vector<int32_t> dof_between, dof_within, p_a, p_b, gdiff_status, top_iso, status_sample, iters_sample, status_group, iters_group, status_all,
+      iters_all;
+   sbgpu_em_gdiff_t raw{}; /* the device arrays -- the (first) context's, valid until its next quantify or gdiff call; its host
+                              pointers are null after the call */
+
+   /* plans, d_count, d_F: n_a + n_b entries, group A's first; d_keep: as many (any null), or empty: everything kept */
+   static GroupDifferentialUsage device(const Context &ctx, int32_t n_a, int32_t n_b, const std::vector<const sbgpu_plan_t *> &plans,
+                                        const std::vector<const int32_t *> &d_count, const std::vector<const double *> &d_F,
+                                        const std::vector<const int32_t *> &d_keep = {}, int64_t max_bytes = 0, void *stream = nullptr)
+   {
+      const size_t S = (size_t)(n_a + n_b);
+      if (n_a < 1 || n_b < 1 || plans.size() != S || d_count.size() != S || d_F.size() != S || (!d_keep.empty() && d_keep.size() != S))
+         throw std::runtime_error("GroupDifferentialUsage::device: one plan, d_count and d_F per sample, at least one sample per group");
+      int64_t info[8];
+      check(sbgpu_plan_info(plans[0], info), "sbgpu_plan_info");
+      GroupDifferentialUsage t;
+      t.prepare(n_a, n_b, info[0], info[2]);
+      const sbgpu_gdiff_params_t par{max_bytes, 0};
+      check(sbgpu_em_gdiff_device(ctx.get(), n_a, n_b, plans.data(), d_count.data(), d_F.data(), d_keep.empty() ? nullptr : d_keep.data(), &par, stream,
+                                  &t.raw),
+            "sbgpu_em_gdiff_device");
+      t.done();
+      return t;
+   }
+   static GroupDifferentialUsage device(int32_t n_a, int32_t n_b, const std::vector<const Context *> &ctxs, const std::vector<const sbgpu_bins_t *> &bins,
+                                        const std::vector<const int32_t *> &d_keep = {}, int64_t max_bytes = 0, void *stream = nullptr)
+   {
+      const size_t S = (size_t)(n_a + n_b);
+      if (n_a < 1 || n_b < 1 || ctxs.size() != S || bins.size() != S || (!d_keep.empty() && d_keep.size() != S))
+         throw std::runtime_error("GroupDifferentialUsage::device: one context and one handle per sample, at least one sample per group");
+      std::vector<sbgpu_ctx_t *> raw_ctx;
+      for (const Context *c : ctxs) raw_ctx.push_back(c ? c->get() : nullptr);
+      int64_t info[8];
+      check(sbgpu_bins_info(bins[0], info), "sbgpu_bins_info");
+      GroupDifferentialUsage t;
+      t.prepare(n_a, n_b, info[0], info[1]);
+      const sbgpu_gdiff_params_t par{max_bytes, 0};
+      check(sbgpu_model_gdiff_device(n_a, n_b, raw_ctx.data(), bins.data(), d_keep.empty() ? nullptr : d_keep.data(), &par, stream, &t.raw),
+            "sbgpu_model_gdiff_device");
+      t.done();
+      return t;
+   }
+
+   /* (public for a caller that fills raw through the host form's three calls) */
+   void prepare(int32_t groups_a, int32_t groups_b, int64_t n_loci, int64_t n_iso)
+   {
+      n_a = groups_a, n_b = groups_b;
+      const size_t S = (size_t)(n_a + n_b), nl = (size_t)n_loci, ni = (size_t)n_iso; /* (one spare entry each: data() of an empty vector may be null) */
+      for (std::vector<double> *v : {&theta_sample, &usage_sample}) v->assign(S * ni + 1, 0.0);
+      for (std::vector<double> *v : {&theta_group, &usage_group}) v->assign(2 * ni + 1, 0.0);
+      for (std::vector<double> *v : {&theta_all, &usage_all, &delta_usage}) v->assign(ni + 1, 0.0);
+      for (std::vector<double> *v : {&lr_between, &lr_within}) v->assign(nl + 1, 0.0);
+      for (std::vector<double> *v : {&loglik_own, &loglik_group, &loglik_all}) v->assign(S * nl + 1, 0.0);
+      n_frag.assign(S * nl + 1, 0), lost_shift.assign(nl + 1, 0);
+      for (std::vector<int32_t> *v : {&dof_between, &dof_within, &p_a, &p_b, &gdiff_status, &top_iso, &status_all, &iters_all}) v->assign(nl + 1, 0);
+      for (std::vector<int32_t> *v : {&status_sample, &iters_sample}) v->assign(S * nl + 1, 0);
+      for (std::vector<int32_t> *v : {&status_group, &iters_group}) v->assign(2 * nl + 1, 0);
+      raw = sbgpu_em_gdiff_t{};
+      raw.theta_sample = theta_sample.data(), raw.theta_group = theta_group.data(), raw.theta_all = theta_all.data();
+      raw.usage_sample = usage_sample.data(), raw.usage_group = usage_group.data(), raw.usage_all = usage_all.data(), raw.delta_usage = delta_usage.data();
+      raw.lr_between = lr_between.data(), raw.lr_within = lr_within.data();
+      raw.loglik_own = loglik_own.data(), raw.loglik_group = loglik_group.data(), raw.loglik_all = loglik_all.data();
+      raw.n_frag = n_frag.data(), raw.lost_shift = lost_shift.data();
+      raw.dof_between = dof_between.data(), raw.dof_within = dof_within.data(), raw.p_a = p_a.data(), raw.p_b = p_b.data();
+      raw.gdiff_status = gdiff_status.data(), raw.top_iso = top_iso.data();
+      raw.status_sample = status_sample.data(), raw.iters_sample = iters_sample.data(), raw.status_group = status_group.data();
+      raw.iters_group = iters_group.data(), raw.status_all = status_all.data(), raw.iters_all = iters_all.data();
+   }
+   void done()
+   {
+      raw.theta_sample = raw.theta_group = raw.theta_all = raw.usage_sample = raw.usage_group = raw.usage_all = raw.delta_usage = nullptr;
+      raw.lr_between = raw.lr_within = raw.loglik_own = raw.loglik_group = raw.loglik_all = nullptr;
+      raw.n_frag = raw.lost_shift = nullptr;
+      raw.dof_between = raw.dof_within = raw.p_a = raw.p_b = raw.gdiff_status = raw.top_iso = nullptr;
+      raw.status_sample = raw.iters_sample = raw.status_group = raw.iters_group = raw.status_all = raw.iters_all = nullptr;
+      for (std::vector<double> *v : {&theta_sample, &theta_group, &theta_all, &usage_sample, &usage_group, &usage_all, &delta_usage, &lr_between, &lr_within,
+                                     &loglik_own, &loglik_group, &loglik_all})
+         v->pop_back();
+      for (std::vector<int64_t> *v : {&n_frag, &lost_shift}) v->pop_back();
+      for (std::vector<int32_t> *v : {&dof_between, &dof_within, &p_a, &p_b, &gdiff_status, &top_iso, &status_sample, &iters_sample, &status_group,
+                                      &iters_group, &status_all, &iters_all})
+         v->pop_back();
+   }
+};
+
 /* The bootstrap of the resident path (sbgpu_bootstrap_keep / sbgpu_abundance_bootstrap_device, include/sbgpu.h): FPKM and TPM
  * mean, variance and percentile interval over resampled bin counts, with the replicates in which the expression filter kept
  * each isoform.  keep(): before the resident call; device(): right after it, on that call's handle.  interval_ranks(): the two

@@ -53,6 +53,8 @@ SYMBOLS = [
     "sbgpu_model_loo_device", "sbgpu_em_loo_limits",
     "sbgpu_em_diff_shapes_host", "sbgpu_em_diff_expand_host", "sbgpu_em_diff_stat_host", "sbgpu_em_diff_device", "sbgpu_model_diff_device",
     "sbgpu_em_diff_limits",
+    "sbgpu_em_gdiff_shapes_host", "sbgpu_em_gdiff_expand_host", "sbgpu_em_gdiff_stat_host", "sbgpu_em_gdiff_device", "sbgpu_model_gdiff_device",
+    "sbgpu_em_gdiff_limits",
     "sbgpu_bins_merge_shapes_host", "sbgpu_bins_merge_fill_host", "sbgpu_bins_merge_device", "sbgpu_bins_merge_fetch", "sbgpu_bins_merge_limits",
     "sbgpu_model_diff_merged_device",
     "sbgpu_body_profile_host", "sbgpu_body_profile_device", "sbgpu_body_profile_limits",
@@ -214,6 +216,17 @@ class sbgpu_em_diff_t(C.Structure):
 
 
 class sbgpu_diff_params_t(C.Structure):
+    _fields_ = [("max_bytes", C.c_int64), ("reserved", C.c_int64)]
+
+
+class sbgpu_em_gdiff_t(C.Structure):
+    _NAMES = ("theta_sample", "theta_group", "theta_all", "usage_sample", "usage_group", "usage_all", "delta_usage", "lr_between", "lr_within",
+              "loglik_own", "loglik_group", "loglik_all", "n_frag", "lost_shift", "dof_between", "dof_within", "p_a", "p_b", "gdiff_status", "top_iso",
+              "status_sample", "iters_sample", "status_group", "iters_group", "status_all", "iters_all")
+    _fields_ = [(n, C.c_void_p) for n in _NAMES] + [("d_" + n, C.c_void_p) for n in _NAMES] + [("sub_count", C.c_void_p), ("sub_F", C.c_void_p)]
+
+
+class sbgpu_gdiff_params_t(C.Structure):
     _fields_ = [("max_bytes", C.c_int64), ("reserved", C.c_int64)]
 
 
@@ -435,6 +448,12 @@ def load():
     L.sbgpu_em_diff_device.argtypes = [vp] * 9 + [C.POINTER(sbgpu_diff_params_t), vp, C.POINTER(sbgpu_em_diff_t)]
     L.sbgpu_model_diff_device.argtypes = [vp] * 6 + [C.POINTER(sbgpu_diff_params_t), vp, C.POINTER(sbgpu_em_diff_t)]
     L.sbgpu_em_diff_limits.argtypes = [C.POINTER(C.c_int64)]
+    L.sbgpu_em_gdiff_shapes_host.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, C.POINTER(C.c_int64)] + [vp] * 7
+    L.sbgpu_em_gdiff_expand_host.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp]
+    L.sbgpu_em_gdiff_stat_host.argtypes = [C.c_int32, C.c_int32] + [vp] * 15 + [C.POINTER(sbgpu_em_gdiff_t)]
+    L.sbgpu_em_gdiff_device.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.POINTER(sbgpu_gdiff_params_t), vp, C.POINTER(sbgpu_em_gdiff_t)]
+    L.sbgpu_model_gdiff_device.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, C.POINTER(sbgpu_gdiff_params_t), vp, C.POINTER(sbgpu_em_gdiff_t)]
+    L.sbgpu_em_gdiff_limits.argtypes = [C.POINTER(C.c_int64)]
     ms, mg = C.POINTER(sbgpu_merge_sample_t), C.POINTER(sbgpu_bins_merged_t)
     L.sbgpu_bins_merge_shapes_host.argtypes = [ms, ms, C.POINTER(C.c_int64), vp, vp, vp, vp]
     L.sbgpu_bins_merge_fill_host.argtypes = [ms, ms, vp, vp, vp, vp]

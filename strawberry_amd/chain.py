@@ -24,9 +24,11 @@ class DeviceSample:
     """Annotation (host arrays, it is small) + hits on the device."""
 
     def __init__(self, torch, dev, n_loci=60000, n_frags=2e8, seed=31, read_len=75, mean=250.0, sd=30.0, noise=0.10,
-                 loci_subset=None, sample_seed=None):
+                 loci_subset=None, sample_seed=None, replicate=None):
         """sample_seed: another SAMPLE of the same annotation -- the expression shares, the per-locus depths and the fragments'
         generator draw from it, the annotation still comes from `seed` (None: everything from `seed`).
+        replicate: a REPLICATE of that sample -- the same shares and depths (the numpy draws still come from seed / sample_seed),
+        independent fragments: only the fragments' generator takes the replicate number (None: today's bits).
         loci_subset: (rank, world) -- keep only this rank's share of the SAME sample's loci (strong scaling:
         every rank draws the same annotation and the same per-locus fragment counts, then generates its own loci's
         fragments only)."""
@@ -68,7 +70,7 @@ class DeviceSample:
         share[last] = 1.0
         up = lambda x, dt=None: torch.from_numpy(np.ascontiguousarray(x if dt is None else x.astype(dt))).to(dev)  # noqa: E731
         g = torch.Generator(device=dev)
-        g.manual_seed(draw * 7919 + (0 if loci_subset is None else 1 + loci_subset[0]))
+        g.manual_seed(draw * 7919 + (0 if loci_subset is None else 1 + loci_subset[0]) + (0 if replicate is None else 104729 * (1 + int(replicate))))
         n = int(per_locus.sum())
         d_locus = torch.repeat_interleave(torch.arange(n_loci, device=dev, dtype=torch.int32), up(per_locus))
         # isoform of each fragment: first isoform of the locus whose cumulative share reaches u
@@ -225,7 +227,7 @@ class ChainQuantifier:
     then FPKM / TPM on the host arrays the call returns (the caller's own epilogue, as in the reference)."""
 
     def __init__(self, ctx, n_loci=60000, n_frags=2e8, seed=31, read_len=75, loci_subset=None, pin=True, resident=False,
-                 empirical=False, comm=None, min_isoform_frac=0.0, keep_context=False, keep_bootstrap=False, sample_seed=None):
+                 empirical=False, comm=None, min_isoform_frac=0.0, keep_context=False, keep_bootstrap=False, sample_seed=None, replicate=None):
         """resident=True: step() is sbgpu_quantify_resident -- the chain with the reference's pass 1 in front (empirical=True: no
         insert-size law is given, the device builds it from the hits; Strawberry's default mode) and the FPKM / Frac / TPM
         epilogue behind it, the collectives over `comm` (dist.AbiComm / dist.HostComm; None: a world of one) inside the call;
@@ -239,11 +241,13 @@ class ChainQuantifier:
         last step's handle, model_fit() the model fit (fit.model_fit_device) and isoform_information() the isoform information
         (info.model_info_device) and isoform_support() the drop-one support (support.model_loo_device), which work from the same
         retention; differential_usage(other) compares this object's last step with another quantifier's (diff.model_diff_device).
-        sample_seed: DeviceSample's -- another sample of the annotation `seed` draws."""
+        differential_usage_groups(group_a, group_b) compares two groups of such quantifiers (gdiff.model_gdiff_device).
+        sample_seed: DeviceSample's -- another sample of the annotation `seed` draws; replicate: DeviceSample's -- the same sample's
+        shares and depths with independent fragments."""
         import torch
         self.torch, self.ctx = torch, ctx
         self.dev = torch.device("cuda", ctx.device)
-        self.sample = DeviceSample(torch, self.dev, n_loci, n_frags, seed, read_len, loci_subset=loci_subset, sample_seed=sample_seed)
+        self.sample = DeviceSample(torch, self.dev, n_loci, n_frags, seed, read_len, loci_subset=loci_subset, sample_seed=sample_seed, replicate=replicate)
         self.annot, self.hits = self.sample.annot, self.sample
         self.insert = InsertSize(250.0, 30.0)
         self.read_len = read_len
@@ -441,6 +445,22 @@ class ChainQuantifier:
         return diff.model_diff_device(self.ctx, self.context_handle, other.ctx, other.context_handle, int(self._out.d_keep), int(other._out.d_keep),
                                       keep_a=self.keep[:self.n_iso], keep_b=other.keep[:other.n_iso], max_bytes=max_bytes, want=want,
                                       with_sub_batch=with_sub_batch)
+
+    @staticmethod
+    def differential_usage_groups(group_a, group_b, max_bytes=0, want=None, with_sub_batch=False):
+        """Differential isoform usage between two GROUPS of replicate samples: group_a and group_b are lists of quantifiers whose
+        last steps were made with keep_bootstrap=True over the same annotation, on contexts of one device (together at most 16):
+        gdiff.model_gdiff_device on their handles with the steps' keeps -> a gdiff.GroupDifferentialUsage (lr_between against
+        lr_within: does usage differ between the groups by more than among the replicates?).  No object's results change; the
+        work is done on the first quantifier's context.  max_bytes, want, with_sub_batch: as differential_usage's."""
+        from . import gdiff
+        qs = list(group_a) + list(group_b)
+        for q in qs:
+            if q.context_handle is None or not q.keep_bootstrap:
+                raise _lib.SbgpuError("differential_usage_groups: no step has run with keep_bootstrap=True")
+        pairs = [(q.ctx, q.context_handle) for q in qs]
+        return gdiff.model_gdiff_device(pairs[:len(group_a)], pairs[len(group_a):], [int(q._out.d_keep) for q in qs],
+                                        keeps=[q.keep[:q.n_iso] for q in qs], max_bytes=max_bytes, want=want, with_sub_batch=with_sub_batch)
 
     def splice_psi(self, events=None, bootstrap=None, coverage=None):
         """The PSI of every annotated exon and intron for the last resident step (splice.SplicePsi), built on the device from the

@@ -296,6 +296,74 @@ inline DiffChunkLayout diff_chunk_layout(int64_t n_tiles, int64_t n_items, int64
    return L;
 }
 
+// The differential usage between two groups of replicates: as DiffLayout -- the whole call's results and what
+// the host makes of its shapes, then, behind `chunk`, one chunk's working set.  A per-sample array is sample-major with a
+// stride of exactly n_iso or n_loci (the caller's layout); S: the samples, slots = S + 3 (the samples, the two groups, ALL).
+struct GdiffSample {
+   const int64_t *row_off, *f_off; // one sample's arrays in HBM: the kernels index a device table of these by sample
+   const int32_t *count;
+   const double *F;
+};
+struct GdiffLayout {
+   size_t lstat, p_a, p_b, rank, koff, kcol, slot, table, upload_bytes; // made on the host
+   size_t th_s, th_g, th_all, us_s, us_g, us_all, delta;                // per isoform
+   size_t lr_b, lr_w, ll_own, ll_grp, ll_all, n_frag, shift;            // per locus
+   size_t dof_b, dof_w, status, top, st_s, it_s, st_g, it_g, st_all, it_all;
+   size_t sum;                                                          // [slots x n_loci]: the statistics' first launch's notes for its second
+   size_t chunk, bytes;
+};
+inline GdiffLayout gdiff_layout(int S, int64_t n_loci, int64_t n_iso, int64_t n_kept, size_t chunk_bytes)
+{
+   const size_t nl1 = (size_t)n_loci + 1, ni1 = (size_t)n_iso + 1, s = (size_t)S, sl = s * (size_t)n_loci + 1, si = s * (size_t)n_iso + 1;
+   Arena a;
+   GdiffLayout L;
+   L.lstat = a.take(nl1 * 4), L.p_a = a.take(nl1 * 4), L.p_b = a.take(nl1 * 4), L.rank = a.take(ni1 * 4), L.koff = a.take(nl1 * 8);
+   L.kcol = a.take(at_least_1(n_kept) * 4), L.slot = a.take(((s + 3) * (size_t)n_loci + 1) * 8), L.table = a.take(s * sizeof(GdiffSample));
+   L.upload_bytes = a.size;
+   L.th_s = a.take(si * 8), L.th_g = a.take((2 * (size_t)n_iso + 1) * 8), L.th_all = a.take(ni1 * 8);
+   L.us_s = a.take(si * 8), L.us_g = a.take((2 * (size_t)n_iso + 1) * 8), L.us_all = a.take(ni1 * 8), L.delta = a.take(ni1 * 8);
+   L.lr_b = a.take(nl1 * 8), L.lr_w = a.take(nl1 * 8), L.ll_own = a.take(sl * 8), L.ll_grp = a.take(sl * 8), L.ll_all = a.take(sl * 8);
+   L.n_frag = a.take(sl * 8), L.shift = a.take(nl1 * 8);
+   L.dof_b = a.take(nl1 * 4), L.dof_w = a.take(nl1 * 4), L.status = a.take(nl1 * 4), L.top = a.take(nl1 * 4);
+   L.st_s = a.take(sl * 4), L.it_s = a.take(sl * 4), L.st_g = a.take((2 * (size_t)n_loci + 1) * 4), L.it_g = a.take((2 * (size_t)n_loci + 1) * 4);
+   L.st_all = a.take(nl1 * 4), L.it_all = a.take(nl1 * 4);
+   L.sum = a.take(((s + 3) * (size_t)n_loci + 1) * 8);
+   L.chunk = a.take(chunk_bytes);
+   L.bytes = a.size;
+   return L;
+}
+struct GdiffTile {
+   int32_t locus, sample, row0, rows; // rows [row0, row0 + rows) of the locus in one sample
+   int32_t own_q, grp_q, all_q;       // the chunk's sub-problems the rows go to; grp_q -1: the sample's group has none
+   int32_t grp_row0, all_row0;        // the sample's first row inside the stacked sub-problems: the earlier present samples' bins
+   int32_t pad[3];
+};
+struct GdiffScaleItem {
+   int32_t first, n, lanes, rows; // as DiffScaleItem; rows: the most bins of one sample among the item's loci
+   int32_t mask, pad[3];          // bit s: sample s is present at one of the item's loci
+};
+struct GdiffChunkLayout {
+   size_t tiles, items, list, src_g, src_a, upload_bytes;
+   size_t c, alpha_g, alpha_a, count, F, theta, status, iters, g_theta, g_status, a_theta, a_status, fit, g_fit, a_fit, bytes;
+};
+inline GdiffChunkLayout gdiff_chunk_layout(int S, int64_t n_tiles, int64_t n_items, int64_t n_list, int64_t n_kept, int64_t n_sub, int64_t sub_rows,
+                                           int64_t sub_iso, int64_t sub_elem, size_t fit_bytes)
+{
+   Arena a;
+   GdiffChunkLayout L;
+   L.tiles = a.take(at_least_1(n_tiles) * sizeof(GdiffTile)), L.items = a.take(at_least_1(n_items) * sizeof(GdiffScaleItem));
+   L.list = a.take(at_least_1(n_list) * 4), L.src_g = a.take(at_least_1(n_sub) * 4), L.src_a = a.take(at_least_1(n_sub) * 4);
+   L.upload_bytes = a.size;
+   L.c = a.take(at_least_1(S * n_kept) * 8), L.alpha_g = a.take(at_least_1(S * n_kept) * 8), L.alpha_a = a.take(at_least_1(S * n_kept) * 8);
+   L.count = a.take(at_least_1(sub_rows) * 4), L.F = a.take(at_least_1(sub_elem) * 8), L.theta = a.take(at_least_1(sub_iso) * 8);
+   L.status = a.take(at_least_1(n_sub) * 4), L.iters = a.take(at_least_1(n_sub) * 4);
+   L.g_theta = a.take(at_least_1(sub_iso) * 8), L.g_status = a.take(at_least_1(n_sub) * 4);
+   L.a_theta = a.take(at_least_1(sub_iso) * 8), L.a_status = a.take(at_least_1(n_sub) * 4);
+   L.fit = a.take(fit_bytes), L.g_fit = a.take(fit_bytes), L.a_fit = a.take(fit_bytes);
+   L.bytes = a.size;
+   return L;
+}
+
 // The bin-table merge.  Its match works in a block of its own (the union's size is only known behind it, and a
 // context's scratch slot loses its contents when it grows); the merged arrays, which outlive the call, are the slot's.
 struct MergeItem {
