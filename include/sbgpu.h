@@ -2091,6 +2091,81 @@ int sbgpu_splice_support_device(sbgpu_ctx_t *ctx, const sbgpu_splice_events_t *d
  * test the extents and walk the list, row by row); out[1]: events of one workgroup, one thread each (the grid is not capped). */
 int sbgpu_splice_limits(int64_t out[2]);
 
+/* ---- variational Bayes: a Dirichlet prior on the isoform shares --------------------------------------------
+ * A second, independent solver over the batch layout of sbgpu_em_run_device, for the loci whose likelihood is flat in some
+ * direction: a symmetric Dirichlet(alpha) prior on the isoform shares and the mean-field posterior q(share) = Dirichlet(alpha +
+ * c).  With alpha < 1 it empties the isoforms the data do not need; it gives a posterior spread per isoform and an evidence bound
+ * (ELBO) per locus.  It calls none of the EM kernels and is NOT a parity path: the reference has no such solve.  The rule
+ * (csrc/vb_rules.h, shared by both forms, compiled under -ffp-contract=off, every fused operation written as fma).  One locus:
+ * bins i with counts n_i (int32 >= 0), isoforms j = 0..K-1, raw weights F[i][j], and alpha, change_limit, max_iter.
+ *    1. A bin is LIVE if some F[i][j] > SBGPU_EM_ROW_EPS (asg_row_live, the row drop of EmSolver::init).  No live bin: status
+ *       SBGPU_EM_INIT_EMPTY, every output 0, iters 0.
+ *    2. s_j = the sum of F[i][j] over the live bins, ascending; column j is ACTIVE if s_j > 0; K_a = the active columns;
+ *       A[i][j] = F[i][j] / s_j for an active column, 0 otherwise -- from the first iteration on.
+ *    3. N = the integer sum of n_i over the live bins.  Start: c_j = (double)N / K_a for an active j, 0 otherwise.  A locus with
+ *       N = 0 has observed nothing: status SBGPU_EM_OK, iters 1 (its one iteration does not move c), count, share, share_sd and
+ *       elbo 0.
+ *    4. psi(x), x > 0: s = 0; while x < 10: s -= 1/x, x += 1; y = 1/(x x); psi = log x - 0.5/x - y (1/12 - y (1/120 - y (1/252 -
+ *       y (1/240 - y (1/132 - y (691/32760 - y/12)))))) + s.
+ *    5. One iteration: p_j = psi(alpha + c_j) for the active j; m = max p_j; w_j = exp(p_j - m), 0 for an inactive j;
+ *       d_i = sum_j A[i][j] w_j in ascending j, a chain of fma; r_i = (double)n_i / d_i where n_i > 0, 0 where n_i = 0; a live bin
+ *       with n_i > 0 and d_i == 0: status SBGPU_EM_DENOM_ZERO, c stays, the solve ends; c'_j = w_j * (sum_i A[i][j] r_i over the
+ *       live bins in ascending i, a chain of fma); sqrt(sum_j (c'_j - c_j)^2) < change_limit: stop with SBGPU_EM_OK and return c,
+ *       not c'; otherwise c = c'.  After max_iter iterations: SBGPU_EM_MAXITER.  iters = the iterations started.
+ *    6. At the returned c: a0 = K_a alpha + (double)N; lw_j = psi(alpha + c_j) - psi(a0); elbo = sum over the live bins with n_i > 0
+ *       of n_i log(sum_j A[i][j] exp(lw_j)) - [lgamma(a0) - sum_j lgamma(alpha + c_j) - lgamma(K_a alpha) + K_a lgamma(alpha) +
+ *       sum_j c_j lw_j], the sums over the active j; -inf where a counted bin has mixture mass 0.
+ *    7. count[j] = c_j, in fragments: comparable with theta, and a valid d_theta for sbgpu_abundance_device;
+ *       share[j] = (alpha + c_j) / a0 for an active j, 0 otherwise; share_sd[j] = sqrt(a_j (a0 - a_j) / (a0^2 (a0 + 1))) with
+ *       a_j = alpha + c_j: the Dirichlet's standard deviation; n_active[l] = K_a; n_frag[l] = N.
+ * params NULL: alpha = 0.01, change_limit = SBGPU_EM_THETA_CHANGE_LIMIT, max_iter = SBGPU_EM_MAX_ITER.  SBGPU_EINVAL: alpha
+ * outside [1e-6, 1e3], change_limit <= 0, max_iter < 1.  A locus of more than 512 isoforms or more than 5632 bins: SBGPU_ESHAPE.
+ * The struct: host arrays to fill (any may be NULL) and, on return -- device forms only -- the device arrays of all of them: the
+ * context's memory, in a scratch slot of their own, valid until the context's next sbgpu_quantify_* or variational call.     */
+typedef struct {
+   double alpha;         /* the Dirichlet's concentration per isoform */
+   double change_limit;  /* the step norm below which a locus stops, in fragments */
+   int32_t max_iter;
+   int32_t reserved;
+} sbgpu_vb_params_t;
+typedef struct {
+   double *count, *share, *share_sd;                /* in: [n_iso]   */
+   int32_t *status, *iters;                         /* in: [n_loci]  */
+   double *elbo;                                    /* in: [n_loci]  */
+   int32_t *n_active;                               /* in: [n_loci]  */
+   int64_t *n_frag;                                 /* in: [n_loci]  */
+   const double *d_count, *d_share, *d_share_sd;    /* out: device forms only */
+   const int32_t *d_status, *d_iters;
+   const double *d_elbo;
+   const int32_t *d_n_active;
+   const int64_t *d_n_frag;
+} sbgpu_em_vb_t;
+/* Host form (csrc/vb_host.cpp; no GPU needed), the plain statement of the rule: every sum in ascending order.  SBGPU_EINVAL,
+ * with the reason in sbgpu_last_error: a negative count, malformed offsets (not beginning at 0, not ascending, f_off not rows x
+ * isoforms), NULL count / F where there are bins / weights, a parameter out of range.                                     */
+int sbgpu_em_vb_host(const sbgpu_batch_t *batch, const sbgpu_vb_params_t *params, sbgpu_em_vb_t *out);
+/* Device form (csrc/vb_device.h) for any batch sbgpu_em_run_device solves: the plan, d_count and d_F as given to it.  A locus'
+ * normalised weights are made once and stay in LDS while it iterates: a wave per locus of at most out[0] weights of
+ * sbgpu_em_vb_limits, a workgroup per larger locus, which keeps A in LDS up to out[1] and reads a normalised copy in the call's
+ * scratch beyond.  d_i and c'_j are the host form's operation for operation; log, exp and lgamma are the device library's, and
+ * the step norm and the ELBO's sums are added along a fixed tree (csrc/vb_device.h states it): status, n_active, n_frag and
+ * which outputs are zero are the host form's exactly, the rest within the rounding of those differences, the same bits from
+ * call to call and wherever a locus stands in the batch.  Only the arrays the caller gave pointers for cross PCIe.  Synchronises
+ * on `stream` (NULL: the context's own).                                                                                  */
+int sbgpu_em_vb_device(sbgpu_ctx_t *ctx, const sbgpu_plan_t *plan, const int32_t *d_count, const double *d_F,
+                       const sbgpu_vb_params_t *params, void *stream, sbgpu_em_vb_t *out);
+/* The same right after a resident call or an sbgpu_front_stream_end made with sbgpu_bootstrap_keep on, from that record (the
+ * call's plan, counts and weights): nothing more is retained, and the call's seven results are the same bits with and without
+ * a variational call behind it.  A handle made without retention, or a stale one: SBGPU_EINVAL, as for sbgpu_model_fit_device.
+ * It may be asked for in any order with the fit, the support and the other retained-result stages.                         */
+int sbgpu_model_vb_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins, const sbgpu_vb_params_t *params, void *stream, sbgpu_em_vb_t *out);
+/* The device form's thresholds (csrc/vb_device.h), for callers and tests that want a locus on either side of each: out[0]
+ * weights of a locus (bins x isoforms) up to which a wave serves it, a workgroup beyond; [1] doubles of LDS the workgroup form
+ * has for one locus: bins x isoforms + bins + 2 isoforms at most that: A stays in LDS, beyond: in the call's scratch; [2] loci
+ * per workgroup in the wave form; [3] workgroups per CU a launch's grid is capped at; [4] threads of a workgroup; [5] of a wave
+ * (the reduction tree's two levels); [6] the most bins and [7] the most isoforms of one locus.                              */
+int sbgpu_em_vb_limits(int64_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif

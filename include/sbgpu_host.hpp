@@ -891,6 +891,78 @@ class ModelFit {
    }
 };
 
+/* The variational Bayes solve (sbgpu_em_vb_* / sbgpu_model_vb_device, include/sbgpu.h states the rule): under a Dirichlet(alpha)
+ * prior on every locus' isoform shares, the posterior's count, share and its standard deviation per isoform, and status,
+ * iterations, evidence bound, active isoforms and fragments per locus.  host(): any batch; no GPU.  device(plan, ...): for a batch
+ * sbgpu_em_run_device solves, on its device arrays; device(bins, ...): right after a resident call made with
+ * AbundanceBootstrap::keep on, on that call's handle.  params: nullptr = alpha 0.01 and the EM's stopping rule.            */
+class VariationalFit {
+ public:
+   std::vector<double> count, share, share_sd; /* [n_iso] */
+   std::vector<int32_t> status, iters;         /* [n_loci] */
+   std::vector<double> elbo;                   /* [n_loci] */
+   std::vector<int32_t> n_active;              /* [n_loci] */
+   std::vector<int64_t> n_frag;                /* [n_loci] */
+   sbgpu_em_vb_t raw{};   /* device(): the device arrays -- the context's, valid until its next quantify or variational call; its
+                             host pointers are null after the call */
+
+   static VariationalFit host(const sbgpu_batch_t &batch, const sbgpu_vb_params_t *params = nullptr)
+   {
+      if (batch.n_loci < 0 || !batch.iso_off) throw std::invalid_argument("VariationalFit::host: bad n_loci or null offset array");
+      VariationalFit t;
+      t.prepare(batch.n_loci, batch.iso_off[batch.n_loci]);
+      check(sbgpu_em_vb_host(&batch, params, &t.raw), "sbgpu_em_vb_host");
+      t.done();
+      return t;
+   }
+   static VariationalFit device(const Context &ctx, const sbgpu_plan_t *plan, const int32_t *d_count, const double *d_F,
+                                const sbgpu_vb_params_t *params = nullptr, void *stream = nullptr)
+   {
+      int64_t info[8];
+      check(sbgpu_plan_info(plan, info), "sbgpu_plan_info");
+      VariationalFit t;
+      t.prepare(info[0], info[2]);
+      check(sbgpu_em_vb_device(ctx.get(), plan, d_count, d_F, params, stream, &t.raw), "sbgpu_em_vb_device");
+      t.done();
+      return t;
+   }
+   static VariationalFit device(const Context &ctx, const sbgpu_bins_t *bins, const sbgpu_vb_params_t *params = nullptr, void *stream = nullptr)
+   {
+      int64_t info[8];
+      check(sbgpu_bins_info(bins, info), "sbgpu_bins_info");
+      VariationalFit t;
+      t.prepare(info[0], info[1]);
+      check(sbgpu_model_vb_device(ctx.get(), bins, params, stream, &t.raw), "sbgpu_model_vb_device");
+      t.done();
+      return t;
+   }
+   /* the isoforms the posterior leaves at least min_count fragments */
+   std::vector<char> supported(double min_count = 1.0) const
+   {
+      std::vector<char> x(count.size());
+      for (size_t i = 0; i < x.size(); ++i) x[i] = count[i] >= min_count;
+      return x;
+   }
+
+ private:
+   void prepare(int64_t n_loci, int64_t n_iso)
+   {
+      const size_t nl = (size_t)n_loci + 1, ni = (size_t)n_iso + 1; /* (one spare entry: data() of an empty vector may be null) */
+      count.assign(ni, 0.0), share.assign(ni, 0.0), share_sd.assign(ni, 0.0);
+      status.assign(nl, 0), iters.assign(nl, 0), elbo.assign(nl, 0.0), n_active.assign(nl, 0), n_frag.assign(nl, 0);
+      raw = sbgpu_em_vb_t{};
+      raw.count = count.data(), raw.share = share.data(), raw.share_sd = share_sd.data();
+      raw.status = status.data(), raw.iters = iters.data(), raw.elbo = elbo.data(), raw.n_active = n_active.data(), raw.n_frag = n_frag.data();
+   }
+   void done()
+   {
+      raw.count = raw.share = raw.share_sd = raw.elbo = nullptr;
+      raw.status = raw.iters = raw.n_active = nullptr;
+      raw.n_frag = nullptr;
+      count.pop_back(), share.pop_back(), share_sd.pop_back(), status.pop_back(), iters.pop_back(), elbo.pop_back(), n_active.pop_back(), n_frag.pop_back();
+   }
+};
+
 /* The isoform information (sbgpu_em_info_* / sbgpu_model_info_device, include/sbgpu.h states the rule): which isoforms of every
  * locus the counted bins identify, alias or never see, the standard error of theta given the locus' total, the strongest
  * partner of every isoform, and -- packed by cov_off, the upper triangle over a locus' isoforms -- the covariance itself.

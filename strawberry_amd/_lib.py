@@ -60,6 +60,7 @@ SYMBOLS = [
     "sbgpu_body_profile_host", "sbgpu_body_profile_device", "sbgpu_body_profile_limits",
     "sbgpu_splice_events_shapes_host", "sbgpu_splice_events_build_host", "sbgpu_splice_psi_host", "sbgpu_splice_support_host",
     "sbgpu_splice_psi_device", "sbgpu_splice_support_device", "sbgpu_splice_limits",
+    "sbgpu_em_vb_host", "sbgpu_em_vb_device", "sbgpu_model_vb_device", "sbgpu_em_vb_limits",
 ]
 
 
@@ -191,6 +192,15 @@ class sbgpu_splice_events_t(C.Structure):
 class sbgpu_em_fit_t(C.Structure):
     _NAMES = ("expected", "resid", "score", "loglik", "deviance", "pearson", "n_live", "n_dropped", "n_impossible", "dof", "worst_bin")
     _fields_ = [(n, C.c_void_p) for n in _NAMES] + [("d_" + n, C.c_void_p) for n in _NAMES]
+
+
+class sbgpu_em_vb_t(C.Structure):
+    _NAMES = ("count", "share", "share_sd", "status", "iters", "elbo", "n_active", "n_frag")
+    _fields_ = [(n, C.c_void_p) for n in _NAMES] + [("d_" + n, C.c_void_p) for n in _NAMES]
+
+
+class sbgpu_vb_params_t(C.Structure):
+    _fields_ = [("alpha", C.c_double), ("change_limit", C.c_double), ("max_iter", C.c_int32), ("reserved", C.c_int32)]
 
 
 class sbgpu_em_info_t(C.Structure):
@@ -473,6 +483,10 @@ def load():
     L.sbgpu_splice_psi_device.argtypes = [vp, C.POINTER(sbgpu_splice_events_t), C.c_int64, vp, vp, vp, vp, vp]
     L.sbgpu_splice_support_device.argtypes = [vp, C.POINTER(sbgpu_splice_events_t), vp, vp, vp, vp]
     L.sbgpu_splice_limits.argtypes = [C.POINTER(C.c_int64)]
+    L.sbgpu_em_vb_host.argtypes = [C.POINTER(sbgpu_batch_t), C.POINTER(sbgpu_vb_params_t), C.POINTER(sbgpu_em_vb_t)]
+    L.sbgpu_em_vb_device.argtypes = [vp, vp, vp, vp, C.POINTER(sbgpu_vb_params_t), vp, C.POINTER(sbgpu_em_vb_t)]
+    L.sbgpu_model_vb_device.argtypes = [vp, vp, C.POINTER(sbgpu_vb_params_t), vp, C.POINTER(sbgpu_em_vb_t)]
+    L.sbgpu_em_vb_limits.argtypes = [C.POINTER(C.c_int64)]
     L.sbgpu_bootstrap_counts_host.argtypes = [C.c_int64, vp, vp, vp, C.c_uint64, C.c_int32, vp]
     L.sbgpu_bootstrap_counts_device.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp]
     L.sbgpu_em_bootstrap_device.argtypes = [vp, vp, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp, vp, vp, vp, vp, vp]

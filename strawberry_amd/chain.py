@@ -405,6 +405,18 @@ class ChainQuantifier:
         return fit.model_fit_device(self.ctx, self.context_handle, int(self._out.d_theta) if d_theta is None else d_theta,
                                     int(self._out.d_keep), int(self._out.d_status), want=want)
 
+    def variational(self, alpha=None, change_limit=None, max_iter=None, want=None):
+        """The variational Bayes solve of the last step (keep_bootstrap=True: it works from the bootstrap's retention):
+        vb.model_vb_device on its handle -> a vb.VariationalFit, whose abundance() gives FPKM / Frac / TPM under this solve with
+        the step's own epilogue parameters.  The step's results do not change.  None: the library's defaults."""
+        from . import vb
+        if self.context_handle is None or not self.keep_bootstrap:
+            raise _lib.SbgpuError("variational: no step has run with keep_bootstrap=True")
+        par = _lib.sbgpu_abundance_params_t(int(self.total_mapped_reads), self._par.effective_len_norm, self._par.filter_by_expression, 0,
+                                            float(self._used.mean), self._par.min_isoform_frac)
+        return vb.model_vb_device(self.ctx, self.context_handle, alpha=alpha, change_limit=change_limit, max_iter=max_iter, want=want,
+                                  abundance=par)
+
     def isoform_information(self, d_theta=None, want=None):
         """The isoform information of the last step (keep_bootstrap=True: it works from the bootstrap's retention):
         info.model_info_device on its handle under the step's own theta -- or d_theta, a float64 tensor / device address [n_iso]

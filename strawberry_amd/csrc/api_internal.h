@@ -178,10 +178,10 @@ hipStream_t ctx_stream(const sbgpu_ctx_t *ctx); // the context's own stream
 hipStream_t ctx_aux_stream(const sbgpu_ctx_t *ctx, int i); // one of the context's side streams (0..7; the EM's kinds use 0, 1, 2, 6)
 int ctx_cu_count(const sbgpu_ctx_t *ctx);
 int ctx_device(const sbgpu_ctx_t *ctx);        // the HIP device the context was made on
-// device scratch that lives with the context (slot 0..16; grows on demand, never shrinks): valid until the next request for the
+// device scratch that lives with the context (slot 0..18; grows on demand, never shrinks): valid until the next request for the
 // same slot; one host thread per context.  Slots 0..7 are the chain's; the retained-result stages' have names:
-enum ScratchSlot { kScratchContextTable = 8, kScratchAssign = 9, kScratchCoverage = 10, kScratchFit = 11, kScratchInfo = 12, kScratchLoo = 13, kScratchBody = 14, kScratchDiff = 15, kScratchMerge = 16, kScratchGdiff = 17 };
-constexpr int kScratchSlots = 18;
+enum ScratchSlot { kScratchContextTable = 8, kScratchAssign = 9, kScratchCoverage = 10, kScratchFit = 11, kScratchInfo = 12, kScratchLoo = 13, kScratchBody = 14, kScratchDiff = 15, kScratchMerge = 16, kScratchGdiff = 17, kScratchVb = 18 };
+constexpr int kScratchSlots = 19;
 hipError_t ctx_scratch(sbgpu_ctx_t *ctx, int slot, size_t bytes, char **out);
 // Device allocations that change hands (a handle's arenas, a plan's arena): a hipMalloc / hipFree pair per call costs a
 // few hundred microseconds -- seconds for the tens of GB of a sample-sized call -- and the free waits for the device, so

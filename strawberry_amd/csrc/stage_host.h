@@ -172,6 +172,27 @@ inline FitLayout fit_layout(int64_t n_loci, int64_t n_bins, int64_t n_iso, size_
    return L;
 }
 
+// The variational Bayes solve.  norm: the normalised weights of the loci too large for LDS, at the batch's own
+// f_off (n_elem doubles where there is such a locus, none otherwise).
+struct VbLayout {
+   size_t small, large, upload_bytes; // the two lists of loci
+   size_t norm;
+   size_t count, share, sd, status, iters, elbo, nact, nfrag, bytes;
+};
+inline VbLayout vb_layout(int64_t n_loci, int64_t n_iso, int64_t n_norm, size_t n_small, size_t n_large)
+{
+   const size_t nl1 = (size_t)n_loci + 1, ni1 = at_least_1(n_iso);
+   Arena a;
+   VbLayout L;
+   L.small = a.take((n_small + 1) * 4), L.large = a.take((n_large + 1) * 4);
+   L.upload_bytes = a.size;
+   L.norm = a.take((size_t)n_norm * 8);
+   L.count = a.take(ni1 * 8), L.share = a.take(ni1 * 8), L.sd = a.take(ni1 * 8);
+   L.status = a.take(nl1 * 4), L.iters = a.take(nl1 * 4), L.elbo = a.take(nl1 * 8), L.nact = a.take(nl1 * 4), L.nfrag = a.take(nl1 * 8);
+   L.bytes = a.size;
+   return L;
+}
+
 struct InfoLayout {
    size_t small, large, covoff, upload_bytes; // the two lists of loci, the packed covariance's offsets
    size_t keep, status;                       // where the caller gave none

@@ -267,6 +267,19 @@ class EmBatchSolver:
         return fit.em_fit_device(self.ctx, self.plan, self.d_count, self.d_F, self.d_theta if d_theta is None else d_theta, d_keep,
                                  self.d_status if d_status is None else d_status, stream=self._stream(), want=want)
 
+    def run_vb(self, alpha=None, change_limit=None, max_iter=None, want=None, abundance=None):
+        """The variational Bayes solve of the batch (sbgpu_em_vb_device; vb.py): a Dirichlet(alpha) prior on every locus' isoform
+        shares -> the posterior's count, share and share_sd per isoform, status, iters, elbo, n_active and n_frag per locus.
+        None: the library's defaults (alpha 0.01, the EM's change limit and iteration cap).  It needs no run_em and touches none
+        of its results.  abundance: a vb.abundance_params(...) -- the result can then run abundance() with the batch's lengths.
+        Synchronises on torch's current stream -> a vb.VariationalFit of host arrays (want: which)."""
+        from . import vb
+        t = vb.em_vb_device(self.ctx, self.plan, self.d_count, self.d_F, alpha=alpha, change_limit=change_limit, max_iter=max_iter,
+                            stream=self._stream(), want=want)
+        if abundance is not None:
+            t._epilogue = (self.ctx, self.plan, self.d_length, abundance, self.torch, self._stream())
+        return t
+
     def run_info(self, d_theta=None, d_keep=None, d_status=None, want=None):
         """The isoform information of the batch (sbgpu_em_info_device; info.py): which isoforms of every locus the counted bins
         identify, alias or never see, and the analytic covariance of theta, under the last run_em's theta and status -- or

@@ -229,7 +229,7 @@ class BinsHandle:
 def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=False, ctx=None, device=0, comm=None,
                       min_isoform_frac=0.0, filter_by_expression=True, effective_len_norm=False, with_context=False, bootstrap=None,
                       keep_bootstrap=False, keep_handle=False, with_assignment=False, with_coverage=False, with_fit=False, with_info=False,
-                      with_support=False, with_body_profile=False, iso_strand=None, n_pos=20, with_splicing=False):
+                      with_support=False, with_body_profile=False, iso_strand=None, n_pos=20, with_splicing=False, with_variational=False):
     """sbgpu_quantify_resident on host hits brought to the device first (torch owns the copies): pass 1 (insert=None: the
     empirical insert-size law, built on the device), bins, weights, EM, FPKM / Frac / keep, the FPKM all-reduce over `comm`
     (dist.AbiComm / dist.HostComm; None: a world of one), TPM.  The hits must come grouped by locus.
@@ -251,6 +251,9 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     (info.model_info_device) -> "isoform_info": an info.IsoformInfo ("info" is the handle's sizes); "bins" as with_context.
     with_support: the bootstrap's retention, and the drop-one isoform support under the call's keep, built on the device
     (support.model_loo_device) -> "isoform_support": a support.IsoformSupport; "bins" as with_context.
+    with_variational (True, or a dict of alpha / change_limit / max_iter): the bootstrap's retention, and the variational Bayes solve of
+    the call's bins, on the device (vb.model_vb_device) -> "variational": a vb.VariationalFit, and "variational_abundance": its
+    abundance() under the call's epilogue parameters; "bins" as with_context.  The call's own results do not change.
     with_splicing (True, or a splice.SpliceEvents / splice.DeviceSpliceEvents built before: the table is annotation-only): the PSI
     of every annotated exon and intron from the call's d_fpkm / d_keep, built on the device (splice.splice_psi) -> "splicing": a
     splice.SplicePsi; with bootstrap=dict(...) also its mean, variance and interval over the bootstrap's replicates at the bootstrap's
@@ -292,7 +295,7 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     retain = bool(with_context) or bool(with_assignment) or bool(with_coverage) or bool(with_body_profile)
     if retain:
         _lib.check(L.sbgpu_context_table_keep(ctx.h, 1), "sbgpu_context_table_keep")
-    keep_bootstrap = bool(keep_bootstrap) or bootstrap is not None or bool(with_fit) or bool(with_info) or bool(with_support)
+    keep_bootstrap = bool(keep_bootstrap) or bootstrap is not None or bool(with_fit) or bool(with_info) or bool(with_support) or bool(with_variational)
     if keep_bootstrap:
         _lib.check(L.sbgpu_bootstrap_keep(ctx.h, 1), "sbgpu_bootstrap_keep")
     try:
@@ -311,9 +314,9 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
     owner = BinsHandle(L, handle) if keep_handle else None     # (from here on an exception frees the handle with the object)
     info = (C.c_int64 * 8)()
     _lib.check(L.sbgpu_bins_info(handle, info), "sbgpu_bins_info")
-    table = bins = boot = assignment = cov = model_fit = iso_info = iso_support = profile = None
-    if retain or bootstrap is not None or with_fit or with_info or with_support:
-        from . import assign, body, context, coverage, fit, support
+    table = bins = boot = assignment = cov = model_fit = iso_info = iso_support = profile = variational = variational_abundance = None
+    if retain or bootstrap is not None or with_fit or with_info or with_support or with_variational:
+        from . import assign, body, context, coverage, fit, support, vb
         from . import info as isoform_info
         from .bootstrap import abundance_bootstrap_device
         from .exonbin import LocusBins
@@ -334,6 +337,11 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
                 iso_info = isoform_info.model_info_device(ctx, handle, int(out.d_theta), int(out.d_keep), int(out.d_status))
             if with_support:
                 iso_support = support.model_loo_device(ctx, handle, int(out.d_keep), keep=res["keep"][:n_iso])
+            if with_variational:
+                vpar = _lib.sbgpu_abundance_params_t(int(out.total_mapped_reads), par.effective_len_norm, par.filter_by_expression, 0,
+                                                     float(used.mean), par.min_isoform_frac)
+                variational = vb.model_vb_device(ctx, handle, abundance=vpar, **(with_variational if isinstance(with_variational, dict) else {}))
+                variational_abundance = variational.abundance()
         except Exception:
             if owner is None:
                 L.sbgpu_bins_destroy(handle)
@@ -370,6 +378,8 @@ def quantify_resident(annot, hits, insert, read_len, mapped_reads, long_read=Fal
         r.update(isoform_info=iso_info, bins=bins)
     if with_support:
         r.update(isoform_support=iso_support, bins=bins)
+    if with_variational:
+        r.update(variational=variational, variational_abundance=variational_abundance, bins=bins)
     if splicing is not None:
         r["splicing"] = splicing
     if keep_handle:
