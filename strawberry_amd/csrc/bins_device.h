@@ -182,7 +182,7 @@ __global__ __launch_bounds__(kThreads) void bins_locus_kernel(BinsArgs a)
       }
       __syncthreads();
       // ---- pass 2: every hit learns its bin; the first of equal fragments adds its mass
-      int my_used = 0;
+      int my_used = 0, my_over = 0;
       for (int64_t h = q0 + tid; h < q1 && nb > 0; h += kThreads) {
          a.hit_bin_local[h] = -1;
          uint32_t any_c = 0, any_k = 0;
@@ -221,8 +221,12 @@ __global__ __launch_bounds__(kThreads) void bins_locus_kernel(BinsArgs a)
          }
          a.dup[h] = dup ? 1 : 0;
          if (!dup) {
-            if (lds_acc) atomicAdd(&acc_count[b], (int)a.mass[h]);
-            else atomicAdd(&a.bin_count[q0 + b], (int)a.mass[h]);
+            // Masses are whole, non-negative and below 2^24 each (else kBinsFractional stands), so the add that takes a bin's
+            // total to 2^24 sees it: its old value is still exact.  The total itself may wrap past it (512 x 2^23 = 2^32).
+            const float mf = a.mass[h];
+            const int mi = (int)mf;
+            const int old = lds_acc ? atomicAdd(&acc_count[b], mi) : atomicAdd(&a.bin_count[q0 + b], mi);
+            if (mf >= 0.0f && mf < 16777216.0f && (unsigned)old + (unsigned)mi >= 16777216u) my_over = kBinsMassOverflow; // (other masses: kBinsFractional)
          }
       }
       if (lds_acc) {
@@ -235,6 +239,7 @@ __global__ __launch_bounds__(kThreads) void bins_locus_kernel(BinsArgs a)
       if (nb == 0)
          for (int64_t h = q0 + tid; h < q1; h += kThreads) a.hit_bin_local[h] = -1;
       if (my_used) atomicAdd(&n_hits_in, my_used);
+      if (my_over) atomicOr(&bad, my_over);
       __syncthreads();
       if (tid == 0) {
          a.n_bins[l] = (RETRY && overflow) ? -1 : nb;
@@ -250,9 +255,9 @@ __global__ __launch_bounds__(kThreads) void bins_locus_kernel(BinsArgs a)
 // ------------------------------------------------------------------ the single-pass form (round 3)
 // The two-pass kernel above reads a hit's feature offsets and end coordinates twice (gathers: ~150 bytes of traffic
 // per hit) and finds the bin of every earlier hit of a (left, right) run to apply the std::set<Contig> rule.  Two
-// observations remove both: (i) fragments with equal feature sequences have equal key and compat words, hence the
-// same bin, so "an equal fragment already in this bin" is "an equal fragment earlier in the run" -- a question about
-// hits alone; (ii) the exon-bin kernel, which has every hit's features in registers anyway, can leave the run key
+// observations remove both: (i) fragments with equal feature sequences -- codes included -- have equal key and compat
+// words, hence the same bin, so "an equal fragment already in this bin" is "an equal fragment earlier in the run" whose
+// words, read only on such a match, are this hit's (equal coordinates under other codes may enter another bin or none); (ii) the exon-bin kernel, which has every hit's features in registers anyway, can leave the run key
 // (span) and a hash of the sequence per hit.  This kernel then reads 25 coalesced bytes per hit -- key, compat, mass,
 // span, hash -- ONCE: the table entry of a hit's key accumulates mass and compat union by SLOT while the bins are
 // still unranked, the ranking follows, and the per-bin results are written from the slots.  Features are touched
@@ -347,7 +352,7 @@ __global__ __launch_bounds__(kThreads) void bins_accum_kernel(BinsArgs a)
             ++my_used;
             for (int w = 0; w < CW; ++w)
                if (cv[i][w] && (acc_compat[CW * slot + w] & cv[i][w]) != cv[i][w]) atomicOr(&acc_compat[CW * slot + w], cv[i][w]);
-            // std::set<Contig>: an equal fragment earlier in this (left, right) run?  (equal fragments share bin and words)
+            // std::set<Contig>: an equal fragment of this bin earlier in this (left, right) run?
             bool dup = false;
             if (sp1[i] == sp[i] || sp1[i] == 0ull) { // (the common case -- the hit before starts another run -- costs no load)
                for (int64_t p = h - 1; p >= q0 && !dup; --p) {
@@ -357,11 +362,21 @@ __global__ __launch_bounds__(kThreads) void bins_accum_kernel(BinsArgs a)
                      break;
                   }
                   const uint32_t pf = p == h - 1 ? fh1[i] : a.fhash[p];
-                  dup = pf == fh[i] && bins_same_fragment(a, p, h);
+                  if (pf != fh[i] || !bins_same_fragment(a, p, h)) continue;
+                  // Equal (left, right) lists.  Their codes may still differ (a mate gap against an intron of the same
+                  // coordinates) and with them the words: p is in this hit's std::set only if it entered a bin, this one
+                  uint32_t pc = 0;
+                  for (int w = 0; w < CW; ++w) pc |= a.compat[p * CW + w];
+                  const unsigned long long pkey = kw == 2 ? (((unsigned long long)a.key[p * 2 + 1] << 32) | a.key[p * 2]) : (unsigned long long)a.key[p];
+                  dup = pc != 0u && pkey == key[i];
                }
             }
             a.dup[h] = dup ? 1 : 0;
-            if (!dup) atomicAdd(&acc_count[slot], (int)m[i]);
+            if (!dup) { // the add that takes the bin's total to 2^24 flags it (bins_locus_kernel): the total may wrap later
+               const int mi = (int)m[i];
+               const int old = atomicAdd(&acc_count[slot], mi);
+               if (m[i] >= 0.0f && m[i] < 16777216.0f && (unsigned)old + (unsigned)mi >= 16777216u) my_bad |= kBinsMassOverflow; // (other masses: kBinsFractional)
+            }
          }
       }
       if (my_bad) atomicOr(&bad, my_bad);
@@ -511,7 +526,8 @@ __global__ __launch_bounds__(256) void bins_ordered_mass_kernel(BinsArgs a)
             ++n_run;
          }
          flush();
-         if (b < nb) a.bin_count[q0 + b] = (int)sum; // (int) float: estimate.cpp:288
+         // (int) float: estimate.cpp:288 -- where the float is in range; 2^24 stands for everything beyond (bins_pack_kernel flags it)
+         if (b < nb) a.bin_count[q0 + b] = sum < 16777216.0f ? (int)sum : 16777216;
          if (too_long) atomicOr(a.flags, (int)kBinsRunTooLong);
       }
    }

@@ -221,6 +221,7 @@ inline std::string bins_decline_reason(int32_t flags)
    if (flags & kBinsUnsorted) why += " hits of a locus are not sorted by (left, right);";
    if (flags & kBinsFractional) why += " fractional hit masses next to another obstacle;";
    if (flags & kBinsTableFull) why += " a locus has more bins than the LDS table holds;";
+   if (flags & kBinsMassOverflow) why += " a bin's mass reaches 2^24;";
    if (flags & kBinsRunTooLong) why += " fractional masses and more than 48 fragments of one bin starting at one position;";
    return why + " use sbgpu_bins_create";
 }

@@ -699,7 +699,7 @@ int BinsCall::finish_middle()
    const int32_t flags = flags_h[1];
    if (totals_h[0] != rows.row_off[(size_t)nl] || totals_h[1] != rows.f_off[(size_t)nl])
       return api_fail(SBGPU_EHIP, "sbgpu_bins_create_device: device and host prefix sums differ");
-   if (flags & kBinsMassOverflow) return api_fail(SBGPU_EUNSUPPORTED, "sbgpu_bins_create_device: a bin's mass reaches 2^24; use sbgpu_bins_create");
+   if (flags & kBinsMassOverflow) return api_fail(SBGPU_EUNSUPPORTED, bins_decline_reason(kBinsMassOverflow)); // (bins_pack_kernel's: a finished total)
    if (flags & (kPairsNotUnder | kPairsForeignSegment))
       return api_fail(SBGPU_EUNSUPPORTED, "sbgpu_bins_create_device: a bin does not sit under an isoform it is compatible with; sbgpu_bins_create reports the details");
    stage("pack + pairs count");

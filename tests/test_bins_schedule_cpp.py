@@ -263,7 +263,8 @@ int main()
    CHECK(bins_decline_reason(2 | 1) == head + " hits of a locus are not sorted by (left, right); fractional hit masses next to another obstacle;" + tail);
    CHECK(bins_decline_reason(2 | 4 | 128) == head + " fractional hit masses next to another obstacle; a locus has more bins than the LDS table holds;"
                                                     " fractional masses and more than 48 fragments of one bin starting at one position;" + tail);
-   CHECK(bins_decline_reason(8) == head + tail); // (a mass overflow is the middle's flag and has a message of its own)
+   CHECK(bins_decline_reason(8) == head + " a bin's mass reaches 2^24;" + tail); // (the grouping kernels' adds and bins_pack_kernel's totals raise it)
+   CHECK(bins_decline_reason(1 | 8) == head + " hits of a locus are not sorted by (left, right); a bin's mass reaches 2^24;" + tail);
    std::printf("ok\n");
    return 0;
 }

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+from bins_util import bins_arrays, bins_arrays_no_pairs, group_both_ways
 import e2e_util as U
 import exonbin_util as XU
 from test_exonbin_oracle import GOLD, annotation_from_arrays
@@ -218,11 +219,6 @@ def test_segment_basis_form_on_coinciding_boundaries(ctx, oracle):
     assert 0.1 < frac < 0.9, frac                                 # both answers are common
 
 
-def bins_arrays(b):
-    return [b.row_off, b.f_off, b.count, b.bin_key, b.bin_compat, np.asarray(b.hit_bin), b.pair_seg_off, b.pair_seg_lens,
-            b.pair_implicit_mask, b.pair_iso_len, b.pair_out_index]
-
-
 def test_device_grouping_equals_host_grouping(ctx, oracle):
     """sbgpu_bins_create_device vs sbgpu_bins_create on the same words: every array identical.  The input has
     duplicate fragments (equal feature sequences: counted once, the first one's mass), masses above 1, hits
@@ -288,29 +284,6 @@ def test_device_pairs_for_narrow_and_wide_loci_in_one_call(ctx):
     assert (np.diff(bh.row_off) > 64).any() and bh.n_pairs > 10000
     for x, y in zip(bins_arrays(bd), bins_arrays(bh)):
         np.testing.assert_array_equal(x, y)
-
-
-def group_both_ways(ctx, annot, hits, compat, key, want_hit_bin=True, host=None):
-    """(device bins or None, host bins) for arbitrary word arrays (they need not come from the kernel).
-    want_hit_bin=False: the device form is not asked for hit -> bin (its hit_bin stays None); host: bins made earlier."""
-    import ctypes as C
-    import torch
-    from strawberry_amd import exonbin as eb
-    dev = torch.device("cuda", ctx.device)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-    d = {k: up(getattr(hits, k).view(np.int32) if getattr(hits, k).dtype == np.uint32 else getattr(hits, k))
-         for k in ("hit_locus", "feat_off", "feat_code", "feat_left", "feat_right")}
-    d_mass, d_compat, d_key = up(hits.mass), up(compat.view(np.int32)), up(key.view(np.int32))
-    d_hit_bin = torch.zeros(hits.n_hits, dtype=torch.int64, device=dev)
-    from strawberry_amd import _lib
-    ht = _lib.sbgpu_hits_t(hits.n_hits, d["hit_locus"].data_ptr(), d["feat_off"].data_ptr(), d["feat_code"].data_ptr(),
-                           d["feat_left"].data_ptr(), d["feat_right"].data_ptr())
-    bd = eb.LocusBins.on_device(ctx, annot, hits, ht, d_mass.data_ptr(), compat.shape[1], key.shape[1], d_compat.data_ptr(),
-                                d_key.data_ptr(), d_hit_bin.data_ptr() if want_hit_bin else None,
-                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if bd is not None and want_hit_bin:
-        bd.hit_bin = d_hit_bin.cpu().numpy()
-    return bd, host if host is not None else eb.LocusBins(annot, hits, compat, key)
 
 
 def test_device_grouping_multiword_keys_and_table_limit(ctx):
@@ -394,10 +367,6 @@ def test_device_grouping_single_pass_with_a_locus_for_the_big_table(ctx):
     assert nb[1] > 1400 and nb[0] < 1400 and nb[2] < 1400
     for x, y in zip(bins_arrays_no_pairs(bd), bins_arrays_no_pairs(bh)):
         np.testing.assert_array_equal(x, y)
-
-
-def bins_arrays_no_pairs(b):
-    return [b.row_off, b.f_off, b.count, b.bin_key, b.bin_compat, np.asarray(b.hit_bin)]
 
 
 def test_device_grouping_heavy_launch_and_light_table_overflow(ctx):
