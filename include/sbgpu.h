@@ -2166,6 +2166,107 @@ int sbgpu_model_vb_device(sbgpu_ctx_t *ctx, const sbgpu_bins_t *bins, const sbgp
  * (the reduction tree's two levels); [6] the most bins and [7] the most isoforms of one locus.                              */
 int sbgpu_em_vb_limits(int64_t out[8]);
 
+/* ---- the annotation: a GTF file's bytes -> sbgpu_annotation_t, sbgpu_clusters_t, the isoforms' lengths and strands, the names
+ * (sbgpu_gtf_*; csrc/gtf_rules.h codes the line's rule once for both forms, csrc/gtf_host.cpp the rest).
+ * GffReader::readAll over GffLine::GffLine (src/gff.cpp) and Sample::addRef2Cluster (src/alignments.cpp:1025-1079), restated.
+ *
+ * LINES.  The input is the file's bytes.  A line ends at '\n' (the last line need not have one); one '\r' in front of the '\n'
+ * is not part of the line.  Every line gets a status:
+ *   SKIP           shorter than 10 bytes, or its first byte that is not isspace is '#' (gff.cpp:460-462)
+ *   FIELDS         fewer than eight tabs (the line is cut at its first eight)
+ *   OTHER          column 3, ASCII-lower-cased, contains "utr", or does not contain "exon" (:162-166).  Only exon lines build
+ *                  transcripts from a GTF in the reference too: a `transcript` line carries no Parent, so its gene is not found
+ *                  and the mRNA case breaks (:491-495)
+ *   COORD          column 4 or 5 -- each the field's leading run of ASCII digits -- has no digit or a value outside
+ *                  1 .. 2^31 - 1.  end < start: the two are swapped (:134-138)
+ *   NO_TRANSCRIPT  no transcript_id, or an empty one.  GFF3 (ID= / Parent=) is not read: such lines end here
+ *   NO_GENE        no gene_id, or an empty one (gene_name may be empty)
+ *   OK             an exon line of a transcript
+ * Column 6 (the score) is NOT read.  This is the one place where a well-formed file reads differently: the reference's `return`
+ * at :147 stands outside its `if`, so a line with a numeric score never becomes a feature there.  Column 7: '+' is strand 1,
+ * '-' is 2, anything else 0 (the clusters' strand codes).  Column 9: gene_id, transcript_id and gene_name are found as
+ * GffLine::extractAttr finds them (:13-69): a key matches outside double quotes, at the column's start or behind a blank or
+ * ';', its bytes compared ASCII-case-insensitively, and must be followed by a blank or the column's end; the value skips blanks
+ * and one optional opening quote and runs to the closing quote, ';' or the end when it was quoted, to ';' or the end when not.
+ * Each key is looked up in the column's ORIGINAL text: the reference deletes an attribute it found before the next lookup
+ * (:71-77).  A NUL is a byte like any other.  A chromosome, gene or transcript name, or a gene_name, of more than 255 bytes in
+ * a line that would be OK makes both forms return SBGPU_EUNSUPPORTED.
+ *
+ * TRANSCRIPTS.  A transcript is the set of OK lines with one key: chromosome name lower-cased, strand, transcript_id bytes.
+ * Its lines may stand anywhere in the file (the reference keeps one tree per chromosome and one list per strand, and looks a
+ * transcript up by walking that list: :405-448).  Its gene_id and gene_name are those of its first line in the file.  Its exons
+ * are sorted by (left, right); exons that are equal, overlap or touch (next.left <= prev.right + 1) are merged into their union,
+ * and the merges are counted.
+ *
+ * CHROMOSOMES.  With a table of names (n_ref, ref_name: a BAM header's) a chromosome's id is its index in the table, names
+ * compared lower-cased as the reference lower-cases both sides (gff.cpp:118, read.cpp:964,980); a transcript on a chromosome the
+ * table lacks is dropped and counted.  Without a table, ids go by first appearance in the file (alignments.cpp:846-849).
+ *
+ * ORDER.  Transcripts are sorted by (1) chromosome id, (2) the exon coordinates l1, r1, l2, r2, .. compared lexicographically, a
+ * proper prefix first -- Contig::operator< over GenomicFeature::operator< (contig.cpp:186-193,342-347) in exon coordinates --,
+ * (3) first line in the file (the reference's std::sort leaves these ties open).
+ *
+ * LOCI.  A locus is all kept transcripts of one (chromosome id, gene_id bytes as written), its isoforms in the sorted order; loci
+ * are ordered by their first isoform's place in it, so they ascend by (chromosome, left) as sbgpu_assign_reads_* need.  The
+ * reference takes consecutive runs of one gene id, then looks 100 transcripts ahead and adds same-gene transcripts without
+ * consuming them, so they come back as a second cluster: where a gene's transcripts are consecutive in the sorted order the two
+ * rules agree; where they interleave, this rule gives one locus per gene and no duplicate.  Per locus: chromosome, left = min and
+ * right = max over its isoforms, strand = its first isoform's.  Per isoform: iso_len, the sum of its exon lengths, and
+ * iso_strand.  The disjoint segments are sbgpu_segments_host's.  A file without one OK line: SBGPU_OK and zero loci.           */
+#define SBGPU_GTF_OK 0
+#define SBGPU_GTF_SKIP 1
+#define SBGPU_GTF_FIELDS 2
+#define SBGPU_GTF_OTHER 3
+#define SBGPU_GTF_COORD 4
+#define SBGPU_GTF_NO_TRANSCRIPT 5
+#define SBGPU_GTF_NO_GENE 6
+typedef struct sbgpu_gtf sbgpu_gtf_t;
+typedef struct {
+   int64_t n_ref;               /* 0: no table */
+   const char *const *ref_name; /* [n_ref] NUL-terminated */
+   int32_t hash_bits;           /* for tests: 0 means 64, otherwise the device form's key hashes are cut to that many bits */
+} sbgpu_gtf_opts_t;
+/* The names: CSR offsets and bytes (not NUL-separated) of gene_id and gene_name per locus, transcript_id per isoform, and the
+ * chromosome name per id -- the table's where one was given, else as first written in the file.                              */
+typedef struct {
+   const int64_t *gene_id_off, *gene_name_off; /* [n_loci + 1] */
+   const char *gene_id, *gene_name;
+   const int64_t *transcript_id_off;           /* [n_iso + 1]  */
+   const char *transcript_id;
+   const int64_t *chrom_off;                   /* [chromosomes + 1] */
+   const char *chrom;
+} sbgpu_gtf_names_t;
+/* Host form (csrc/gtf_host.cpp; no GPU needed): a hash map whose keys are compared byte by byte; takes a line of any length.
+ * opts may be NULL (no table).  All three forms return a handle that holds HOST arrays.                                      */
+int sbgpu_gtf_read_host(const uint8_t *bytes, int64_t n_bytes, const sbgpu_gtf_opts_t *opts, sbgpu_gtf_t **out);
+/* Device form (csrc/gtf_device.h): the bytes are in HBM, at any alignment.  The line index, the parse -- one lane per line -- and
+ * the grouping of lines into transcripts (two stable radix sorts, by (left, right), then by a 64-bit FNV-1a hash of the
+ * transcript's key, and a pass per transcript that merges its exons and compares every member's key bytes with its first
+ * member's) run on the device; the statuses, a row per transcript, the merged exons and the names come back, and the order, the
+ * loci, the arrays and the segments are built on the host in the host form's code.  Every array, name, status and info word is
+ * the host form's.  SBGPU_EUNSUPPORTED, and the caller uses the host form: a line longer than limits[2] of sbgpu_gtf_limits (its '\r' and '\n' not counted);
+ * 2^31 - 2 lines or more; two transcripts whose keys share a hash -- the text then has the word "collision".  Synchronises on
+ * `stream` (NULL: the context's own) on every way out.                                                                       */
+int sbgpu_gtf_read_device(sbgpu_ctx_t *ctx, const uint8_t *d_bytes, int64_t n_bytes, const sbgpu_gtf_opts_t *opts, void *stream, sbgpu_gtf_t **out);
+/* The device form on host bytes: uploaded through the context's pool first.                                                   */
+int sbgpu_gtf_read_upload(sbgpu_ctx_t *ctx, const uint8_t *bytes, int64_t n_bytes, const sbgpu_gtf_opts_t *opts, void *stream, sbgpu_gtf_t **out);
+/* What the handle holds; every pointer is owned by it and lives until sbgpu_gtf_destroy.  Any out argument may be NULL.
+ * iso_len, iso_strand: [n_iso].                                                                                               */
+int sbgpu_gtf_annotation(const sbgpu_gtf_t *g, sbgpu_annotation_t *annot, sbgpu_clusters_t *clusters, const int32_t **iso_len, const uint8_t **iso_strand);
+int sbgpu_gtf_names(const sbgpu_gtf_t *g, sbgpu_gtf_names_t *names);
+/* info[0] lines; [1 .. 7] lines per status SBGPU_GTF_OK .. SBGPU_GTF_NO_GENE; [8] transcripts kept; [9] loci; [10] exons; [11]
+ * segments; [12] chromosomes; [13] exons the merges took away, over every transcript of the file; [14] transcripts dropped for
+ * their chromosome; [15] 0.                                                                                                   */
+int sbgpu_gtf_info(const sbgpu_gtf_t *g, int64_t info[16]);
+/* a copy of the lines' statuses: status[info[0]] */
+int sbgpu_gtf_line_status(const sbgpu_gtf_t *g, uint8_t *status);
+/* The device form's thresholds (csrc/gtf_schedule.h), for tests that want an input on either side of each: limits[0] lines per
+ * tile of the parse (a wave's pass); [1] bytes of a tile up to which it is staged in LDS, beyond: walked in global memory; [2]
+ * the longest line the device form takes; [3] entries per round of the scan over the tiles' totals; [4] bytes per tile of the
+ * line index; [5] workgroups a kernel's grid is capped at; [6] the longest name; [7] lines from which the device form refuses. */
+int sbgpu_gtf_limits(int64_t limits[8]);
+void sbgpu_gtf_destroy(sbgpu_gtf_t *g);
+
 #ifdef __cplusplus
 }
 #endif

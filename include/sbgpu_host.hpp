@@ -1535,5 +1535,90 @@ class SplicePsi {
    }
 };
 
+/* A GTF annotation read by the library (sbgpu_gtf_*, include/sbgpu.h states the rule).  host(): no GPU.  device(): the file's
+ * bytes are uploaded through the context's pool and parsed and grouped into transcripts on the device; the same arrays, names
+ * and counts come back.  The handle's arrays are the object's: annot() / clusters() point into it and live as long as it does.
+ * ref_names: a BAM header's reference names (empty: chromosome ids by first appearance in the file).                          */
+class GtfAnnotation {
+ public:
+   static GtfAnnotation host(const uint8_t *bytes, int64_t n_bytes, const std::vector<std::string> &ref_names = {})
+   {
+      GtfAnnotation g;
+      const Opts o(ref_names);
+      check(sbgpu_gtf_read_host(bytes, n_bytes, &o.raw, &g.h_), "sbgpu_gtf_read_host");
+      g.load();
+      return g;
+   }
+   static GtfAnnotation device(const Context &ctx, const uint8_t *bytes, int64_t n_bytes, const std::vector<std::string> &ref_names = {}, void *stream = nullptr)
+   {
+      GtfAnnotation g;
+      const Opts o(ref_names);
+      check(sbgpu_gtf_read_upload(ctx.get(), bytes, n_bytes, &o.raw, stream, &g.h_), "sbgpu_gtf_read_upload");
+      g.load();
+      return g;
+   }
+   GtfAnnotation(GtfAnnotation &&o) noexcept { *this = std::move(o); }
+   GtfAnnotation &operator=(GtfAnnotation &&o) noexcept
+   {
+      if (this != &o) {
+         sbgpu_gtf_destroy(h_);
+         h_ = o.h_, o.h_ = nullptr;
+         annot_ = o.annot_, clusters_ = o.clusters_, names_ = o.names_, iso_len_ = o.iso_len_, iso_strand_ = o.iso_strand_;
+         for (int k = 0; k < 16; ++k) info_[k] = o.info_[k];
+      }
+      return *this;
+   }
+   GtfAnnotation(const GtfAnnotation &) = delete;
+   GtfAnnotation &operator=(const GtfAnnotation &) = delete;
+   ~GtfAnnotation() { sbgpu_gtf_destroy(h_); }
+
+   const sbgpu_annotation_t &annot() const { return annot_; }
+   const sbgpu_clusters_t &clusters() const { return clusters_; }
+   const int32_t *iso_len() const { return iso_len_; }
+   const uint8_t *iso_strand() const { return iso_strand_; }
+   int64_t n_loci() const { return annot_.n_loci; }
+   int64_t n_iso() const { return annot_.iso_off[annot_.n_loci]; }
+   int64_t info(int k) const { return info_[k]; } // sbgpu_gtf_info's words
+   std::string gene_id(int64_t locus) const { return std::string(names_.gene_id + names_.gene_id_off[locus], names_.gene_id + names_.gene_id_off[locus + 1]); }
+   std::string gene_name(int64_t locus) const { return std::string(names_.gene_name + names_.gene_name_off[locus], names_.gene_name + names_.gene_name_off[locus + 1]); }
+   std::string transcript_id(int64_t iso) const
+   {
+      return std::string(names_.transcript_id + names_.transcript_id_off[iso], names_.transcript_id + names_.transcript_id_off[iso + 1]);
+   }
+   std::string chrom(int64_t id) const { return std::string(names_.chrom + names_.chrom_off[id], names_.chrom + names_.chrom_off[id + 1]); }
+   std::vector<uint8_t> line_status() const
+   {
+      std::vector<uint8_t> s((size_t)info_[0] + 1);
+      check(sbgpu_gtf_line_status(h_, s.data()), "sbgpu_gtf_line_status");
+      s.pop_back();
+      return s;
+   }
+
+ private:
+   struct Opts {
+      std::vector<const char *> names;
+      sbgpu_gtf_opts_t raw;
+      explicit Opts(const std::vector<std::string> &ref_names)
+      {
+         for (const std::string &n : ref_names) names.push_back(n.c_str());
+         raw.n_ref = (int64_t)names.size(), raw.ref_name = names.empty() ? nullptr : names.data(), raw.hash_bits = 0;
+      }
+   };
+   GtfAnnotation() {}
+   void load()
+   {
+      check(sbgpu_gtf_annotation(h_, &annot_, &clusters_, &iso_len_, &iso_strand_), "sbgpu_gtf_annotation");
+      check(sbgpu_gtf_names(h_, &names_), "sbgpu_gtf_names");
+      check(sbgpu_gtf_info(h_, info_), "sbgpu_gtf_info");
+   }
+   sbgpu_gtf_t *h_ = nullptr;
+   sbgpu_annotation_t annot_{};
+   sbgpu_clusters_t clusters_{};
+   sbgpu_gtf_names_t names_{};
+   const int32_t *iso_len_ = nullptr;
+   const uint8_t *iso_strand_ = nullptr;
+   int64_t info_[16] = {};
+};
+
 } // namespace sbgpu
 #endif /* SBGPU_HOST_HPP_ */

@@ -61,6 +61,8 @@ SYMBOLS = [
     "sbgpu_splice_events_shapes_host", "sbgpu_splice_events_build_host", "sbgpu_splice_psi_host", "sbgpu_splice_support_host",
     "sbgpu_splice_psi_device", "sbgpu_splice_support_device", "sbgpu_splice_limits",
     "sbgpu_em_vb_host", "sbgpu_em_vb_device", "sbgpu_model_vb_device", "sbgpu_em_vb_limits",
+    "sbgpu_gtf_read_host", "sbgpu_gtf_read_device", "sbgpu_gtf_read_upload", "sbgpu_gtf_annotation", "sbgpu_gtf_names", "sbgpu_gtf_info",
+    "sbgpu_gtf_line_status", "sbgpu_gtf_limits", "sbgpu_gtf_destroy",
 ]
 
 
@@ -270,6 +272,17 @@ class sbgpu_locus_bootstrap_t(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in _NAMES] + [("d_" + n, C.c_void_p) for n in _NAMES] +
                 [("n_iso", C.c_int64), ("n_loci", C.c_int64), ("n_rep", C.c_int32), ("reserved", C.c_int32)])
 
+
+class sbgpu_gtf_opts_t(C.Structure):
+    _fields_ = [("n_ref", C.c_int64), ("ref_name", C.POINTER(C.c_char_p)), ("hash_bits", C.c_int32)]
+
+
+class sbgpu_gtf_names_t(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("gene_id_off", "gene_name_off", "gene_id", "gene_name", "transcript_id_off", "transcript_id",
+                                          "chrom_off", "chrom")]
+
+
+GTF_STATUS_NAMES = ["OK", "SKIP", "FIELDS", "OTHER", "COORD", "NO_TRANSCRIPT", "NO_GENE"]
 
 _lib = None
 
@@ -487,6 +500,16 @@ def load():
     L.sbgpu_em_vb_device.argtypes = [vp, vp, vp, vp, C.POINTER(sbgpu_vb_params_t), vp, C.POINTER(sbgpu_em_vb_t)]
     L.sbgpu_model_vb_device.argtypes = [vp, vp, C.POINTER(sbgpu_vb_params_t), vp, C.POINTER(sbgpu_em_vb_t)]
     L.sbgpu_em_vb_limits.argtypes = [C.POINTER(C.c_int64)]
+    L.sbgpu_gtf_read_host.argtypes = [vp, C.c_int64, C.POINTER(sbgpu_gtf_opts_t), C.POINTER(vp)]
+    L.sbgpu_gtf_read_device.argtypes = [vp, vp, C.c_int64, C.POINTER(sbgpu_gtf_opts_t), vp, C.POINTER(vp)]
+    L.sbgpu_gtf_read_upload.argtypes = [vp, vp, C.c_int64, C.POINTER(sbgpu_gtf_opts_t), vp, C.POINTER(vp)]
+    L.sbgpu_gtf_annotation.argtypes = [vp, C.POINTER(sbgpu_annotation_t), C.POINTER(sbgpu_clusters_t), C.POINTER(vp), C.POINTER(vp)]
+    L.sbgpu_gtf_names.argtypes = [vp, C.POINTER(sbgpu_gtf_names_t)]
+    L.sbgpu_gtf_info.argtypes = [vp, i64p]
+    L.sbgpu_gtf_line_status.argtypes = [vp, vp]
+    L.sbgpu_gtf_limits.argtypes = [i64p]
+    L.sbgpu_gtf_destroy.argtypes = [vp]
+    L.sbgpu_gtf_destroy.restype = None
     L.sbgpu_bootstrap_counts_host.argtypes = [C.c_int64, vp, vp, vp, C.c_uint64, C.c_int32, vp]
     L.sbgpu_bootstrap_counts_device.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp]
     L.sbgpu_em_bootstrap_device.argtypes = [vp, vp, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp, vp, vp, vp, vp, vp]
