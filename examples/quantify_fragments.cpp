@@ -29,6 +29,7 @@
 #include <cstdio>
 #include <fstream>
 #include <iostream>
+#include <iterator>
 #include <map>
 #include <sstream>
 #include <string>
@@ -232,18 +233,25 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "genome.fa: this driver takes one chromosome per run (header `chrom %s`, a locus on %s)\n", chrom.c_str(), gc.c_str());
             return 2;
          }
-      std::ifstream fa(argv[4]);
+      std::ifstream fa(argv[4], std::ios::binary);
       if (!fa) {
          std::fprintf(stderr, "cannot open %s\n", argv[4]);
          return 2;
       }
-      std::string genome, line;
-      bool mine = false;
-      while (std::getline(fa, line)) {
-         if (!line.empty() && line[0] == '>')
-            mine = line.substr(1, line.find_first_of(" \t") == std::string::npos ? std::string::npos : line.find_first_of(" \t") - 1) == chrom;
-         else if (mine)
-            genome += line;
+      // the library's reader (sbgpu::FastaGenome): the run's chromosome by name, out of a FASTA of any number of contigs
+      const std::string fa_bytes((std::istreambuf_iterator<char>(fa)), std::istreambuf_iterator<char>());
+      std::string genome;
+      try {
+         const sbgpu::FastaGenome fasta = sbgpu::FastaGenome::host((const uint8_t *)fa_bytes.data(), (int64_t)fa_bytes.size());
+         const int64_t contig = fasta.find(chrom);
+         if (contig < 0) {
+            std::fprintf(stderr, "%s: no contig named %s among its %lld\n", argv[4], chrom.c_str(), (long long)fasta.n_contigs());
+            return 2;
+         }
+         genome = fasta.sequence(contig);
+      } catch (const std::exception &e) {
+         std::fprintf(stderr, "error: %s\n", e.what());
+         return 1;
       }
       try {
          sbgpu::Context ctx(rank % std::max(1, sbgpu_device_count()));

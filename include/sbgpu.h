@@ -2267,6 +2267,100 @@ int sbgpu_gtf_line_status(const sbgpu_gtf_t *g, uint8_t *status);
 int sbgpu_gtf_limits(int64_t limits[8]);
 void sbgpu_gtf_destroy(sbgpu_gtf_t *g);
 
+/* ---- the genome: a FASTA file's bytes -> the contigs' names, their sequences packed back to back, and a .fai index
+ * (sbgpu_fasta_*; csrc/fasta_rules.h holds what both forms share, csrc/fasta_host.cpp the host form and the handle).
+ * The reference cannot build an index (FaIndex::buildIndex is a stub, src/fasta.cpp:86-89; without a .fai it shells out to
+ * `samtools faidx`, :286-291) and reads a sequence line by line through one (FaSeqGetter::loadSeq, :132-193).
+ *
+ * LINES.  The input is the file's bytes.  A line ends at '\n' (the last line need not have one); one '\r' directly in front of the
+ * '\n' is the terminator's, not the line's.  A NUL is a byte like any other.
+ *
+ * HEADERS.  A header is a line whose first byte is '>'; it opens a contig.  The contig's name is the bytes behind '>' up to the
+ * first byte for which C's isspace holds, or up to the line's end; the rest of the line is not kept.  Empty lines in front of the
+ * first header are skipped; a non-empty one makes both forms return SBGPU_EINVAL, and the text carries that line's byte offset.
+ * No header at all, or zero bytes: SBGPU_OK and zero contigs.
+ *
+ * SEQUENCE.  A contig's sequence is every byte of every line between its header and the next header (or the end), as it stands:
+ * no case folding and no filtering (the bin statistics code the bytes, and loadSeq copies them raw too).  All contigs' sequences
+ * are packed back to back in file order; seq_off[n_contigs + 1] bounds them, length[c] = seq_off[c + 1] - seq_off[c].
+ *
+ * INDEX.  Per contig the five .fai columns: the name, the length, `offset` -- the byte behind the header line's terminator --,
+ * `line_bases` -- the length of the first line behind the header -- and `line_width` -- line_bases plus the terminator bytes that
+ * line actually has (0, 1 or 2).
+ *
+ * FLAGS.  One byte per contig:
+ *   EMPTY      no base; line_bases = line_width = 0 (the reference exits on these, fasta.cpp:140-143)
+ *   RAGGED     the lines behind the header are NOT, in this order: k >= 0 lines of exactly line_bases bytes, each with the first
+ *              line's terminator; at most one line of 1 .. line_bases bytes with any terminator or none; any number of empty
+ *              lines.  (A first line of length 0 followed by bases is RAGGED.)  The sequence is still packed and exact; only the
+ *              index arithmetic does not hold
+ *   DUPLICATE  an earlier contig has this name under the lookup's comparison
+ *   NONAME     the name is empty
+ * For a contig that is neither EMPTY nor RAGGED and every p in 1 .. length,
+ *   file[offset + ((p - 1) / line_bases) * line_width + (p - 1) % line_bases] == seq[seq_off[c] + p - 1]
+ * which is loadSeq's arithmetic (fasta.cpp:144-146).
+ *
+ * LOOKUP.  sbgpu_fasta_find compares names ASCII-lower-cased on both sides, as the GTF reader compares chromosome names with a BAM
+ * header's; the first match in file order wins.  This deviates from the reference, which compares the FASTA's name as written
+ * with the GTF's lower-cased one: `Chr1` in a FASTA is never found there.                                                     */
+#define SBGPU_FASTA_EMPTY 1
+#define SBGPU_FASTA_RAGGED 2
+#define SBGPU_FASTA_DUPLICATE 4
+#define SBGPU_FASTA_NONAME 8
+typedef struct sbgpu_fasta sbgpu_fasta_t;
+/* Host form (csrc/fasta_host.cpp; no GPU needed): line by line; takes lines and headers of any length.  The packed sequence is in
+ * host memory.                                                                                                               */
+int sbgpu_fasta_read_host(const uint8_t *bytes, int64_t n_bytes, sbgpu_fasta_t **out);
+/* Device form (csrc/fasta_device.h): the bytes are in HBM, at any alignment.  A stream compaction over tiles of limits[0] bytes:
+ * the headers are counted, scanned and walked (a wave per header line); the bases are counted per tile, scanned in 64 bits and
+ * packed by popcount prefix.  No array has an entry per line, and an unwrapped contig is read like a wrapped one.  The packed
+ * sequence stays in HBM, owned by the handle; the index columns, flags, seq_off and names come back to the host, and every
+ * array, flag, name and info word is the host form's.  SBGPU_EUNSUPPORTED, and the caller uses the host form: a header line
+ * longer than limits[3] of sbgpu_fasta_limits ('>' counted, its '\r' and '\n' not) -- the text then has the words "header line"
+ * --, or more than limits[4] contigs.  Synchronises on `stream` (NULL: the context's own) on every way out.                    */
+int sbgpu_fasta_read_device(sbgpu_ctx_t *ctx, const uint8_t *d_bytes, int64_t n_bytes, void *stream, sbgpu_fasta_t **out);
+/* The device form on host bytes: uploaded through the context's pool first.                                                   */
+int sbgpu_fasta_read_upload(sbgpu_ctx_t *ctx, const uint8_t *bytes, int64_t n_bytes, void *stream, sbgpu_fasta_t **out);
+/* info[0] bytes; [1] lines; [2] contigs; [3] bases; [4 .. 7] contigs with EMPTY, RAGGED, DUPLICATE, NONAME; [8] the longest
+ * contig's length and [9] its index (the first of equals; -1 without a contig); [10] 1 where the sequence is on a device and
+ * [11] that device (-1: the host); [12 .. 15] 0.                                                                              */
+int sbgpu_fasta_info(const sbgpu_fasta_t *g, int64_t info[16]);
+/* What the handle holds; every pointer is owned by it and lives until sbgpu_fasta_destroy.  Any out argument may be NULL.
+ * seq_off: [contigs + 1]; offset, line_bases, line_width, flags: [contigs].  The names: CSR offsets [contigs + 1] plus bytes
+ * (not NUL-separated).  The sequence: seq_off[contigs] bytes, in HBM where *on_device comes back 1.                          */
+int sbgpu_fasta_index(const sbgpu_fasta_t *g, const int64_t **seq_off, const int64_t **offset, const int64_t **line_bases, const int64_t **line_width,
+                      const uint8_t **flags);
+int sbgpu_fasta_names(const sbgpu_fasta_t *g, const int64_t **name_off, const char **names);
+int sbgpu_fasta_sequence(const sbgpu_fasta_t *g, const uint8_t **seq, int32_t *on_device);
+/* *contig: the first contig of that name (name_len bytes, compared lower-cased), -1 where there is none                        */
+int sbgpu_fasta_find(const sbgpu_fasta_t *g, const char *name, int64_t name_len, int64_t *contig);
+/* The .fai text: one line per contig in file order, name\tlength\toffset\tline_bases\tline_width\n.  EMPTY contigs are left out
+ * (the reference's loader rejects such a line, fasta.cpp:72); a RAGGED or NONAME contig makes it return SBGPU_EUNSUPPORTED, the
+ * text names the contig.  *need: the text's bytes (no NUL is written); buf may be NULL to ask for it, cap < *need: SBGPU_EINVAL. */
+int sbgpu_fasta_fai(const sbgpu_fasta_t *g, char *buf, int64_t cap, int64_t *need);
+/* `len` bases of contig `contig` from base `start` (1-based) to host memory; from a handle on a device: a synchronous copy.  A
+ * window outside the contig: SBGPU_EINVAL.                                                                                    */
+int sbgpu_fasta_fetch(const sbgpu_fasta_t *g, int64_t contig, int64_t start, int64_t len, uint8_t *out);
+/* The device form's thresholds (csrc/fasta_schedule.h), for tests that want an input on either side of each: limits[0] bytes per
+ * tile; [1] entries per round of the scans; [2] workgroups a kernel's grid is capped at (a tile each per round); [3] the longest
+ * header line the device form takes; [4] the most contigs; [5 .. 7] 0.                                                        */
+int sbgpu_fasta_limits(int64_t limits[8]);
+void sbgpu_fasta_destroy(sbgpu_fasta_t *g);
+/* `-b genome.fa` over every chromosome of an annotation: the per-bin sequence statistics above with the genome taken from a
+ * handle.  Bins run_off[r] .. run_off[r + 1] - 1 lie on contig run_contig[r] (host arrays; run_off ascends from 0 to n_bins;
+ * the runs' contigs may come in any order); one launch of the same kernel per run, with the contig's packed sequence as the
+ * genome (genome_start 1, genome_len its length); the per-bin arrays are advanced by run_off[r], the coordinate arrays are
+ * indexed absolutely.  The handle must hold its sequence on the context's device, and a run must not lie on an EMPTY contig, else
+ * SBGPU_EINVAL; a contig of 2^32 bases or more in a run: SBGPU_ESHAPE.  Asynchronous on `stream` like the entry above.         */
+int sbgpu_binseq_fasta_device(sbgpu_ctx_t *ctx, const sbgpu_fasta_t *g, int64_t n_runs, const int64_t *run_off, const int32_t *run_contig, int64_t n_bins,
+                              const int64_t *d_seg_off, const uint32_t *d_seg_left, const uint32_t *d_seg_right, double *d_gc, double *d_entropy,
+                              uint8_t *d_flags, int32_t *d_error, void *stream);
+/* The same with host arrays and either kind of handle: validates as the host-buffer form above does, and per run calls it on the
+ * contig's window from the first base the run's segments touch to the last.                                                   */
+int sbgpu_binseq_fasta_host(sbgpu_ctx_t *ctx, const sbgpu_fasta_t *g, int64_t n_runs, const int64_t *run_off, const int32_t *run_contig, int64_t n_bins,
+                            const int64_t *seg_off, const uint32_t *seg_left, const uint32_t *seg_right, double *gc_out, double *entropy_out,
+                            uint8_t *flags_out);
+
 #ifdef __cplusplus
 }
 #endif

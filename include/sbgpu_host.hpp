@@ -1620,5 +1620,110 @@ class GtfAnnotation {
    int64_t info_[16] = {};
 };
 
+/* A genome FASTA read by the library (sbgpu_fasta_*, include/sbgpu.h states the rule).  host(): no GPU, the packed sequence is
+ * in host memory.  device(): the file's bytes are uploaded through the context's pool and packed on the device, where the
+ * sequence stays -- the genome of binseq_device().  The index arrays point into the handle and live as long as the object.    */
+class FastaGenome {
+ public:
+   static FastaGenome host(const uint8_t *bytes, int64_t n_bytes)
+   {
+      FastaGenome g;
+      check(sbgpu_fasta_read_host(bytes, n_bytes, &g.h_), "sbgpu_fasta_read_host");
+      g.load();
+      return g;
+   }
+   static FastaGenome device(const Context &ctx, const uint8_t *bytes, int64_t n_bytes, void *stream = nullptr)
+   {
+      FastaGenome g;
+      check(sbgpu_fasta_read_upload(ctx.get(), bytes, n_bytes, stream, &g.h_), "sbgpu_fasta_read_upload");
+      g.load();
+      return g;
+   }
+   FastaGenome(FastaGenome &&o) noexcept { *this = std::move(o); }
+   FastaGenome &operator=(FastaGenome &&o) noexcept
+   {
+      if (this != &o) {
+         sbgpu_fasta_destroy(h_);
+         h_ = o.h_, o.h_ = nullptr;
+         seq_off_ = o.seq_off_, offset_ = o.offset_, line_bases_ = o.line_bases_, line_width_ = o.line_width_, name_off_ = o.name_off_;
+         flags_ = o.flags_, names_ = o.names_;
+         for (int k = 0; k < 16; ++k) info_[k] = o.info_[k];
+      }
+      return *this;
+   }
+   FastaGenome(const FastaGenome &) = delete;
+   FastaGenome &operator=(const FastaGenome &) = delete;
+   ~FastaGenome() { sbgpu_fasta_destroy(h_); }
+
+   const sbgpu_fasta_t *get() const { return h_; }
+   int64_t n_contigs() const { return info_[2]; }
+   int64_t info(int k) const { return info_[k]; } // sbgpu_fasta_info's words
+   bool on_device() const { return info_[10] != 0; }
+   std::string name(int64_t c) const { return std::string(names_ + name_off_[c], names_ + name_off_[c + 1]); }
+   int64_t length(int64_t c) const { return seq_off_[c + 1] - seq_off_[c]; }
+   int64_t offset(int64_t c) const { return offset_[c]; }
+   int64_t line_bases(int64_t c) const { return line_bases_[c]; }
+   int64_t line_width(int64_t c) const { return line_width_[c]; }
+   uint8_t flags(int64_t c) const { return flags_[c]; }
+   const int64_t *seq_off() const { return seq_off_; }
+   /* the first contig of that name, compared ASCII-lower-cased; -1: none */
+   int64_t find(const std::string &name) const
+   {
+      int64_t c = -1;
+      check(sbgpu_fasta_find(h_, name.data(), (int64_t)name.size(), &c), "sbgpu_fasta_find");
+      return c;
+   }
+   /* `len` bases of contig c from base `start` (1-based) */
+   std::string fetch(int64_t c, int64_t start, int64_t len) const
+   {
+      std::string s((size_t)(len > 0 ? len : 0), '\0');
+      check(sbgpu_fasta_fetch(h_, c, start, len, s.empty() ? nullptr : (uint8_t *)&s[0]), "sbgpu_fasta_fetch");
+      return s;
+   }
+   std::string sequence(int64_t c) const { return fetch(c, 1, length(c)); }
+   std::string fai_text() const
+   {
+      int64_t need = 0;
+      check(sbgpu_fasta_fai(h_, nullptr, 0, &need), "sbgpu_fasta_fai");
+      std::string s((size_t)need, '\0');
+      if (need) check(sbgpu_fasta_fai(h_, &s[0], need, &need), "sbgpu_fasta_fai");
+      return s;
+   }
+   /* `-b` over chromosomes with host arrays (sbgpu_binseq_fasta_host): bins [run_off[r], run_off[r + 1]) lie on contig run_contig[r] */
+   void binseq(const Context &ctx, const std::vector<int64_t> &run_off, const std::vector<int32_t> &run_contig, const std::vector<int64_t> &seg_off,
+               const std::vector<uint32_t> &seg_left, const std::vector<uint32_t> &seg_right, std::vector<double> &gc, std::vector<double> &entropy,
+               std::vector<uint8_t> &flags) const
+   {
+      const int64_t n_bins = (int64_t)seg_off.size() - 1;
+      gc.assign((size_t)n_bins, 0.0), entropy.assign((size_t)n_bins, 0.0), flags.assign((size_t)n_bins, 0);
+      check(sbgpu_binseq_fasta_host(ctx.get(), h_, (int64_t)run_contig.size(), run_off.data(), run_contig.data(), n_bins, seg_off.data(), seg_left.data(),
+                                    seg_right.data(), gc.data(), entropy.data(), flags.data()),
+            "sbgpu_binseq_fasta_host");
+   }
+   /* the same on device arrays, with the sequence resident (sbgpu_binseq_fasta_device) */
+   void binseq_device(const Context &ctx, const std::vector<int64_t> &run_off, const std::vector<int32_t> &run_contig, int64_t n_bins, const int64_t *d_seg_off,
+                      const uint32_t *d_seg_left, const uint32_t *d_seg_right, double *d_gc, double *d_entropy, uint8_t *d_flags, int32_t *d_error,
+                      void *stream = nullptr) const
+   {
+      check(sbgpu_binseq_fasta_device(ctx.get(), h_, (int64_t)run_contig.size(), run_off.data(), run_contig.data(), n_bins, d_seg_off, d_seg_left, d_seg_right,
+                                      d_gc, d_entropy, d_flags, d_error, stream),
+            "sbgpu_binseq_fasta_device");
+   }
+
+ private:
+   FastaGenome() {}
+   void load()
+   {
+      check(sbgpu_fasta_index(h_, &seq_off_, &offset_, &line_bases_, &line_width_, &flags_), "sbgpu_fasta_index");
+      check(sbgpu_fasta_names(h_, &name_off_, &names_), "sbgpu_fasta_names");
+      check(sbgpu_fasta_info(h_, info_), "sbgpu_fasta_info");
+   }
+   sbgpu_fasta_t *h_ = nullptr;
+   const int64_t *seq_off_ = nullptr, *offset_ = nullptr, *line_bases_ = nullptr, *line_width_ = nullptr, *name_off_ = nullptr;
+   const uint8_t *flags_ = nullptr;
+   const char *names_ = nullptr;
+   int64_t info_[16] = {};
+};
+
 } // namespace sbgpu
 #endif /* SBGPU_HOST_HPP_ */

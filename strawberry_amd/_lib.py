@@ -63,6 +63,9 @@ SYMBOLS = [
     "sbgpu_em_vb_host", "sbgpu_em_vb_device", "sbgpu_model_vb_device", "sbgpu_em_vb_limits",
     "sbgpu_gtf_read_host", "sbgpu_gtf_read_device", "sbgpu_gtf_read_upload", "sbgpu_gtf_annotation", "sbgpu_gtf_names", "sbgpu_gtf_info",
     "sbgpu_gtf_line_status", "sbgpu_gtf_limits", "sbgpu_gtf_destroy",
+    "sbgpu_fasta_read_host", "sbgpu_fasta_read_device", "sbgpu_fasta_read_upload", "sbgpu_fasta_info", "sbgpu_fasta_index", "sbgpu_fasta_names",
+    "sbgpu_fasta_sequence", "sbgpu_fasta_find", "sbgpu_fasta_fai", "sbgpu_fasta_fetch", "sbgpu_fasta_limits", "sbgpu_fasta_destroy",
+    "sbgpu_binseq_fasta_device", "sbgpu_binseq_fasta_host",
 ]
 
 
@@ -510,6 +513,21 @@ def load():
     L.sbgpu_gtf_limits.argtypes = [i64p]
     L.sbgpu_gtf_destroy.argtypes = [vp]
     L.sbgpu_gtf_destroy.restype = None
+    L.sbgpu_fasta_read_host.argtypes = [vp, C.c_int64, C.POINTER(vp)]
+    L.sbgpu_fasta_read_device.argtypes = [vp, vp, C.c_int64, vp, C.POINTER(vp)]
+    L.sbgpu_fasta_read_upload.argtypes = [vp, vp, C.c_int64, vp, C.POINTER(vp)]
+    L.sbgpu_fasta_info.argtypes = [vp, i64p]
+    L.sbgpu_fasta_index.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.sbgpu_fasta_names.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.sbgpu_fasta_sequence.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32)]
+    L.sbgpu_fasta_find.argtypes = [vp, C.c_char_p, C.c_int64, i64p]
+    L.sbgpu_fasta_fai.argtypes = [vp, vp, C.c_int64, i64p]
+    L.sbgpu_fasta_fetch.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, vp]
+    L.sbgpu_fasta_limits.argtypes = [i64p]
+    L.sbgpu_fasta_destroy.argtypes = [vp]
+    L.sbgpu_fasta_destroy.restype = None
+    L.sbgpu_binseq_fasta_device.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.sbgpu_binseq_fasta_host.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
     L.sbgpu_bootstrap_counts_host.argtypes = [C.c_int64, vp, vp, vp, C.c_uint64, C.c_int32, vp]
     L.sbgpu_bootstrap_counts_device.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp]
     L.sbgpu_em_bootstrap_device.argtypes = [vp, vp, vp, vp, C.POINTER(sbgpu_bootstrap_params_t), vp, vp, vp, vp, vp, vp, vp]

@@ -193,6 +193,32 @@ def write_genome(rng, length, out_dir):
         f.write("chr1\t%d\t6\t60\t61\n" % length)
 
 
+def write_genome_chroms(rng, length, out_dir, chroms=(("chr1", 60), ("chr2", 50))):
+    """genome.fa with one contig per chromosome, each wrapped at its own width, and the genome.fa.fai this library's reader
+    writes for it (strawberry_amd.fasta, the host form): the reference then reads the sequence through an index built here."""
+    from strawberry_amd.fasta import read_fasta
+    alphabet = np.frombuffer(b"ACGT", np.uint8)
+    path = os.path.join(out_dir, "genome.fa")
+    with open(path, "w") as f:
+        for name, width in chroms:
+            seq = np.empty(length, np.uint8)
+            at = 0
+            while at < length:                   # stretches of 30-300 bases, each with its own GC content
+                n = int(rng.integers(30, 300))
+                gc = float(rng.choice([0.15, 0.35, 0.5, 0.65, 0.85, 0.95]))
+                p = np.array([(1 - gc) / 2, gc / 2, gc / 2, (1 - gc) / 2])
+                seq[at:at + n] = rng.choice(alphabet, size=n, p=p)[:length - at]
+                at += n
+            seq[rng.random(length) < 0.08] |= 0x20
+            seq[rng.random(length) < 0.01] = ord("N")
+            text = seq.tobytes().decode()
+            f.write(">%s\n" % name)
+            for i in range(0, length, width):
+                f.write(text[i:i + width] + "\n")
+    with open(path + ".fai", "w") as f:
+        f.write(read_fasta(path).fai_text())
+
+
 def main():
     build(with_ref=True)
     only = sys.argv[1:]
@@ -237,6 +263,10 @@ def main():
     # e2e_toy_chroms: the genes alternate between two chromosomes: the mapped-read total runs over both
     #          (alignments.cpp:1372) and the output is written chromosome by chromosome.
     make("e2e_toy_chroms", 4949, 150, 500, chroms=2)
+    # e2e_bias_chroms: `-b genome.fa` over two chromosomes.  The genome's two contigs are wrapped at 60 and at 50 bases, and
+    #          its .fai is the one strawberry_amd.fasta writes: the reference reads every bin's sequence through an index this
+    #          library built, and the library's reader reproduces the reference's six columns.
+    make("e2e_bias_chroms", 5050, 60, 400, chroms=2, genome="chroms", plain_header=True)
     # e2e_toy_assembly (BASELINE config 4 / C1 plumbing): the reference in its DEFAULT mode -- no -g, no -r: the first pass
     #          assembles transcripts from the reads (assembleSample, alignments.cpp:1658), the second quantifies the
     #          ASSEMBLED contigs (reset_refmRNAs, alignments.cpp:1091-1101) with kMinIsoformFrac = 0.01, so the post-EM
@@ -326,7 +356,7 @@ def make_c4_em_golden():
 
 
 def make(name, seed, ex_lo, ex_hi, dup=0.0, multi=0.0, extra=(), insert=True, single=False, long_reads=False, n_frags=900,
-         genome=False, minus=False, chroms=1, assembly=False):
+         genome=False, minus=False, chroms=1, assembly=False, plain_header=False):
     rng = np.random.Generator(np.random.PCG64(seed))
     genes, chrom_len = make_annotation(rng, 6, ex_lo, ex_hi)
     if minus:
@@ -350,7 +380,10 @@ def make(name, seed, ex_lo, ex_hi, dup=0.0, multi=0.0, extra=(), insert=True, si
         bam = os.path.join(tmp, "toy.bam")
         subprocess.check_call([SAM2BAM, sam, bam])
         extra = list(extra)
-        if genome:
+        if genome == "chroms":
+            write_genome_chroms(rng, chrom_len + 500, tmp)
+            extra += ["-b", "genome.fa"]
+        elif genome:
             write_genome(rng, chrom_len + 500, tmp)
             extra += ["-b", "genome.fa"]
         cmd = [REF_BIN, bam] + ([] if assembly else ["-g", gtf, "-r"]) + (["-i", "%d/%d" % (MEAN, SD)] if insert else []) + ["-o", os.path.join(tmp, "out.gtf"),
@@ -361,6 +394,10 @@ def make(name, seed, ex_lo, ex_hi, dup=0.0, multi=0.0, extra=(), insert=True, si
         r.check_returncode()
         for name in ("toy.gtf", "out.gtf", "ctx.tsv") + (("genome.fa",) if genome else ()):
             data = open(os.path.join(tmp, name)).read()
+            if plain_header and name == "out.gtf" and data.startswith("#"):
+                # the program writes its command line into the first line: keep the words, not where the files lay
+                first, rest = data.split("\n", 1)
+                data = "#" + " ".join(os.path.basename(w) if w.startswith("/") else w for w in first[1:].split(" ")) + "\n" + rest
             open(os.path.join(out_dir, name), "w").write(data)
         with open(os.path.join(out_dir, "theta_log.txt"), "w") as f:
             for line in open(os.path.join(tmp, "log.txt")):
